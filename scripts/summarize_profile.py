@@ -45,7 +45,7 @@ for cfg in (2, 4, 5, 6):
                 if cs is not None: u += ce - cs
                 union[name] = u
         with open(os.path.join(out_dir, ROUND + "_config%d_kernel_stats.csv" % cfg), "w") as f:
-            f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --config %d --steps 1 --warmup %d --cpu-sample 0 [--also none] --plain   (durations in ns; vgpr = the trace record's arch_vgpr field, NOT the allocation: the code objects say 72 for k_fill<10,frame>)\n" % (cfg, 0 if cfg == 5 else 1))
+            f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --config %d --steps 1 --warmup %d --cpu-sample 0 [--also none] --plain --full   (durations in ns; vgpr = the trace record's arch_vgpr field, NOT the allocation: the code objects say 72 for k_fill<10,frame>)\n" % (cfg, 0 if cfg == 5 else 1))
             f.write("# union_ns: wall time with at least one dispatch of the kernel running.  The fill launches of a bucket that needs several of them are PIPELINED since round 6 (main stream / a second\n")
             f.write("# stream alternately): their durations overlap, total_ns and avg_ns count waiting -- union_ns / passes over the batch is the fill time bench.py brackets with HIP events (roofline.launch_ms x launches).\n")
             f.write("kernel,calls,total_ns,avg_ns,min_ns,max_ns,percent,vgpr,sgpr,lds_bytes,max_grid_x,workgroup_x,union_ns\n")
@@ -63,7 +63,7 @@ PASSES = {2: 2, 4: 2, 5: 3}
 alns = {2: 16000 * PASSES[2], 4: 10000 * PASSES[4], 5: 8192 * 2048 * PASSES[5]}
 dominant = {2: "k_fill", 4: "k_chainq", 5: "k_filldb"}
 with open(os.path.join(out_dir, ROUND + "_pmc.csv"), "w") as f:
-    f.write("# rocprofv3 --pmc <counters> -- python bench.py --config N (config 2: 16000 reads, config 4: full size, config 5: 8192 x 2048), one pass per counter group\n")
+    f.write("# rocprofv3 --pmc <counters> -- python bench.py --full --config N (config 2: 16000 reads, config 4: full size, config 5: 8192 x 2048), one pass per counter group\n")
     f.write("pass,kernel,counter,dispatches,sum,avg_per_dispatch,avg_dispatch_ns\n")
     sums = {}
     for d in dbs("pmc*"):

@@ -217,6 +217,20 @@ def cli_goldens():
     print("example goldens: 2")
 
 
+def blosum50_golden():
+    """the BLOSUM50 table of the reference CLI (src/main.c, mat50[], 24 x 24 in the order ARNDCQEGHILKMFPSTWYVBZX*), as data"""
+    src = open(os.path.join(os.path.dirname(DEMO), "src", "main.c")).read()
+    body = src[src.index("mat50[] = {"):src.index("};", src.index("mat50[] = {"))]
+    body = re.sub(r"//[^\n]*", "", body.split("{", 1)[1])
+    vals = [int(x) for x in re.findall(r"-?\d+", body)]
+    assert len(vals) == 24 * 24
+    with open(os.path.join(HERE, "blosum50_reference.json"), "w") as f:
+        json.dump({"generator": "tests/golden/make_golden.py", "source": "reference src/main.c mat50[]", "order": "ARNDCQEGHILKMFPSTWYVBZX*",
+                   "values": vals}, f)
+    print("blosum50_reference.json:", len(vals), "values")
+
+
 if __name__ == "__main__":
     cli_goldens()
+    blosum50_golden()
     main()

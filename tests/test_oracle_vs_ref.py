@@ -147,16 +147,11 @@ def test_mark_mismatch(reflib, oracle):
 
 
 def test_blosum50_matches_reference_table():
-    """tests/sswutil.blosum50() is the table the reference CLI uses (reference src/main.c:43-69)."""
-    path = "/root/reference/src/main.c"
-    if not os.path.exists(path):
-        pytest.skip("reference sources not present")
-    import re
-    src = open(path).read()
-    body = src[src.index("mat50[] = {"):src.index("};", src.index("mat50[] = {"))]
-    body = re.sub(r"//[^\n]*", "", body.split("{", 1)[1])
-    vals = [int(x) for x in re.findall(r"-?\d+", body)]
-    assert vals == [int(x) for x in blosum50()]
+    """tests/sswutil.blosum50() is the table the reference CLI uses (reference src/main.c:43-69, stored by tests/golden/make_golden.py)."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "blosum50_reference.json")) as f:
+        vals = json.load(f)["values"]
+    assert len(vals) == 24 * 24 and vals == [int(x) for x in blosum50()]
 
 
 def test_example_c_known_answer():

@@ -23,7 +23,7 @@ def test_two_rank_bench_over_gloo(emu_lib_path, tmp_path):
     env = dict(os.environ, SSW_BENCH_DUMP=str(tmp_path), SSW_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--reads", "5", "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "3", "--lib", emu_lib_path]
+           "--reads", "5", "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "3", "--full", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -51,13 +51,13 @@ def test_two_rank_bench_over_gloo(emu_lib_path, tmp_path):
 
 
 def test_eight_rank_strong_scaling_job_over_gloo(emu_lib_path):
-    """bench.py --config 3 --full at the node's size: 8 ranks over gloo, the job's read blocks divided over them (block b on rank b mod 8:
+    """bench.py --config 3 --stated-size at the node's size: 8 ranks over gloo, the job's read blocks divided over them (block b on rank b mod 8:
     a fixed job, strong scaling), every block of every rank checked against the reference, one line from rank 0.  Toy shapes on the
     emulator; the same code path as the 1M-read job on 1..8 MI355X."""
     env = dict(os.environ, SSW_BENCH_BACKEND="gloo", SSW_EMU_DEVICES="8", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "3", "--full", "--blocks", "12",
-           "--steps", "1", "--warmup", "1", "--reads", "3", "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "2", "--lib", emu_lib_path]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "3", "--stated-size", "--blocks", "12",
+           "--steps", "1", "--warmup", "1", "--reads", "3", "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "2", "--full", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -75,8 +75,8 @@ def test_eight_rank_strong_scaling_job_over_gloo(emu_lib_path):
 def test_full_job_on_one_rank_streams_its_blocks(emu_lib_path):
     """the one-GPU line of the same job: all blocks through one context, then once more with the reads on the host and the next block
     uploaded by a feeder thread while the current one is aligned (same records, checked inside bench.py)"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--full", "--blocks", "5", "--steps", "1", "--warmup", "1", "--reads", "3",
-           "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "2", "--lib", emu_lib_path]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--stated-size", "--blocks", "5", "--steps", "1", "--warmup", "1", "--reads", "3",
+           "--ref-len", "2500", "--read-len", "70", "--cpu-sample", "2", "--full", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -91,7 +91,7 @@ def test_two_rank_database_search_over_gloo(emu_lib_path):
     data path), rank 0 prints the one aggregated line"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "5", "--steps", "1", "--warmup", "0",
-           "--reads", "24", "--db-targets", "9", "--db-chunk", "4", "--cpu-sample", "2", "--lib", emu_lib_path]
+           "--reads", "24", "--db-targets", "9", "--db-chunk", "4", "--cpu-sample", "2", "--full", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, SSW_BENCH_BACKEND="gloo"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -106,7 +106,7 @@ def test_two_rank_database_search_over_gloo(emu_lib_path):
 def test_pool_mode_of_bench_on_two_pretend_devices(emu_lib_path):
     """bench.py --pool 2: the in-library per-GPU work queues drive the batch (single process, reads on the host)"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--pool", "2", "--steps", "1", "--warmup", "0", "--reads", "12", "--ref-len", "2500",
-           "--read-len", "70", "--cpu-sample", "4", "--lib", emu_lib_path]
+           "--read-len", "70", "--cpu-sample", "4", "--full", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, SSW_EMU_DEVICES="2"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -133,7 +133,7 @@ def test_gpus_flag_without_a_launcher_starts_the_ranks_itself(emu_lib_path):
 def test_also_block_carries_the_other_configs(emu_lib_path):
     """the metric's line with configs 3, 4 and 5 attached (`also`): here on the emulator with toy shapes, on the GPU at the stated sizes"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--reads", "3", "--ref-len", "2000", "--read-len", "60",
-           "--cpu-sample", "0", "--also", "2u8,3,4,5,6", "--lib", emu_lib_path]
+           "--cpu-sample", "0", "--full", "--also", "2u8,3,4,5,6", "--lib", emu_lib_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
