@@ -332,6 +332,45 @@ typedef struct {
 	int32_t nq;
 } ssw_gather_args;
 
+/* explicit pair lists (ssw_gpu_align_pairs): one job of k_fillpairs = up to two (query, target) pairs, the low and the high 16-bit half of
+   every register; both queries have the same row class R = ceil(len / 16) */
+typedef struct {
+	int32_t qa, qb;          /* query of the low / high half; qb = -1: the high half is idle */
+	int32_t ta, tb;          /* target of the low / high half (tb = ta when qb = -1) */
+} ssw_pjob;
+
+typedef struct {
+	const int8_t* qcodes;
+	const int64_t* qoff;
+	const int8_t* tcodes;
+	const int64_t* toff;
+	const ssw_pjob* jobs;    /* jobs of this launch, sorted by target length */
+	int64_t njobs;
+	int32_t nch;             /* chains (jobs) per workgroup: as many profiles + rings as fit the LDS (0), or fewer when the host asks */
+	const int8_t* mat;
+	int32_t n;
+	uint32_t gapO2, gapE2;
+	uint32_t* cm16;          /* [njobs][cm_stride] column maxima of the job (both halves packed) */
+	uint32_t* cm8;
+	int64_t cm_stride;
+	int32_t maskLen, bias, score_size;
+	struct ssw_out_rec* out; /* [2 * njobs]: record of the low half of job j at 2j, of the high half at 2j + 1 */
+	int32_t* counters;       /* optional: [0] alignments decided under 16-bit rules, [1] under 8-bit rules */
+	int32_t form;            /* 1: column frame (fr_base / fr_kmask), 0: plain int16 */
+	int32_t fr_base, fr_kmask;
+	int32_t mark_word;       /* records decided under 16-bit rules carry SSW_OUT_WORD in their status (the host reads and clears it) */
+} ssw_fillpairs_args;
+
+/* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
+typedef struct {
+	const int8_t* src;
+	const int64_t* src_off;
+	const int32_t* idx;      /* count source indices */
+	const int64_t* dst_off;  /* count + 1 */
+	int8_t* dst;
+	int32_t count;
+} ssw_seqgather_args;
+
 /* sequence preparation on the device: ASCII -> residue codes, reverse complement of code sequences */
 typedef struct {
 	const uint8_t* text;     /* mode 0: ASCII residues */
@@ -380,6 +419,8 @@ int ssw_shim_launch_fill(int R, const ssw_fill_args* a, void* stream);
 int ssw_shim_fill_class(int R);    /* register class of k_fill<R>: sub-launches of one k_fillm grid share it */
 int ssw_shim_launch_fillm(const ssw_fillm_args* a, const int32_t* host_R, int n, int form, int64_t total_wgs, void* stream);
 int ssw_shim_launch_filldb(int R, const ssw_filldb_args* a, void* stream);
+int ssw_shim_launch_fillpairs(int R, const ssw_fillpairs_args* a, void* stream);   /* -2: no instance for R (1..40) */
+int ssw_shim_fillpairs_nch(int R, int n);   /* chains per workgroup of k_fillpairs<R> for an alphabet of n letters */
 int ssw_shim_launch_reduce(const ssw_reduce_args* a, void* stream);
 int ssw_shim_launch_reducem(const ssw_reducem_args* a, int64_t total_pairs, void* stream);
 int ssw_shim_launch_capture(int R, const ssw_capture_args* a, void* stream);
@@ -396,6 +437,7 @@ int ssw_shim_launch_gather(const ssw_gather_args* a, void* stream);
 int ssw_shim_launch_select(const ssw_select_args* a, void* stream);   /* the pass in a->pass */
 int ssw_shim_launch_mark(const ssw_mark_args* a, void* stream);
 int ssw_shim_launch_prep(const ssw_prep_args* a, void* stream);
+int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream);
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

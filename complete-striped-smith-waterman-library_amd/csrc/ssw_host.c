@@ -2353,6 +2353,472 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	return rc;
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * Explicit pair lists (ssw_gpu_align_pairs): results[i] = the record of (query qidx[i], target tidx[i]) -- a mapper's
+ * "for each read: Align(read, its window)" loop as one call.
+ *   envelope (flag 0, gapO > gapE, n <= 32, max(mat) <= 49, queries 1..640 residues, targets 1..65000 columns -- the fused
+ *   database search's gates): k_fillpairs, jobs of two pairs that share the row class R = ceil(len / 16), one chain per job,
+ *   final records in one launch per R (and per chunk of the scratch budget).  Planning is a counting sort by (R, target-length
+ *   class): O(npairs), no comparison sort.
+ *   everything else (flag != 0, empty sequences, longer sequences, gapO <= gapE, wide alphabets, large scores): one internal
+ *   batch per distinct target over the subset of its queries, gathered into a temporary set on the device (k_seqgather) --
+ *   exact, and slow: a batch call per target.
+ * ------------------------------------------------------------------------------------------------ */
+#define PJ_TCLS 2048      /* target-length classes of the planner: 32 columns each (65000 columns: 2031 classes) */
+
+static double wall_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+static void timing_add(ssw_gpu_timing* acc, const ssw_gpu_timing* t, int64_t* best_cells)
+{
+	acc->fill_ms += t->fill_ms; acc->fill_launches += t->fill_launches; acc->fill_cells += t->fill_cells; acc->cells += t->cells;
+	acc->reduce_ms += t->reduce_ms; acc->locate_ms += t->locate_ms; acc->trace_ms += t->trace_ms; acc->n_word += t->n_word; acc->n_byte += t->n_byte;
+	acc->db_repeats += t->db_repeats; acc->fill_pipelined += t->fill_pipelined;
+	if (t->fill_cells > *best_cells) {
+		*best_cells = t->fill_cells;
+		memcpy(acc->fill_kernel, t->fill_kernel, sizeof acc->fill_kernel);
+		acc->fill_ops_per_row = t->fill_ops_per_row; acc->fill_rows_per_lane = t->fill_rows_per_lane; acc->fill_strips = t->fill_strips;
+	}
+}
+
+/* the pairs list[0 .. nl) outside the kernel's envelope: grouped by target (counting sort), their queries gathered on the device in
+   chunks of at most max(budget / 8, 1 MiB) residues, one align_batch per target; CIGARs appended to the staging pool *spool */
+static int pairs_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                          const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
+                          uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+{
+	const int32_t nt = T->count;
+	int64_t* tstart = (int64_t*)calloc((size_t)nt + 1, sizeof(int64_t));
+	int64_t* bytgt = (int64_t*)malloc(sizeof(int64_t) * (size_t)(nl > 0 ? nl : 1));
+	ssw_gpu_result* tmp = 0; int32_t* gidx = 0; int64_t* goff = 0;
+	int rc = -1;
+	if (!tstart || !bytgt) { fail(c, "out of host memory%s", ""); goto out; }
+	for (int64_t k = 0; k < nl; ++k) tstart[tidx[list[k]] + 1]++;
+	for (int32_t t = 0; t < nt; ++t) tstart[t + 1] += tstart[t];
+	{
+		int64_t* pos = (int64_t*)malloc(sizeof(int64_t) * ((size_t)nt + 1));
+		if (!pos) { fail(c, "out of host memory%s", ""); goto out; }
+		memcpy(pos, tstart, sizeof(int64_t) * ((size_t)nt + 1));
+		for (int64_t k = 0; k < nl; ++k) bytgt[pos[tidx[list[k]]]++] = list[k];      /* stable: pair order inside a target */
+		free(pos);
+	}
+	int64_t maxgrp = 0;
+	for (int32_t t = 0; t < nt; ++t) if (tstart[t + 1] - tstart[t] > maxgrp) maxgrp = tstart[t + 1] - tstart[t];
+	if (maxgrp > 0x7fffffff) { fail(c, "align_pairs: %s", "more than 2^31 pairs against one target outside the fused kernel's envelope"); goto out; }
+	tmp = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)(maxgrp > 0 ? maxgrp : 1));
+	if (!tmp) { fail(c, "out of host memory%s", ""); goto out; }
+	int64_t lim = (int64_t)(c->cm_budget / 8); if (lim < ((int64_t)1 << 20)) lim = (int64_t)1 << 20;
+	for (int32_t t0 = 0; t0 < nt; ) {
+		/* a chunk of consecutive targets whose gathered queries stay within `lim` residues (at least one target) */
+		int32_t t1 = t0; int64_t res_sum = 0;
+		while (t1 < nt) {
+			int64_t s = 0;
+			for (int64_t k = tstart[t1]; k < tstart[t1 + 1]; ++k) s += Q->h_off[qidx[bytgt[k]] + 1] - Q->h_off[qidx[bytgt[k]]];
+			if (t1 > t0 && res_sum + s > lim) break;
+			res_sum += s; ++t1;
+		}
+		const int64_t k0 = tstart[t0], cnt = tstart[t1] - k0;
+		if (cnt == 0) { t0 = t1; continue; }
+		if (cnt > 0x7fffffff) { fail(c, "align_pairs: %s", "fallback chunk too large"); goto out; }
+		free(gidx); free(goff);
+		gidx = (int32_t*)malloc(sizeof(int32_t) * (size_t)cnt); goff = (int64_t*)malloc(sizeof(int64_t) * ((size_t)cnt + 1));
+		if (!gidx || !goff) { fail(c, "out of host memory%s", ""); goto out; }
+		goff[0] = 0;
+		for (int64_t k = 0; k < cnt; ++k) { const int32_t q = qidx[bytgt[k0 + k]]; gidx[k] = q; goff[k + 1] = goff[k] + (Q->h_off[q + 1] - Q->h_off[q]); }
+		ssw_gpu_seqs* G = seqs_new(c, goff, (int32_t)cnt);
+		if (!G) goto out;
+		int32_t* d_idx = (int32_t*)ssw_shim_malloc(sizeof(int32_t) * (size_t)cnt);
+		ssw_seqgather_args ga; ga.src = Q->d_codes; ga.src_off = Q->d_off; ga.idx = d_idx; ga.dst_off = G->d_off; ga.dst = G->d_codes; ga.count = (int32_t)cnt;
+		const int ok = d_idx && !ssw_shim_h2d(d_idx, gidx, sizeof(int32_t) * (size_t)cnt, c->stream) &&
+		               !ssw_shim_h2d(G->d_off, G->h_off, sizeof(int64_t) * ((size_t)cnt + 1), c->stream) &&
+		               !ssw_shim_launch_seqgather(&ga, c->stream) && !ssw_shim_stream_sync(c->stream);
+		ssw_shim_free(d_idx);
+		if (!ok) { fail(c, "align_pairs: query gather failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(G); goto out; }
+		for (int32_t t = t0; t < t1; ++t) {
+			const int64_t a0 = tstart[t] - k0, m = tstart[t + 1] - tstart[t];
+			if (m == 0) continue;
+			/* a view of the gathered set: this target's queries (offsets stay absolute in G's codes) */
+			struct ssw_gpu_seqs V; V.ctx = c; V.d_codes = G->d_codes; V.d_off = G->d_off + a0; V.h_off = G->h_off + a0; V.count = (int32_t)m;
+			V.total = V.h_off[m] - V.h_off[0];
+			uint32_t* pool = 0; int64_t words = 0;
+			if (align_batch_locked(c, &V, T, t, 1, prm, tmp, &pool, &words, 0)) { ssw_gpu_seqs_free(G); goto out; }      /* (the pool is always taken: offsets in pair order) */
+			timing_add(acc, &c->tm, best_cells);
+			if (words > 0) {
+				if (*swords + words > *scap) {
+					const int64_t ncap = (*swords + words) * 2 + 1024;
+					uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
+					if (!np2) { free(pool); ssw_gpu_seqs_free(G); fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
+					*spool = np2; *scap = ncap;
+				}
+				memcpy(*spool + *swords, pool, sizeof(uint32_t) * (size_t)words);
+			}
+			for (int64_t k = 0; k < m; ++k) {
+				ssw_gpu_result r = tmp[k];
+				if (r.cigarLen > 0 && r.cigar_off >= 0) r.cigar_off += *swords;
+				results[bytgt[tstart[t] + k]] = r;
+			}
+			*swords += words;
+			free(pool);
+		}
+		ssw_gpu_seqs_free(G);
+		t0 = t1;
+	}
+	rc = 0;
+out:
+	free(tstart); free(bytgt); free(tmp); free(gidx); free(goff);
+	return rc;
+}
+
+/* Flagged pairs inside the fused kernel's envelope: k_fillpairs gave scores and end positions (status carries SSW_OUT_WORD); the pairs that
+   pass the reference's gate (src/ssw.c:900-903, 916) become a survivor list grouped by query geometry bucket, and the reverse pass
+   (window_pass) and the traceback (trace_phase, k_mark included) run over it as (query, target) jobs through an ssw_vmap -- the flagged
+   database search's phases (dbx_chunk) over a pair list.  rec[0 .. nrec) are the fill's records of the pairs pix[]; they are completed in
+   place, CIGARs appended to the staging pool (always, like align_batch does). */
+static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                         const int64_t* pix, ssw_gpu_result* rec, int64_t nrec, const ssw_gpu_params* prm, const int8_t* d_mat,
+                         int32_t maxmat, int32_t minmat, uint32_t** spool, int64_t* swords, int64_t* scap,
+                         double* locate_ms, double* trace_ms)
+{
+	const int32_t n = prm->n;
+	/* geometry of the window kernels, as align_batch chooses it (queries here are <= 640 residues) */
+	int32_t xlanes = 64, xrmax = 4 * (24 / (n + 1) < 1 ? 1 : 24 / (n + 1) > 3 ? 3 : 24 / (n + 1)), xrcap = 12;
+	if (c->kn.xlanes16) xlanes = 16;
+	if (c->kn.xr) { xrmax = c->kn.xr; xrcap = xrmax; }
+	if (c->kn.xr_window) xrcap = c->kn.xr_window;
+	while (xlanes == 64 && xrmax > 4 && (int64_t)n * ((xrmax + 3) / 4) * 1024 > 65535) xrmax -= 4;
+	const int32_t rows = xlanes * (xlanes == 64 ? xrmax : SSW_RMAX);
+	/* bucket key per query length: R (short queries), SSW_RMAX + 1 + Rq (one strip), SSW_RMAX + 64 + P16 / 16 (several strips) */
+	const int NKEY = SSW_RMAX + 64 + 41;
+	int64_t kfirst[SSW_RMAX + 64 + 42]; int32_t kp16[SSW_RMAX + 64 + 41];
+	memset(kfirst, 0, sizeof kfirst); memset(kp16, 0, sizeof kp16);
+	int32_t* key = (int32_t*)malloc(sizeof(int32_t) * (size_t)(nrec > 0 ? nrec : 1));
+	int64_t* order = (int64_t*)malloc(sizeof(int64_t) * (size_t)(nrec > 0 ? nrec : 1));
+	ssw_dres* hs = 0; int32_t* hvq = 0; int32_t* hvt = 0; int32_t* ids = 0; int32_t* hneed = 0; int64_t* goffs = 0;
+	int rc = -1;
+	if (!key || !order) { fail(c, "out of host memory%s", ""); goto out; }
+	int64_t ns = 0; int32_t maxlen = 0; int64_t maxt = 0;
+	for (int64_t k = 0; k < nrec; ++k) {
+		ssw_gpu_result* o = &rec[k];
+		const int word = (o->status & SSW_OUT_WORD) != 0;
+		o->status &= 0xffu;
+		key[k] = -1;
+		if (o->status != 0 || o->score1 == 0 || (prm->flag == 2 && (int)o->score1 < prm->filters)) continue;      /* ssw.c:900-903, 916 */
+		const int64_t i = pix[k];
+		const int32_t len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]), P16q = (len + 15) / 16 * 16;
+		const int64_t tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		int32_t kk;
+		if (len <= 16 * SSW_RMAX) kk = P16q / 16;
+		else { const int32_t st = (P16q + rows - 1) / rows, Rq = (P16q + xlanes * st - 1) / (xlanes * st); kk = st == 1 ? SSW_RMAX + 1 + Rq : SSW_RMAX + 64 + P16q / 16; }
+		key[k] = kk | (word << 30);
+		kfirst[kk + 1]++;
+		if (P16q > kp16[kk]) kp16[kk] = P16q;
+		if (len > maxlen) maxlen = len;
+		if (tl > maxt) maxt = tl;
+		++ns;
+	}
+	if (ns == 0) { rc = 0; goto out; }
+	if (ns > 0x7fffff00) { fail(c, "align_pairs: %s", "more than 2^31 flagged pairs in one call"); goto out; }
+	for (int b = 0; b < NKEY; ++b) kfirst[b + 1] += kfirst[b];
+	{
+		int64_t pos[SSW_RMAX + 64 + 41];
+		memcpy(pos, kfirst, sizeof pos);
+		for (int64_t k = 0; k < nrec; ++k) if (key[k] >= 0) order[pos[key[k] & 0xffff]++] = k;
+	}
+	hs = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)ns); hvq = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)ns); hvt = hvq + ns;
+	if (!hs || !hvq) { fail(c, "out of host memory%s", ""); goto out; }
+	for (int64_t v = 0; v < ns; ++v) {
+		const int64_t k = order[v], i = pix[k];
+		const ssw_gpu_result* o = &rec[k];
+		ssw_dres* r = &hs[v];
+		memset(r, 0, sizeof *r);
+		r->score1 = o->score1; r->score2 = o->score2; r->ref_begin1 = -1; r->ref_end1 = o->ref_end1; r->read_begin1 = -1; r->read_end1 = o->read_end1;
+		r->ref_end2 = o->ref_end2; r->word = (key[k] >> 30) & 1; r->want_begin = 1; r->loc_done = 1;      /* (as k_select writes them) */
+		hvq[v] = qidx[i]; hvt[v] = tidx[i]; hvq[2 * ns + v] = (int32_t)v;
+	}
+	{
+		ssw_dres* d_sres = (ssw_dres*)ensure(c, &c->sres, sizeof(ssw_dres) * (size_t)ns);
+		int32_t* d_maps = (int32_t*)ensure(c, &c->svq, sizeof(int32_t) * 4 * (size_t)ns);      /* vq, vt, identity list, traceback job lists */
+		if (!d_sres || !d_maps) goto out;
+		int32_t* d_vq = d_maps; int32_t* d_vt = d_maps + ns; int32_t* d_vl = d_maps + 2 * (size_t)ns; int32_t* d_tl = d_maps + 3 * (size_t)ns;
+		ssw_shim_event_record(c->ev_a, c->stream);
+		if (ssw_shim_h2d(d_sres, hs, sizeof(ssw_dres) * (size_t)ns, c->stream) || ssw_shim_h2d(d_maps, hvq, sizeof(int32_t) * 3 * (size_t)ns, c->stream)) {
+			fail(c, "upload failed: %s", ssw_shim_last_error()); goto out;
+		}
+		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off;
+		win_in wi; memset(&wi, 0, sizeof wi);
+		wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = (int32_t)maxt; wi.d_mat = d_mat; wi.n = n; wi.maxmat = maxmat; wi.minmat = minmat;
+		wi.fill_form = c->kn.fill_plain ? 0 : -1; wi.xlanes = xlanes; wi.xrmax = xrmax; wi.xrcap = xrcap;
+		for (int kk = 0; kk < NKEY; ++kk) {
+			const int64_t f0 = kfirst[kk], cnt = kfirst[kk + 1] - kfirst[kk];
+			if (cnt <= 0) continue;
+			bucket B; memset(&B, 0, sizeof B);
+			if (kk <= SSW_RMAX) { B.R = kk; B.strips = 1; B.P16 = 16 * kk; B.lanes = 16; B.use_x = 0; }
+			else {      /* the strip geometry of align_batch's bucket (ssw_host.c align_batch_locked) */
+				B.P16 = kp16[kk]; B.lanes = xlanes; B.use_x = 1;
+				B.strips = (B.P16 + rows - 1) / rows;
+				B.R = (B.P16 + B.lanes * B.strips - 1) / (B.lanes * B.strips);
+				if (B.lanes == 64 && B.strips > 1 && xrmax > 4 && !c->kn.no_tail) {
+					const int32_t rem = B.P16 - (B.strips - 1) * 64 * xrmax, need = (rem + 63) / 64, tr = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 0;
+					if (rem > 0 && tr > 0 && xrmax * (B.strips - 1) + tr < B.R * B.strips) { B.R = xrmax; B.tailR = tr; }
+				}
+			}
+			wi.d_res = d_sres + f0; wi.vm = vm; wi.vm.vq = d_vq + f0; wi.vm.vt = d_vt + f0;
+			if (window_pass(c, &wi, &B, 1, d_vl, (int32_t)cnt, 0)) goto out;
+		}
+		ssw_shim_event_record(c->ev_b, c->stream);
+		/* traceback over slabs of survivors (a slab = the CIGAR slots that fit half the budget), as the flagged database search does it */
+		const int32_t halo_max = halo_for((maxlen + 15) / 16 * 16, maxmat, prm->gapE);
+		const int64_t ref_span = halo_max < maxt ? halo_max : maxt;
+		const int64_t slot_bytes = 8 * ((int64_t)maxlen + ref_span + 16) + 4 * (int64_t)maxlen + 256;
+		int64_t slab = (int64_t)(c->cm_budget / 2) / slot_bytes;
+		if (slab < 1024) slab = 1024;
+		if (c->kn.dbx_slab) slab = c->kn.dbx_slab;
+		const int64_t sl = ns < slab ? ns : slab;
+		ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)sl);
+		if (!ids || !hneed || !goffs) { fail(c, "out of host memory%s", ""); goto out; }
+		for (int64_t s0 = 0; s0 < ns; s0 += slab) {
+			const int32_t cnt = (int32_t)(ns - s0 < slab ? ns - s0 : slab);
+			trace_out tro; memset(&tro, 0, sizeof tro);
+			if ((prm->flag & 7) != 0) {
+				for (int32_t k = 0; k < cnt; ++k) ids[k] = k;
+				trace_in tri; memset(&tri, 0, sizeof tri);
+				tri.Q = Q; tri.prm = prm; tri.d_tgt = T->d_codes; tri.vm = vm; tri.vm.vq = d_vq + s0; tri.vm.vt = d_vt + s0; tri.d_mat = d_mat; tri.n = n;
+				tri.d_res = d_sres + s0; tri.nslots = cnt; tri.ids = ids; tri.nids = cnt; tri.d_list = d_tl; tri.hneed = hneed; tri.maxlen = maxlen; tri.ref_span = ref_span;
+				if (trace_phase(c, &tri, &tro)) goto out;
+			}
+			if (ssw_shim_d2h(hs + s0, d_sres + s0, sizeof(ssw_dres) * (size_t)cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto out; }
+			int64_t gwords = 0;
+			for (int32_t k = 0; k < cnt; ++k) {
+				const ssw_dres* r = &hs[s0 + k];
+				if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); goto out; }
+				goffs[k] = gwords;
+				if (r->cigarLen > 0 && r->status == 0) gwords += r->cigarLen;
+			}
+			if (gwords > 0) {
+				int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
+				uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
+				if (!d_goff || !d_gpool) goto out;
+				if (*swords + gwords > *scap) {
+					const int64_t ncap = (*swords + gwords) * 2 + 1024;
+					uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
+					if (!np2) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
+					*spool = np2; *scap = ncap;
+				}
+				ssw_gather_args ga; ga.src = tro.d_cig; ga.res = d_sres + s0; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
+				if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
+				    ssw_shim_d2h(*spool + *swords, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream) || ssw_shim_stream_sync(c->stream)) {
+					fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); goto out;
+				}
+			}
+			for (int32_t k = 0; k < cnt; ++k) {      /* what the reverse pass and the traceback added to the records */
+				const ssw_dres* r = &hs[s0 + k];
+				ssw_gpu_result* o = &rec[order[s0 + k]];
+				o->ref_begin1 = r->ref_begin1; o->read_begin1 = r->read_begin1; o->cigarLen = r->cigarLen; o->flag = (uint16_t)r->flag;
+				o->edit_distance = r->nm; o->cigar_off = r->cigarLen > 0 && r->status == 0 ? *swords + goffs[k] : -1;
+			}
+			*swords += gwords;
+		}
+		ssw_shim_event_record(c->ev_c, c->stream);
+		if (ssw_shim_stream_sync(c->stream) || chainq_check(c)) { if (!c->err[0]) fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto out; }
+		*locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+		*trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
+	}
+	rc = 0;
+out:
+	free(key); free(order); free(hs); free(hvq); free(ids); free(hneed); free(goffs);
+	return rc;
+}
+
+static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                              int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !results))) return fail(c, "align_pairs: NULL argument%s", "");
+	if (Q->ctx != c || T->ctx != c) return fail(c, "align_pairs: sequences belong to another context%s", "");
+	if (prm->n < 1) return fail(c, "align_pairs: alphabet size must be >= 1%s", "");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_pairs: score_size must be 0, 1 or 2%s", "");
+	for (int64_t i = 0; i < np; ++i)
+		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
+			char msg[160];
+			snprintf(msg, sizeof msg, "pair %lld: query %d of %d, target %d of %d", (long long)i, qidx[i], Q->count, tidx[i], T->count);
+			return fail(c, "align_pairs: index out of range (%s)", msg);
+		}
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	memset(&c->tm, 0, sizeof c->tm);
+	if (np == 0) return 0;
+	const double t_start = wall_ms();
+	ssw_shim_set_device(c->device);
+	knobs_load(&c->kn);
+
+	int32_t minmat = 0, maxmat = 0;
+	for (int64_t i = 0; i < (int64_t)prm->n * prm->n; ++i) { if (prm->mat[i] < minmat) minmat = prm->mat[i]; if (prm->mat[i] > maxmat) maxmat = prm->mat[i]; }
+	const int32_t bias = (prm->score_size == 0 || prm->score_size == 2) ? -minmat : 0;
+	const int32_t n = prm->n;
+	/* (flagged pairs: the window kernels address the concatenated targets with 32-bit column indices, like the flagged database search) */
+	const int kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db && (prm->flag == 0 || T->total < 0x7fff0000);
+
+	/* ---- plan: counting sort of the kernel's pairs by (R, target-length class); the rest to the fallback list */
+	const int64_t nkeys = (int64_t)40 * PJ_TCLS;
+	int64_t* kcount = (int64_t*)calloc((size_t)nkeys + 1, sizeof(int64_t));
+	uint32_t* key = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)np);
+	int64_t* perm = (int64_t*)malloc(sizeof(int64_t) * (size_t)np);
+	int64_t* fb = 0; int64_t nfb = 0;
+	ssw_pjob* jobs = 0; int64_t* jix = 0; ssw_gpu_result* stage = 0;
+	uint32_t* spool = 0; int64_t swords = 0, scap = 0;
+	ssw_gpu_timing acc; memset(&acc, 0, sizeof acc);
+	int64_t best_cells = 0;
+	int rc = -1;
+	if (!kcount || !key || !perm) { fail(c, "out of host memory%s", ""); goto done; }
+	for (int64_t i = 0; i < np; ++i) {
+		const int64_t ql = Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]], tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		const int R = (int)((ql + 15) / 16);
+		if (!kern_ok || ql < 1 || ql > 640 || tl < 1 || tl > 65000 || (int64_t)n * ((R + 3) / 4) * 256 > 65535) { key[i] = 0xffffffffu; ++nfb; continue; }
+		key[i] = (uint32_t)((R - 1) * PJ_TCLS + (tl >> 5 < PJ_TCLS ? tl >> 5 : PJ_TCLS - 1));
+		kcount[key[i] + 1]++;
+	}
+	for (int64_t k = 0; k < nkeys; ++k) kcount[k + 1] += kcount[k];
+	const int64_t nk = kcount[nkeys];
+	if (nfb > 0) { fb = (int64_t*)malloc(sizeof(int64_t) * (size_t)nfb); if (!fb) { fail(c, "out of host memory%s", ""); goto done; } }
+	{
+		int64_t f = 0;
+		for (int64_t i = 0; i < np; ++i) { if (key[i] == 0xffffffffu) fb[f++] = i; else perm[kcount[key[i]]++] = i; }      /* kcount[k] ends as the end of class k */
+	}
+
+	if (nk > 0) {
+		/* jobs: neighbours of one R (sorted by target length: the two halves and the chains of a workgroup finish together) */
+		const int64_t njmax = nk / 2 + 40;
+		jobs = (ssw_pjob*)malloc(sizeof(ssw_pjob) * (size_t)njmax);
+		jix = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)njmax);
+		if (!jobs || !jix) { fail(c, "out of host memory%s", ""); goto done; }
+		int64_t rfirst[41], maxt[40]; int64_t nj = 0;
+		for (int R = 1; R <= 40; ++R) {
+			const int64_t lo = R == 1 ? 0 : kcount[(int64_t)(R - 1) * PJ_TCLS - 1], hi = kcount[(int64_t)R * PJ_TCLS - 1];
+			rfirst[R - 1] = nj; maxt[R - 1] = 0;
+			for (int64_t k = lo; k < hi; k += 2) {
+				const int64_t pa = perm[k], pb = k + 1 < hi ? perm[k + 1] : -1;
+				ssw_pjob* j = &jobs[nj];
+				j->qa = qidx[pa]; j->ta = tidx[pa];
+				j->qb = pb >= 0 ? qidx[pb] : -1; j->tb = pb >= 0 ? tidx[pb] : tidx[pa];
+				jix[2 * nj] = pa; jix[2 * nj + 1] = pb;
+				const int64_t L = T->h_off[tidx[pa] + 1] - T->h_off[tidx[pa]], Lb = pb >= 0 ? T->h_off[tidx[pb] + 1] - T->h_off[tidx[pb]] : 0;
+				if (L > maxt[R - 1]) maxt[R - 1] = L;
+				if (Lb > maxt[R - 1]) maxt[R - 1] = Lb;
+				++nj;
+			}
+		}
+		rfirst[40] = nj;
+		/* the call's small inputs: matrix + jobs in one upload */
+		const size_t hdr_mat = ((size_t)n * n + 15) / 16 * 16;
+		unsigned char* d_hdr = (unsigned char*)ensure(c, &c->pairs, hdr_mat + sizeof(ssw_pjob) * (size_t)nj);
+		int32_t* d_cnt = (int32_t*)ensure(c, &c->need, DB_COUNTERS * sizeof(int32_t));
+		stage = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * 2 * (size_t)nj);
+		if (!d_hdr || !d_cnt) goto done;
+		if (!stage) { fail(c, "out of host memory%s", ""); goto done; }
+		int8_t* d_mat = (int8_t*)d_hdr;
+		ssw_pjob* d_jobs = (ssw_pjob*)(d_hdr + hdr_mat);
+		c->nev = 0;
+		ssw_shim_event_record(c->ev_t0, c->stream);
+		if (ssw_shim_h2d(d_mat, prm->mat, (size_t)n * n, c->stream) || ssw_shim_h2d(d_jobs, jobs, sizeof(ssw_pjob) * (size_t)nj, c->stream) ||
+		    ssw_shim_memset(d_cnt, 0, DB_COUNTERS * sizeof(int32_t), c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+		const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
+		int64_t kcells = 0, kbest = 0;
+		for (int R = 1; R <= 40; ++R) {
+			const int64_t j0 = rfirst[R - 1], jn = rfirst[R] - j0;
+			if (jn == 0) continue;
+			const int nch = ssw_shim_fillpairs_nch(R, n);
+			if (nch < 1) { fail(c, "align_pairs: %s", "no k_fillpairs geometry for this alphabet"); goto done; }
+			const int64_t stride = (maxt[R - 1] + 15) / 16 * 16 + 16;
+			/* scratch of a job: its two column-maximum rows + two records; jobs per launch: what half the budget holds, whole workgroups */
+			const int64_t per_job = 8 * stride + 2 * (int64_t)sizeof(ssw_gpu_result);
+			int64_t jpl = (int64_t)(c->cm_budget / 2) / per_job;
+			const int nch_l = jpl < nch ? (jpl > 1 ? (int)jpl : 1) : nch;      /* a small budget: fewer chains per workgroup (one job at the least) */
+			jpl = jpl / nch_l * nch_l;
+			if (jpl < nch_l) jpl = nch_l;
+			if (jpl > jn) jpl = jn;
+			uint32_t* d_cm16 = (uint32_t*)ensure(c, &c->cm16, (size_t)(4 * stride * jpl));
+			uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
+			struct ssw_out_rec* d_out = (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
+			if (!d_cm16 || !d_cm8 || !d_out) goto done;
+			int32_t fr_base = 0, fr_kmask = 0;
+			const int fr = !c->kn.db_plain && ssw_frame_params(&c->kn, (int64_t)16 * R * maxmat, prm->gapO, prm->gapE, minmat, 16, &fr_base, &fr_kmask);
+			int64_t rcells = 0;
+			for (int64_t a0 = 0; a0 < jn; a0 += jpl) {
+				ssw_fillpairs_args fa; memset(&fa, 0, sizeof fa);
+				fa.qcodes = Q->d_codes; fa.qoff = Q->d_off; fa.tcodes = T->d_codes; fa.toff = T->d_off; fa.jobs = d_jobs + j0 + a0;
+				fa.njobs = jn - a0 < jpl ? jn - a0 : jpl; fa.mat = d_mat; fa.n = n; fa.gapO2 = gapO2; fa.gapE2 = gapE2;
+				fa.cm16 = d_cm16; fa.cm8 = d_cm8; fa.cm_stride = stride; fa.maskLen = prm->maskLen; fa.bias = bias; fa.score_size = prm->score_size;
+				fa.out = d_out; fa.counters = d_cnt; fa.form = fr; fa.fr_base = fr_base; fa.fr_kmask = fr_kmask;
+				fa.nch = nch_l; fa.mark_word = prm->flag != 0;
+				void* e0 = next_event(c); void* e1 = next_event(c);
+				ssw_shim_event_record(e0, c->stream);
+				if (ssw_shim_launch_fillpairs(R, &fa, c->stream)) { fail(c, "fillpairs launch failed: %s", ssw_shim_last_error()); goto done; }
+				ssw_shim_event_record(e1, c->stream);
+				/* same stream: the next launch of the loop reuses d_out / d_cm* only after this download */
+				if (ssw_shim_d2h(stage + 2 * (j0 + a0), d_out, sizeof(struct ssw_out_rec) * 2 * (size_t)fa.njobs, c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+				c->tm.fill_launches++;
+				for (int64_t j = j0 + a0; j < j0 + a0 + fa.njobs; ++j) {
+					const ssw_pjob* jb = &jobs[j];
+					const int64_t La = T->h_off[jb->ta + 1] - T->h_off[jb->ta], Lb = jb->qb >= 0 ? T->h_off[jb->tb + 1] - T->h_off[jb->tb] : 0;
+					rcells += (int64_t)16 * R * 2 * (La > Lb ? La : Lb);
+				}
+			}
+			kcells += rcells;
+			char nm[48];
+			snprintf(nm, sizeof nm, "k_fillpairs<%d,%s>", R, fr ? "frame" : "int16+max3");
+			note_fill_kernel(c, rcells, &kbest, nm, fr ? 7.5 : 9.5, R, 1);
+		}
+		int32_t cnt[DB_COUNTERS] = { 0, 0, 0, 0 };
+		ssw_shim_event_record(c->ev_d, c->stream);
+		if (ssw_shim_d2h(cnt, d_cnt, sizeof cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+		for (int e = 0; e + 1 < c->nev; e += 2) c->tm.fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
+		c->tm.fill_cells = kcells; c->tm.n_word = cnt[0]; c->tm.n_byte = cnt[1];      /* (the reduction is fused into the fill: reduce_ms stays 0) */
+		/* the records of the pairs in job order (stage holds two per job; an idle high half is dropped) */
+		int64_t nrec = 0;
+		for (int64_t j = 0; j < nj; ++j)
+			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
+		if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, tidx, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
+		                                    &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
+		for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
+		timing_add(&acc, &c->tm, &best_cells);
+	}
+	if (nfb > 0 && pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+	if (swords > 0) {      /* the pool in pair order (offsets as the caller's pool would have them, also when it asked for none) */
+		uint32_t* pool = cigar_pool ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)swords) : 0;
+		if (cigar_pool && !pool) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto done; }
+		int64_t w = 0;
+		for (int64_t i = 0; i < np; ++i) {
+			ssw_gpu_result* r = &results[i];
+			if (r->cigarLen > 0 && r->cigar_off >= 0) {
+				if (pool) memcpy(pool + w, spool + r->cigar_off, sizeof(uint32_t) * (size_t)r->cigarLen);
+				r->cigar_off = w; w += r->cigarLen;
+			}
+		}
+		if (cigar_pool) *cigar_pool = pool;
+		if (cigar_words) *cigar_words = w;
+	}
+	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
+		const int64_t i = perm[k]; acc.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * (T->h_off[tidx[i] + 1] - T->h_off[tidx[i]]); }
+	acc.total_ms = wall_ms() - t_start;
+	c->tm = acc;
+	rc = 0;
+done:
+	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(spool);
+	return rc;
+}
+
+int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx, int64_t npairs,
+                        const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_pairs: NULL context%s", "");
+	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return SSW_GPU_BUSY;
+	}
+	const int rc = align_pairs_locked(c, Q, T, qidx, tidx, npairs, prm, results, cigar_pool, cigar_words);
+	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
+	return rc;
+}
+
 void* ssw_gpu_host_alloc(ssw_gpu_ctx* c, size_t bytes)
 {
 	if (!c) return 0;

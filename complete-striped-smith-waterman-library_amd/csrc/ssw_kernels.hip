@@ -59,7 +59,8 @@ template <int R> struct ChainGeom {
 };
 
 /* build one packed profile: rows of query A in the low halves, query B in the high halves */
-/* PM: 0 packed int16, 2 column frame (score + gapE per live row, FR_DEAD for dead rows: lanes.h) */
+/* PM: 0 packed int16, 2 column frame (score + gapE per live row, FR_DEAD for dead rows: lanes.h), 3 the same per half (halves merged from
+   different entries: k_fillpairs) */
 template <int R, int PM = 0>
 SSW_DEV void build_profile(unsigned char* lds, u32 base, int first, int nthreads,
                            const int8_t* mat, int n,
@@ -80,6 +81,7 @@ SSW_DEV void build_profile(unsigned char* lds, u32 base, int first, int nthreads
 			if (row < lena) lo = mat[b * n + (reva ? qa[lena - 1 - row] : qa[row])];
 			if (qb && row < lenb) hi = mat[b * n + qb[row]];
 			if (PM == 2) v = fr_pack(lo == -32768 ? FR_DEAD : lo + gapE, hi == -32768 ? FR_DEAD : hi + gapE);
+			else if (PM == 3) v = pk_make(lo == -32768 ? FR_DEAD : lo + gapE, hi == -32768 ? FR_DEAD : hi + gapE);      /* per half (pk_addw) */
 			else v = pk_make(lo, hi);
 		}
 		lds_st32(lds, base + (u32)w * 4u, v);
@@ -726,6 +728,308 @@ __global__ void __launch_bounds__(16 * NCH) SSW_WAVES_PER_EU(DB_WAVES_PER_EU, 8)
 	SSW_DYN_LDS(lds);
 	if (FR) filldb_pass<R, NCH, true, DB_UNROLL>(a, lds);
 	else filldb_pass<R, NCH, false, 4>(a, lds);
+}
+
+/* ================================================================================================
+ * k_fillpairs: an explicit list of (query, target) pairs.  k_filldb's chain (column-frame or int16 recurrence, best-cell records,
+ * the chain's own column-maxima reduction under both padding rules: final records in one launch), but every 16-bit half of a
+ * register has its OWN target: a job is (qa, ta) in the low halves and (qb, tb) in the high halves.  Each chain keeps the packed
+ * profile of its own query pair in LDS and two target rings; a step reads both ring entries and both score chunks and merges them
+ * per row (low half from ta's residue, high half from tb's: one v_bfi per row).  grid = ceil(njobs / nch) workgroups of nch chains.
+ * Jobs of a workgroup share the row class R; the host sorts them by target length so that the chains finish together.
+ * ================================================================================================ */
+#define PJ_CHAIN_EXTRA (2 * DB_RING_BYTES + 8 * DB_OUT_RING)      /* per chain beside its profile: rings a / b, out16 / out8 */
+
+/* db_rows with a score chunk per half: row r scores bfi(low from sa, high from sb) */
+template <int R, bool FR>
+SSW_DEV void pj_rows(const unsigned char* lds, u32 pa_next, u32 pb_next, u32x4 (&sa)[(R + 3) / 4], u32x4 (&sb)[(R + 3) / 4],
+                     u32 (&H)[R], u32 (&E)[R], u32 d, u32& f, u32& cm, u32& ck, u32 gO, u32 gE, u32 fl)
+{
+	constexpr int C = (R + 3) / 4, K8 = ChainGeom<R>::K8;
+	u32 pa = pa_next, pb = pb_next;
+#pragma unroll
+	for (int r = 0; r < R; ++r) {
+		const int seg0 = r < K8 ? 0 : K8, seg1 = r < K8 ? K8 : R;
+		const bool second = ((r - seg0) & 1) == 1;
+		const bool pair = !second && r + 1 < seg1;
+		if (r == K8) ck = cm;
+		{
+			const u32 hold = H[r];
+			const u32 s = bfi32(0x0000ffffu, sa[r >> 2][r & 3], sb[r >> 2][r & 3]);
+			u32 h;
+			if (FR) {
+				h = pk_max3_fr(pk_addw(d, s), E[r], f);      /* (the halves of s come from different entries: per-half add, PM 3 profile) */
+				const u32 t = h - gO;
+				E[r] = pk_max3_fr(E[r], t, fl);
+				f = pk_max(f, t);
+				if (r != R - 1) f -= gE;
+			} else {
+				const u32 h0 = pk_max(pk_adds(d, s), E[r]);
+				h = pk_max(h0, f);
+				const u32 t0 = pk_subu(h0, gO);
+				E[r] = pk_max(pk_subu(E[r], gE), t0);
+				f = pk_max(pk_subu(f, gE), t0);
+			}
+			if (second) cm = pk_max3_nonneg(cm, H[r - 1 >= 0 ? r - 1 : 0], h);
+			else if (!pair) cm = pk_max(cm, h);
+			H[r] = h;
+			d = hold;
+		}
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			const int last = 4 * c + 3 < R - 1 ? 4 * c + 3 : R - 1;
+			if (last <= db_done<R>(r) && last > db_done<R>(r - 1)) {
+				pa = after(pa, H[last]);
+				pb = after(pb, H[last]);
+				if (c + 1 < C) { sa[c] = lds_ld128(lds, pa + 256u * c); sb[c] = lds_ld128(lds, pb + 256u * c); }
+				else { sa[c] = lds_ld_rows<R - 4 * (C - 1)>(lds, pa + 256u * c); sb[c] = lds_ld_rows<R - 4 * (C - 1)>(lds, pb + 256u * c); }
+			}
+		}
+	}
+}
+
+template <int R, bool FR, int UNROLL>
+SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
+{
+	typedef ChainGeom<R> G;
+	constexpr int C = G::C;
+	constexpr u32 OM = DB_OUT_RING - 1;
+	const int nch = a.nch;
+	const int tid = (int)threadIdx.x, l16 = tid & 15, grp = tid >> 4;
+	const int gapEi = (int)(a.gapE2 & 0xffffu);
+	const u32 prof_bytes = (u32)(a.n + 1) * G::PSTRIDE;
+	const u32 pbase = (u32)grp * (prof_bytes + PJ_CHAIN_EXTRA);
+	const u32 ringa = pbase + prof_bytes, ringb = ringa + DB_RING_BYTES, out16 = ringb + DB_RING_BYTES, out8 = out16 + 4u * DB_OUT_RING;
+	const u32 nulloff = (u32)a.n * G::PSTRIDE;
+	const int64_t job = (int64_t)blockIdx.x * nch + grp;
+	const bool active = job < a.njobs;
+	const ssw_pjob jb = a.jobs[active ? job : 0];
+	const int lena = active ? (int)(a.qoff[jb.qa + 1] - a.qoff[jb.qa]) : 0;
+	const int lenb = active && jb.qb >= 0 ? (int)(a.qoff[jb.qb + 1] - a.qoff[jb.qb]) : 0;
+	build_profile<R, FR ? 3 : 0>(lds, pbase, l16, 16, a.mat, a.n, a.qcodes + a.qoff[jb.qa], lena, 0,
+	                             jb.qb >= 0 ? a.qcodes + a.qoff[jb.qb] : (const int8_t*)0, lenb, 0x7fffffff, 0x7fffffff, gapEi);
+
+	const int8_t* tga = a.tcodes + a.toff[jb.ta];
+	const int8_t* tgb = jb.qb >= 0 ? a.tcodes + a.toff[jb.tb] : tga;
+	const int ncola = active ? (int)(a.toff[jb.ta + 1] - a.toff[jb.ta]) : 0;
+	const int ncolb = active && jb.qb >= 0 ? (int)(a.toff[jb.tb + 1] - a.toff[jb.tb]) : 0;
+	const int ncols = ncola > ncolb ? ncola : ncolb;      /* columns whose maxima this chain keeps (both halves stand in the same column) */
+	uint32_t* o16 = a.cm16 + (active ? job : 0) * a.cm_stride;
+	uint32_t* o8 = a.cm8 + (active ? job : 0) * a.cm_stride;
+	/* uniform step count of the workgroup: the longest target of its jobs */
+	int maxcols = 0;
+	for (int k = 0; k < nch; ++k) {
+		const int64_t jj = (int64_t)blockIdx.x * nch + k;
+		if (jj >= a.njobs) break;
+		const ssw_pjob o = a.jobs[jj];
+		int L = (int)(a.toff[o.ta + 1] - a.toff[o.ta]);
+		if (o.qb >= 0) { const int Lb = (int)(a.toff[o.tb + 1] - a.toff[o.tb]); L = Lb > L ? Lb : L; }
+		maxcols = L > maxcols ? L : maxcols;
+	}
+	const int nsteps = (maxcols + 16 + 15) & ~15;
+	const int last_step = maxcols + 15;
+
+	/* two target rings: profile offsets of ta's columns (low halves) and tb's (high halves) */
+	lds_st16(lds, ringa + 2u * (48 + l16), nulloff);
+	lds_st16(lds, ringb + 2u * (48 + l16), nulloff);
+	{
+		int ca = l16 < ncola ? tga[l16] : a.n, cb = l16 < ncolb ? tgb[l16] : a.n;
+		if (ca < 0 || ca > a.n) ca = a.n;
+		if (cb < 0 || cb > a.n) cb = a.n;
+		lds_st16(lds, ringa + 2u * l16, (u32)ca * G::PSTRIDE); lds_st16(lds, ringa + 2u * (64 + l16), (u32)ca * G::PSTRIDE);
+		lds_st16(lds, ringb + 2u * l16, (u32)cb * G::PSTRIDE); lds_st16(lds, ringb + 2u * (64 + l16), (u32)cb * G::PSTRIDE);
+	}
+	u32 nxa, nxb;
+	{
+		const int tc = 16 + l16;
+		int ca = tc < ncola ? tga[tc] : a.n, cb = tc < ncolb ? tgb[tc] : a.n;
+		if (ca < 0 || ca > a.n) ca = a.n;
+		if (cb < 0 || cb > a.n) cb = a.n;
+		nxa = (u32)ca * G::PSTRIDE; nxb = (u32)cb * G::PSTRIDE;
+	}
+	__syncthreads();
+
+	const u32 zero0 = FR ? pk_dup(fr_phi(0, l16, 16, a.fr_base, a.fr_kmask, gapEi) - gapEi) : 0u;
+	u32 fl = zero0 + a.gapE2;
+	u32 H[R], E[R], snap[R];
+#pragma unroll
+	for (int r = 0; r < R; ++r) { H[r] = zero0; E[r] = FR ? fl : 0u; snap[r] = 0; }
+	u32 Hlast = zero0, Fout = FR ? zero0 + a.gapE2 : zero0, cmout = zero0, ck = 0, hsave = zero0;
+	u32 best = zero0;
+	u32 btc2 = 0xffffffffu;
+	const u32 lane_prof = pbase + (u32)l16 * 16u;
+	const u32 gO = FR ? a.gapO2 - a.gapE2 : a.gapO2;
+	const u32 gE = a.gapE2;
+	const u32 gEv = opaque(gE);
+	u32 fin = 0;
+
+	u32x4 sa[C], sb[C];
+	u32 pa_n, pb_n;
+	{
+		const u32 r0 = 2u * (u32)((0 - l16) & 63);
+		const u32 pa0 = lds_ld16(lds, ringa + r0) + lane_prof, pb0 = lds_ld16(lds, ringb + r0) + lane_prof;
+#pragma unroll
+		for (int c = 0; c + 1 < C; ++c) { sa[c] = lds_ld128(lds, pa0 + 256u * c); sb[c] = lds_ld128(lds, pb0 + 256u * c); }
+		sa[C - 1] = lds_ld_rows<R - 4 * (C - 1)>(lds, pa0 + 256u * (C - 1));
+		sb[C - 1] = lds_ld_rows<R - 4 * (C - 1)>(lds, pb0 + 256u * (C - 1));
+		pa_n = lds_ld16(lds, ringa + r0 + 2u) + lane_prof;
+		pb_n = lds_ld16(lds, ringb + r0 + 2u) + lane_prof;
+	}
+
+	for (int s0 = 0; s0 < nsteps; s0 += 16) {
+		if (FR && s0 > 0 && (s0 & a.fr_kmask) == 0) {
+			const u32 k = (u32)(a.fr_kmask + 1) * a.gapE2;
+#pragma unroll
+			for (int r = 0; r < R; ++r) { H[r] -= k; E[r] -= k; }
+			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl -= k; best -= k;
+		}
+		{
+			const int p = (s0 + 16 + l16) & 63;
+			lds_st16(lds, ringa + 2u * p, nxa); lds_st16(lds, ringb + 2u * p, nxb);
+			if (p < 32) { lds_st16(lds, ringa + 2u * (64 + p), nxa); lds_st16(lds, ringb + 2u * (64 + p), nxb); }
+			const int tc = s0 + 32 + l16;
+			int ca = tc < ncola ? tga[tc] : a.n, cb = tc < ncolb ? tgb[tc] : a.n;
+			if (ca < 0 || ca > a.n) ca = a.n;
+			if (cb < 0 || cb > a.n) cb = a.n;
+			nxa = (u32)ca * G::PSTRIDE; nxb = (u32)cb * G::PSTRIDE;
+		}
+		wave_lds_fence();
+		if (s0 >= 32) {
+			const int tc = s0 - 32 + l16;
+			if (tc < ncols) {
+				const u32 v16 = lds_ld32(lds, out16 + 4u * ((u32)(tc + 15) & OM)), v8 = lds_ld32(lds, out8 + 4u * ((u32)(tc + G::TAP) & OM));
+				o16[tc] = FR ? v16 - pk_dup(fr_phi(tc + 15, 15, 16, a.fr_base, a.fr_kmask, gapEi)) : v16;
+				o8[tc] = FR ? v8 - pk_dup(fr_phi(tc + G::TAP, G::TAP, 16, a.fr_base, a.fr_kmask, gapEi)) : v8;
+			}
+		}
+		wave_lds_fence();
+		{   /* the chain's best so far, once per 16 steps (k_filldb) */
+			const u32 ph = FR ? fl - a.gapE2 : 0u;
+			u32 g = best - ph;
+			g = pk_max(g, xl_row_ror<1>(g)); g = pk_max(g, xl_row_ror<2>(g)); g = pk_max(g, xl_row_ror<4>(g)); g = pk_max(g, xl_row_ror<8>(g));
+			best = pk_max(best, pk_subu(g, 0x00010001u) + ph);
+		}
+		const u32 rp = 2u * (u32)((s0 - l16) & 63);
+		const u32 ob16 = out16 + 4u * ((u32)s0 & OM), ob8 = out8 + 4u * ((u32)s0 & OM);
+		const int jend = last_step - s0 < 16 ? (last_step - s0 + UNROLL - 1) / UNROLL * UNROLL : 16;
+		for (int j0 = 0; j0 < jend; j0 += UNROLL)
+#pragma unroll
+		for (int ju = 0; ju < UNROLL; ++ju) {
+			const int j = j0 + ju;
+			const int tc = s0 + j - l16;
+			const u32 pa_next = lds_ld16(lds, ringa + rp + 2u * (j + 2)), pb_next = lds_ld16(lds, ringb + rp + 2u * (j + 2));
+			u32 hin, f;
+			if (FR) {
+				hin = xl_row_shr1_umax(Hlast, fl); fl += gE; best += gE;
+				xl_row_shr1_sub_keep(fin, Fout, gEv);
+				f = fin;
+			} else { hin = xl_row_shr1_zero(Hlast); f = xl_row_shr1_zero(Fout); }
+			u32 cm = xl_row_shr1_zero(cmout);
+			const u32 pre = pk_max(best, cm);
+			pj_rows<R, FR>(lds, pa_n, pb_n, sa, sb, H, E, hsave, f, cm, ck, gO, gE, fl);
+			pa_n = pa_next + lane_prof; pb_n = pb_next + lane_prof;
+			hsave = hin; Hlast = H[R - 1]; Fout = f; cmout = cm;
+			best = pk_max(best, cm);
+			if (G::TAP == 15) {
+				if (l16 == 15) { lds_st32(lds, ob16 + 4u * j, cm); lds_st32(lds, ob8 + 4u * j, ck); }
+			} else {
+				if (l16 == 15) lds_st32(lds, ob16 + 4u * j, cm);
+				if (l16 == G::TAP) lds_st32(lds, ob8 + 4u * j, ck);
+			}
+			if (wave_any(best != pre)) db_record<R>(best, pre, tc, H, snap, btc2);
+		}
+	}
+	int bval[2], btc[2], brow[2];
+	{
+		u32 mx = 0;
+#pragma unroll
+		for (int r = 0; r < R; ++r) mx = pk_max(mx, snap[r]);
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			bval[h] = (int)((mx >> (16 * h)) & 0xffffu);
+			btc[h] = bval[h] > 0 ? (int)((btc2 >> (16 * h)) & 0xffffu) : 0x7fffffff;
+			brow[h] = 0x7fffffff;
+#pragma unroll
+			for (int k = R - 1; k >= 0; --k) if (bval[h] > 0 && (int)((snap[k] >> (16 * h)) & 0xffffu) == bval[h]) brow[h] = l16 * R + k;
+			if (FR && bval[h] > 0) bval[h] -= fr_phi(btc[h] + l16, l16, 16, a.fr_base, a.fr_kmask, gapEi);
+		}
+	}
+	wave_lds_fence();
+	for (int base = nsteps - 32; base < nsteps; base += 16) {
+		const int tc = base + l16;
+		if (tc >= 0 && tc < ncols) {
+			const u32 v16 = lds_ld32(lds, out16 + 4u * ((u32)(tc + 15) & OM)), v8 = lds_ld32(lds, out8 + 4u * ((u32)(tc + G::TAP) & OM));
+			o16[tc] = FR ? v16 - pk_dup(fr_phi(tc + 15, 15, 16, a.fr_base, a.fr_kmask, gapEi)) : v16;
+			o8[tc] = FR ? v8 - pk_dup(fr_phi(tc + G::TAP, G::TAP, 16, a.fr_base, a.fr_kmask, gapEi)) : v8;
+		}
+	}
+	dev_fence();
+
+	/* ---- per half: the reduction of k_filldb over this half's own target ---- */
+	const u32 red = ringa;      /* the rings are free now */
+	for (int h = 0; h < 2; ++h) {
+		if (h == 1 && jb.qb < 0) continue;           /* uniform in the chain */
+		const int len = h ? lenb : lena, nc = h ? ncolb : ncola;
+		lds_st32(lds, red + 16u * l16, (u32)bval[h]);
+		lds_st32(lds, red + 16u * l16 + 4, (u32)btc[h]);
+		lds_st32(lds, red + 16u * l16 + 8, (u32)brow[h]);
+		wave_lds_fence();
+		int bv = 0, bc = 0x7fffffff, br = 0x7fffffff;
+		for (int k = 0; k < 16; ++k) {
+			const int v = (int)lds_ld32(lds, red + 16u * k), cc = (int)lds_ld32(lds, red + 16u * k + 4), w = (int)lds_ld32(lds, red + 16u * k + 8);
+			if (v > bv || (v == bv && v > 0 && cc < bc)) { bv = v; bc = cc; br = w; }
+		}
+		wave_lds_fence();
+		const bool padded = (len & 15) >= 1 && (len & 15) <= 8;
+		const int maskLen = a.maskLen >= 0 ? a.maskLen : len / 2;
+		const bool have_byte = a.score_size == 0 || a.score_size == 2, have_word = a.score_size == 1 || a.score_size == 2;
+		int word = 0, status = 0;
+		if (have_byte && bv < 255 - a.bias) word = 0;
+		else if (have_word) word = 1;
+		else status = 1;
+		int s2 = 0, i2 = 0x7fffffff;
+		if (status == 0 && bv > 0) {
+			const uint32_t* arr = (word && padded) ? o8 : o16;
+			const int lo_edge = bc - maskLen > 0 ? bc - maskLen : 0;
+			const int hi_edge = bc + maskLen > nc ? nc : bc + maskLen;
+			const int up_from = word ? hi_edge : hi_edge + 1;
+			for (int c = l16; c < nc; c += 16) {
+				if (c < lo_edge || c >= up_from) {
+					const int v = (int)((arr[c] >> (16 * h)) & 0xffffu);
+					if (v > s2) { s2 = v; i2 = c; }
+				}
+			}
+		}
+		lds_st32(lds, red + 16u * l16, (u32)s2);
+		lds_st32(lds, red + 16u * l16 + 4, (u32)i2);
+		wave_lds_fence();
+		if (l16 == 0 && active) {
+			for (int k = 1; k < 16; ++k) {
+				const int v = (int)lds_ld32(lds, red + 16u * k), cc = (int)lds_ld32(lds, red + 16u * k + 4);
+				if (v > s2 || (v == s2 && cc < i2)) { s2 = v; i2 = cc; }
+			}
+			ssw_out_rec o;
+			o.score1 = 0; o.score2 = 0; o.ref_begin1 = -1; o.ref_end1 = 0; o.read_begin1 = -1; o.read_end1 = 0; o.ref_end2 = 0;
+			o.cigarLen = 0; o.edit_distance = 0; o.cigar_off = -1; o.flag = 0;
+			o.status = (uint16_t)(status | (a.mark_word && word && status == 0 && bv > 0 ? SSW_OUT_WORD : 0));
+			if (status == 0 && bv > 0) {
+				o.score1 = (uint16_t)bv; o.ref_end1 = bc; o.read_end1 = br < len - 1 ? br : len - 1;
+				if (maskLen >= 15) { o.score2 = (uint16_t)s2; o.ref_end2 = s2 > 0 ? i2 : 0; }
+				else { o.score2 = 0; o.ref_end2 = -1; }
+			}
+			a.out[2 * job + h] = o;
+			if (a.counters && status == 0 && bv > 0) atomicAdd(a.counters + (word ? 0 : 1), 1);
+		}
+		wave_lds_fence();
+	}
+}
+
+template <int R, bool FR>
+__global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(1, 8) k_fillpairs(ssw_fillpairs_args a)
+{
+	SSW_DYN_LDS(lds);
+	if (FR) fillpairs_pass<R, true, DB_UNROLL>(a, lds);
+	else fillpairs_pass<R, false, 4>(a, lds);
 }
 
 /* ================================================================================================
@@ -3270,6 +3574,18 @@ __global__ void __launch_bounds__(256) k_gather(ssw_gather_args a)
 	for (int i = 0; i < len; ++i) dst[i] = src[i];
 }
 
+/* k_seqgather: sequence src_idx[i] of a set into slot i of a new one (ssw_gpu_align_pairs: the queries of one target's fallback batch).
+   One workgroup per sequence. */
+__global__ void __launch_bounds__(256) k_seqgather(ssw_seqgather_args a)
+{
+	const int i = (int)blockIdx.x;
+	if (i >= a.count) return;
+	const int8_t* src = a.src + a.src_off[a.idx[i]];
+	int8_t* dst = a.dst + a.dst_off[i];
+	const int64_t len = a.dst_off[i + 1] - a.dst_off[i];
+	for (int64_t k = threadIdx.x; k < len; k += blockDim.x) dst[k] = src[k];
+}
+
 /* k_select (ssw_select_args): the pairs of a database-search chunk that go on to the reverse pass, compacted in (bucket-ordered
    query, target) order.  256 pairs per block; linear index i = k * nt + t, query order[k], record out[order[k] * nt + t]. */
 SSW_DEV bool select_pred(const ssw_select_args& a, int64_t i, int64_t n, int& q, int& t, ssw_out_rec& o)
@@ -3442,6 +3758,44 @@ extern "C" int ssw_shim_launch_filldb(int R, const ssw_filldb_args* a, void* str
 #undef X
 		default: return -2;
 	}
+	return SSW_LAUNCH_OK();
+}
+
+/* k_fillpairs: every chain keeps its own profile ((n + 1) x PSTRIDE bytes) and two target rings; as many chains per workgroup as fit
+   the LDS, at most 16 */
+extern "C" int ssw_shim_fillpairs_nch(int R, int n)
+{
+	if (R < 1 || R > 40) return 0;
+	const int64_t per = (int64_t)(n + 1) * ((R + 3) / 4) * 256 + PJ_CHAIN_EXTRA;
+	int64_t k = (int64_t)SSW_LDS_LIMIT / per;
+	return k > 16 ? 16 : (int)k;
+}
+extern "C" int ssw_shim_launch_fillpairs(int R, const ssw_fillpairs_args* a, void* stream)
+{
+	ssw_fillpairs_args args = *a;
+	const int nmax = ssw_shim_fillpairs_nch(R, args.n);
+	if (nmax < 1) return -2;
+	const int nch = args.nch > 0 && args.nch < nmax ? args.nch : nmax;      /* (the host may ask for fewer: small scratch budgets) */
+	args.nch = nch;
+	const int64_t grid = (args.njobs + nch - 1) / nch;
+	if (grid <= 0) return 0;
+	switch (R) {
+#define X(r) case r: { const size_t ldsb = (size_t)nch * ((size_t)(args.n + 1) * ChainGeom<r>::PSTRIDE + PJ_CHAIN_EXTRA); \
+		if (args.form) SSW_LAUNCH((k_fillpairs<r, true>), ssw_fillpairs_args, args, grid, 16 * nch, ldsb, stream); \
+		else SSW_LAUNCH((k_fillpairs<r, false>), ssw_fillpairs_args, args, grid, 16 * nch, ldsb, stream); } break;
+		FOR_EACH_R(X)
+		FOR_EACH_DBR_LONG(X)
+#undef X
+		default: return -2;
+	}
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream)
+{
+	ssw_seqgather_args args = *a;
+	if (args.count <= 0) return 0;
+	SSW_LAUNCH(k_seqgather, ssw_seqgather_args, args, args.count, 256, 0, stream);
 	return SSW_LAUNCH_OK();
 }
 

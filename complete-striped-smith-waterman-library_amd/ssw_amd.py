@@ -105,6 +105,10 @@ def load(path=None):
     L.ssw_gpu_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Params),
                                       C.c_void_p, C.POINTER(_u32p), _i64p]
     L.ssw_gpu_align_batch.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_pairs"):
+        L.ssw_gpu_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params),
+                                          C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_pairs.restype = C.c_int
     L.ssw_gpu_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ssw_gpu_last_timing.restype = C.c_int
     L.ssw_gpu_last_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -257,6 +261,38 @@ class Context(object):
                                           C.byref(words))
         if rc != 0:
             raise RuntimeError("ssw_gpu_align_batch: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        if want_cigar and words.value > 0:
+            cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy()
+        else:
+            cig = np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        return res, cig
+
+    def align_pairs(self, queries, targets, qidx, tidx, mat, n, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1,
+                    score_size=2, want_cigar=True, mark_mismatch=False, out=None):
+        """explicit pair list (ssw_gpu_align_pairs): record i is the alignment of query qidx[i] against target tidx[i]
+        -> (numpy record array [npairs] of RESULT_DTYPE, numpy uint32 CIGAR pool in pair order)"""
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        if qi.ndim != 1 or qi.shape != ti.shape:
+            raise ValueError("qidx and tidx must be 1-D arrays of the same length")
+        npairs = int(qi.shape[0])
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            res = np.zeros(npairs, dtype=RESULT_DTYPE)
+        else:
+            res = out
+            if res.dtype != RESULT_DTYPE or res.shape != (npairs,) or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a C-contiguous [npairs] array of RESULT_DTYPE")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_align_pairs(self.h, queries.h, targets.h, qi.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                                          npairs, C.byref(p), res.ctypes.data_as(C.c_void_p),
+                                          C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_align_pairs: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
         if want_cigar and words.value > 0:
             cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy()
         else:

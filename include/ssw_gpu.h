@@ -120,6 +120,24 @@ int ssw_gpu_align_batch(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
                         int32_t target_first, int32_t target_count, const ssw_gpu_params* params,
                         ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
 
+/*
+ * Align an explicit list of (query, target) pairs: results[i] is, bit for bit, the record that
+ * ssw_gpu_align_batch(ctx, queries, targets, tidx[i], 1, ...) gives at row qidx[i] -- the loop "for each read: ssw_align
+ * against ITS window(s)" of a mapper or variant caller as one call.  Pairs come in any order, repeats allowed.  The CIGAR pool
+ * (optional, malloc()ed, caller frees) holds the CIGARs in pair order.  npairs == 0 returns 0 with *cigar_words = 0; an index out of
+ * range returns -1 with a message before anything is launched or written.  Every phase stays within ssw_gpu_get_budget(ctx).
+ *
+ * Fast path (one fused kernel, k_fillpairs: two pairs per 16-lane chain, each half of a register against its own target): gapO > gapE,
+ * n <= 32, max(mat) <= 49, queries of 1..640 residues (n x ceil(ceil(len/16)/4) x 256 < 64 KiB), targets of 1..65 000 columns; with
+ * flag != 0 the pairs that pass src/ssw.c:916 then go through ONE batched reverse pass and traceback (targets below 2^31 residues in all).
+ * Every other pair -- empty sequences, longer ones, gapO <= gapE, wider alphabets, larger scores -- is answered exactly but SLOWLY: one
+ * internal ssw_gpu_align_batch per distinct target over the subset of its queries (gathered on the device).
+ */
+int ssw_gpu_align_pairs(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                        const int32_t* qidx, const int32_t* tidx, int64_t npairs,
+                        const ssw_gpu_params* params, ssw_gpu_result* results,
+                        uint32_t** cigar_pool, int64_t* cigar_words);
+
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
    an earlier, shorter ssw_gpu_timing passes ITS sizeof and is not written past it */

@@ -135,6 +135,45 @@ class BatchAligner {
     free(pool);
   }
 
+  // A mapper's loop as one call: alignments[i] is what Aligner::Align(queries[i], filter, &alignments[i], maskLen) gives against reference
+  // target_index_per_query[i] (ssw_gpu_align_pairs); flags[i] (optional) its return value.  maskLen < 15 is raised to 15 like there.
+  void AlignPairs(const std::vector<std::string>& queries, const std::vector<int32_t>& target_index_per_query, const Filter& filter,
+                  std::vector<Alignment>* alignments, int32_t maskLen, std::vector<uint16_t>* flags = 0) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::AlignPairs: no reference sequences");
+    if (target_index_per_query.size() != queries.size()) throw std::runtime_error("BatchAligner::AlignPairs: one target index per query");
+    const int32_t nq = (int32_t)queries.size();
+    for (int32_t i = 0; i < nq; ++i)
+      if (target_index_per_query[(size_t)i] < 0 || target_index_per_query[(size_t)i] >= n_targets_) throw std::runtime_error("BatchAligner::AlignPairs: no such reference sequence");
+    alignments->assign(queries.size(), Alignment());
+    if (flags) flags->assign(queries.size(), 0);
+    if (nq == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0);
+    for (int32_t i = 0; i < nq; ++i) { text += queries[i]; off.push_back((int64_t)text.size()); }
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nq, table_.data());
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<int32_t> qidx((size_t)nq);
+    for (int32_t i = 0; i < nq; ++i) qidx[(size_t)i] = i;
+    std::vector<ssw_gpu_result> res((size_t)nq);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_align_pairs(ctx_, Q, targets_, qidx.data(), target_index_per_query.data(), nq, &p, res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_pairs: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t i = 0; i < nq; ++i) {
+      const ssw_gpu_result& r = res[(size_t)i];
+      Alignment& a = (*alignments)[(size_t)i];
+      a.sw_score = r.score1; a.sw_score_next_best = r.score2; a.ref_begin = r.ref_begin1; a.ref_end = r.ref_end1;
+      a.query_begin = r.read_begin1; a.query_end = r.read_end1; a.ref_end_next_best = r.ref_end2;
+      if (flags) (*flags)[(size_t)i] = r.flag;
+      const int8_t* ref = ref_codes_.data() + ref_off_[(size_t)target_index_per_query[(size_t)i]];
+      Expand(a, r.cigarLen > 0 ? pool + r.cigar_off : 0, r.cigarLen, ref, text.data() + off[(size_t)i], (int)queries[(size_t)i].size());
+    }
+    free(pool);
+  }
+
  private:
   // soft clips, '=' / 'X' runs and the mismatch count of one alignment: the outcome of the reference's ConvertAlignment +
   // CalculateNumberMismatch (ssw_cpp.cpp:52-89, 123-199).  Like there, the clips are written even when ssw_align returned no CIGAR
