@@ -371,6 +371,22 @@ typedef struct {
 	int32_t count;
 } ssw_seqgather_args;
 
+/* Top-K selection of the database search (ssw_gpu_search_topk): one launch per streamed chunk merges the chunk's compact records
+   hits[q][nt] into a running list per query, kept in HBM across chunks.  The list of query q holds cnt <= k entries sorted by score1
+   descending, then target ascending: target lst_t[q * k + r], record lst_h[q * k + r]; state[2 q] = cnt, state[2 q + 1] = score1 of
+   entry k - 1 once the list is full (the admission score: a later chunk enters only above it).  All-zero state = empty lists. */
+typedef struct {
+	const struct ssw_hit_rec* hits;   /* [nq][nt]: the chunk's records, target tfirst + j at column j */
+	int32_t nq, nt;
+	int32_t tfirst;          /* target index of column 0 */
+	int32_t k;               /* 1 .. SSW_GPU_TOPK_MAX */
+	int32_t cap;             /* entries of the LDS key buffer: a power of two >= 2 k (and >= 64) */
+	int32_t min_score;       /* eligible: score1 >= max(min_score, 1), ref_end2 != -2 */
+	int32_t* lst_t;          /* [nq][k] */
+	struct ssw_hit_rec* lst_h; /* [nq][k] */
+	int32_t* state;          /* [nq][2] */
+} ssw_topk_args;
+
 /* sequence preparation on the device: ASCII -> residue codes, reverse complement of code sequences */
 typedef struct {
 	const uint8_t* text;     /* mode 0: ASCII residues */
@@ -438,6 +454,7 @@ int ssw_shim_launch_select(const ssw_select_args* a, void* stream);   /* the pas
 int ssw_shim_launch_mark(const ssw_mark_args* a, void* stream);
 int ssw_shim_launch_prep(const ssw_prep_args* a, void* stream);
 int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream);
+int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefront per query */
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

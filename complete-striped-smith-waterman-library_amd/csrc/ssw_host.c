@@ -98,6 +98,7 @@ struct ssw_gpu_ctx {
 	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab;
 	dbuf sres, svq, svt, scnt;          /* flagged database search: survivor records, their (query, target) maps, counters */
 	dbuf scratch0, need0, list0;        /* traceback: round 0 of the narrow alignments while the wide ones' teams already run (trace_phase "early") */
+	dbuf tk_hits0, tk_hits1, tk_lst;    /* top-K search: the two chunk record buffers, the per-query lists + their state */
 	void** ev; int nev, capev;          /* event pairs around fill launches */
 	void *ev_t0, *ev_a, *ev_b, *ev_c, *ev_d, *ev_db;
 	size_t cm_budget;                   /* bytes allowed for the two column-max buffers */
@@ -327,6 +328,7 @@ void ssw_gpu_close(ssw_gpu_ctx* c)
 	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab);
 	dbuf_free(&c->sres); dbuf_free(&c->svq); dbuf_free(&c->svt); dbuf_free(&c->scnt);
 	dbuf_free(&c->scratch0); dbuf_free(&c->need0); dbuf_free(&c->list0);
+	dbuf_free(&c->tk_hits0); dbuf_free(&c->tk_hits1); dbuf_free(&c->tk_lst);
 	for (int i = 0; i < c->capev; ++i) ssw_shim_event_destroy(c->ev[i]);
 	free(c->ev);
 	ssw_shim_event_destroy(c->ev_t0); ssw_shim_event_destroy(c->ev_a); ssw_shim_event_destroy(c->ev_b);
@@ -636,12 +638,19 @@ static int tkey_cmp(const void* a, const void* b)
 	return x->t < y->t ? -1 : (x->t > y->t);
 }
 
+/* select mode of the streamed search (ssw_gpu_search_topk): k_topk merges every chunk into per-query lists on the second stream */
+typedef struct {
+	ssw_topk_args a;                    /* lists, k, key buffer, min_score (hits / nt / tfirst are set per chunk) */
+	void** ev; int nev;                 /* an event pair around the selection of every chunk (2 x chunks, created by the caller) */
+} topk_sel;
+
 /* streamed database search (ssw_gpu_search_db): compact records of one target chunk go to one of two device buffers, are
    downloaded on the second stream into one of two page-locked host buffers while the next chunk is computed, and are handed
-   to the caller's function */
+   to the caller's function -- or, in select mode (fn == NULL, sel set), stay on the device for k_topk */
 typedef struct {
 	int32_t chunk;                      /* targets per chunk */
 	ssw_gpu_hits_fn fn; void* user;
+	topk_sel* sel;
 	struct ssw_hit_rec* d_hits[2];
 	ssw_gpu_hit* h_hits[2];
 	int fn_rc;                          /* non-zero: the caller's function asked to stop */
@@ -750,6 +759,8 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 		const int buf = chunk_i & 1;
 		if (ds) {      /* all-zero bytes ARE the empty compact record (score 0, ends 0): empty queries / targets need no patching */
 			d_hits = ds->d_hits[buf]; d_cnt = d_cnt_s;
+			/* select mode: the selection that last read this buffer (two chunks back) must be done -- a wait of the stream, not of the host */
+			if (ds->sel && chunk_i >= 2 && ssw_shim_stream_wait_event(c->stream, c->ev_red[buf])) { fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; }
 			if (ssw_shim_memset(d_hits, 0, sizeof(struct ssw_hit_rec) * (size_t)nq * (size_t)nt, c->stream)) { fail(c, "memset failed: %s", ssw_shim_last_error()); goto done; }
 		} else
 		if (direct) {
@@ -842,6 +853,18 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 		}
 		ssw_shim_event_record(e1, c->stream);
 		c->tm.fill_launches++;      /* one launch group: all size classes of this chunk of targets */
+		if (ds && ds->sel) {      /* select mode: k_topk on the second stream after this chunk's fill, while the next chunk is computed */
+			topk_sel* s = ds->sel;
+			s->a.hits = d_hits; s->a.nt = nt; s->a.tfirst = tfirst + t0;
+			if (2 * chunk_i + 1 >= s->nev) { fail(c, "top-K selection: %s", "more chunks than planned"); goto done; }
+			if (ssw_shim_event_record(c->ev_fill[buf], c->stream) || ssw_shim_stream_wait_event(c->stream2, c->ev_fill[buf]) ||
+			    ssw_shim_event_record(s->ev[2 * chunk_i], c->stream2) || ssw_shim_launch_topk(&s->a, c->stream2) ||
+			    ssw_shim_event_record(s->ev[2 * chunk_i + 1], c->stream2) || ssw_shim_event_record(c->ev_red[buf], c->stream2)) {
+				fail(c, "top-K selection launch failed: %s", ssw_shim_last_error()); goto done;
+			}
+			prev_t0 = t0; prev_nt = nt;
+			continue;
+		}
 		if (ds) {   /* download of this chunk on the second stream; meanwhile hand the previous chunk to the caller */
 			if (ssw_shim_event_record(c->ev_fill[buf], c->stream) || ssw_shim_stream_wait_event(c->stream2, c->ev_fill[buf]) ||
 			    ssw_shim_d2h(ds->h_hits[buf], d_hits, sizeof(struct ssw_hit_rec) * (size_t)nq * (size_t)nt, c->stream2) ||
@@ -922,12 +945,14 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 	if (ds && prev_t0 >= 0) {     /* the last chunk */
 		const int buf = (chunk_i - 1) & 1;
 		int32_t cnt[DB_COUNTERS] = { 0, 0, 0, 0 };
-		if (ssw_shim_event_sync(c->ev_red[buf]) || ssw_shim_d2h(cnt, d_cnt_s, sizeof cnt, c->stream) || ssw_shim_stream_sync(c->stream)) {
+		/* (select mode: the main stream waits for the last selection -- the call's end event then covers it) */
+		if ((ds->sel ? ssw_shim_stream_wait_event(c->stream, c->ev_red[buf]) : ssw_shim_event_sync(c->ev_red[buf])) ||
+		    ssw_shim_d2h(cnt, d_cnt_s, sizeof cnt, c->stream) || ssw_shim_stream_sync(c->stream)) {
 			fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
 		}
 		c->tm.n_word += cnt[0]; c->tm.n_byte += cnt[1]; c->tm.db_repeats += cnt[2];
 		c->tm.cells += (Q->h_off[nq] - Q->h_off[0]) * (T->h_off[tfirst + tcount] - T->h_off[tfirst]);
-		ds->fn_rc = ds->fn(ds->user, tfirst + prev_t0, prev_nt, ds->h_hits[buf]);
+		if (!ds->sel) ds->fn_rc = ds->fn(ds->user, tfirst + prev_t0, prev_nt, ds->h_hits[buf]);
 	}
 	rc = 0;
 done:
@@ -2815,6 +2840,195 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seq
 		return SSW_GPU_BUSY;
 	}
 	const int rc = align_pairs_locked(c, Q, T, qidx, tidx, npairs, prm, results, cigar_pool, cigar_words);
+	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
+	return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Top-K database search (ssw_gpu_search_topk): the best k eligible targets of every query, selected on the device.
+ *   streamed path (the fused database search's envelope): ssw_gpu_search_db's chunk loop in select mode -- k_topk merges every chunk's
+ *   [nq][nt] compact records into per-query lists in HBM on the second stream, the lists come to the host once, at the end;
+ *   generic path (SSW_NOT_STREAMABLE): full records per chunk, merged on the host with the same order -- exact, slower;
+ *   flag != 0: the selected (query, target) pairs, in (q, r) order, through align_pairs_locked with the caller's parameters.
+ * Queries go in blocks whose lists take at most half the budget; the two chunk buffers at most a quarter each.
+ * ------------------------------------------------------------------------------------------------ */
+static void topk_pad(ssw_gpu_result* o) { memset(o, 0, sizeof *o); o->ref_begin1 = -1; o->read_begin1 = -1; o->cigar_off = -1; }
+static uint64_t topk_hkey(uint32_t score1, int32_t t) { return ((uint64_t)score1 << 32) | (uint32_t)~(uint32_t)t; }
+
+typedef struct { uint64_t key; int32_t t; ssw_gpu_result r; } topk_cand;
+static int topk_cand_cmp(const void* a, const void* b)
+{
+	const uint64_t x = ((const topk_cand*)a)->key, y = ((const topk_cand*)b)->key;
+	return x < y ? 1 : x > y ? -1 : 0;      /* descending */
+}
+
+/* generic path of one query block: lists in lt[q * k ..] / lr[q * k ..], counts in cnt[] */
+static int topk_generic(ssw_gpu_ctx* c, const ssw_gpu_seqs* V, const ssw_gpu_seqs* T, const ssw_gpu_params* p0, int32_t k, int32_t lo,
+                        int64_t chunk, int32_t* lt, ssw_gpu_result* lr, ssw_gpu_timing* acc, int64_t* best_cells)
+{
+	const int32_t nq = V->count, nt_all = T->count;
+	ssw_gpu_result* full = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nq * (size_t)chunk);
+	topk_cand* cand = (topk_cand*)malloc(sizeof(topk_cand) * ((size_t)k + (size_t)chunk));
+	int32_t* cnt = (int32_t*)calloc((size_t)nq, sizeof(int32_t));
+	int rc = -1;
+	if (!full || !cand || !cnt) { fail(c, "out of host memory (%s)", "top-K search"); goto out; }
+	for (int32_t t0 = 0; t0 < nt_all; t0 += (int32_t)chunk) {
+		const int32_t nt = nt_all - t0 < chunk ? nt_all - t0 : (int32_t)chunk;
+		if (align_batch_locked(c, V, T, t0, nt, p0, full, 0, 0, 0)) goto out;
+		timing_add(acc, &c->tm, best_cells);
+		for (int32_t q = 0; q < nq; ++q) {
+			int32_t* qt = lt + (int64_t)q * k; ssw_gpu_result* qr = lr + (int64_t)q * k;
+			const int32_t m0 = cnt[q];
+			int32_t need = lo;
+			if (m0 == k && (int32_t)qr[k - 1].score1 + 1 > need) need = qr[k - 1].score1 + 1;      /* ties stay with the lower target */
+			int64_t n = 0;
+			for (int32_t r = 0; r < m0; ++r) { cand[n].key = topk_hkey(qr[r].score1, qt[r]); cand[n].t = qt[r]; cand[n].r = qr[r]; ++n; }
+			for (int32_t j = 0; j < nt; ++j) {
+				const ssw_gpu_result* r = &full[(int64_t)q * nt + j];
+				if (r->status != 0 || (int32_t)r->score1 < need) continue;
+				cand[n].key = topk_hkey(r->score1, t0 + j); cand[n].t = t0 + j; cand[n].r = *r; ++n;
+			}
+			if (n == m0) continue;
+			qsort(cand, (size_t)n, sizeof(topk_cand), topk_cand_cmp);
+			const int32_t m = n < k ? (int32_t)n : k;
+			for (int32_t r = 0; r < m; ++r) { qt[r] = cand[r].t; qr[r] = cand[r].r; }
+			cnt[q] = m;
+		}
+	}
+	rc = 0;
+out:
+	free(full); free(cand); free(cnt);
+	return rc;
+}
+
+static int search_topk_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm, int32_t k,
+                              int32_t min_score, int32_t targets_per_chunk, int32_t* tidx, ssw_gpu_result* results,
+                              uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	const double t_start = wall_ms();
+	const int32_t nq = Q->count, nt_all = T->count;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	memset(&c->tm, 0, sizeof c->tm);
+	if (nq == 0) return 0;
+	for (int64_t i = 0; i < (int64_t)nq * k; ++i) { tidx[i] = -1; topk_pad(&results[i]); }
+	if (nt_all == 0) return 0;
+	ssw_shim_set_device(c->device);
+	if (ctx_side_streams(c)) return -1;
+	/* the lists are decided by score1 alone, which the flag does not change: the search runs score-only, the caller's flag comes after */
+	ssw_gpu_params p0 = *prm;
+	if (p0.flag != 0) { p0.flag = 0; p0.mark_mismatch = 0; }
+	const int32_t lo = min_score > 1 ? min_score : 1;
+	int32_t cap = 64;
+	while (cap < 2 * k) cap <<= 1;
+	const int64_t per_q = (int64_t)k * (int64_t)(sizeof(int32_t) + sizeof(struct ssw_hit_rec)) + 2 * (int64_t)sizeof(int32_t);
+	const int64_t budget = (int64_t)c->cm_budget;
+	int64_t qb = budget / 2 / per_q;
+	if (qb < 1) qb = 1;
+	if (qb > nq) qb = nq;
+	int64_t chunk = targets_per_chunk > 0 ? targets_per_chunk : 2048;
+	const int64_t hits_lim = budget / 4 < ((int64_t)2 << 30) ? budget / 4 : ((int64_t)2 << 30);      /* bytes of one chunk buffer */
+	while (chunk > 16 && qb * chunk * 16 > hits_lim) chunk /= 2;
+	while (qb > 1 && qb * chunk * 16 > hits_lim) qb = (qb + 1) / 2;
+	if (chunk > nt_all) chunk = nt_all;
+	const int64_t nch = (nt_all + chunk - 1) / chunk;
+
+	topk_sel sel; memset(&sel, 0, sizeof sel);
+	ssw_gpu_timing acc; memset(&acc, 0, sizeof acc);
+	int64_t best_cells = 0;
+	int32_t* hlt = 0; struct ssw_hit_rec* hlh = 0; int32_t* hst = 0;
+	int32_t *pq = 0, *pt = 0; int64_t* ppos = 0; ssw_gpu_result* pres = 0;
+	int rc = -1;
+	void* d_hits0 = ensure(c, &c->tk_hits0, (size_t)(qb * chunk * 16));
+	void* d_hits1 = d_hits0 ? ensure(c, &c->tk_hits1, (size_t)(qb * chunk * 16)) : 0;
+	unsigned char* d_lst = d_hits1 ? (unsigned char*)ensure(c, &c->tk_lst, (size_t)(qb * per_q + 64)) : 0;
+	if (!d_lst) goto done;
+	sel.ev = (void**)calloc((size_t)(2 * nch), sizeof(void*));
+	hlt = (int32_t*)malloc(sizeof(int32_t) * (size_t)(qb * k));
+	hlh = (struct ssw_hit_rec*)malloc(sizeof(struct ssw_hit_rec) * (size_t)(qb * k));
+	hst = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)qb);
+	if (!sel.ev || !hlt || !hlh || !hst) { fail(c, "out of host memory (%s)", "top-K search"); goto done; }
+	for (int64_t i = 0; i < 2 * nch; ++i) { sel.ev[i] = ssw_shim_event_create(); if (!sel.ev[i]) { fail(c, "event creation failed: %s", ssw_shim_last_error()); goto done; } sel.nev = (int)(i + 1); }
+	/* list layout: states [qb][2], targets [qb][k], records [qb][k] (16-byte aligned) */
+	int32_t* d_state = (int32_t*)d_lst;
+	int32_t* d_lt = d_state + 2 * qb;
+	struct ssw_hit_rec* d_lh = (struct ssw_hit_rec*)(d_lst + ((size_t)(2 * qb + qb * k) * sizeof(int32_t) + 15) / 16 * 16);
+
+	for (int64_t q0 = 0; q0 < nq; q0 += qb) {
+		const int32_t nb = (int32_t)(nq - q0 < qb ? nq - q0 : qb);
+		struct ssw_gpu_seqs V; V.ctx = c; V.d_codes = Q->d_codes; V.d_off = Q->d_off + q0; V.h_off = Q->h_off + q0; V.count = nb;
+		V.total = V.h_off[nb] - V.h_off[0];
+		int32_t* lt = tidx + q0 * k; ssw_gpu_result* lr = results + q0 * k;
+		if (ssw_shim_memset(d_state, 0, sizeof(int32_t) * 2 * (size_t)nb, c->stream)) { fail(c, "memset failed: %s", ssw_shim_last_error()); goto done; }
+		sel.a.hits = 0; sel.a.nq = nb; sel.a.nt = 0; sel.a.tfirst = 0; sel.a.k = k; sel.a.cap = cap; sel.a.min_score = lo;
+		sel.a.lst_t = d_lt; sel.a.lst_h = d_lh; sel.a.state = d_state;
+		db_stream ds; memset(&ds, 0, sizeof ds);
+		ds.chunk = (int32_t)chunk; ds.sel = &sel;
+		ds.d_hits[0] = (struct ssw_hit_rec*)d_hits0; ds.d_hits[1] = (struct ssw_hit_rec*)d_hits1;
+		const int brc = align_batch_locked(c, &V, T, 0, nt_all, &p0, 0, 0, 0, &ds);
+		if (brc == SSW_NOT_STREAMABLE) {
+			ssw_shim_stream_sync(c->stream); ssw_shim_stream_sync(c->stream2);
+			if (topk_generic(c, &V, T, &p0, k, lo, chunk, lt, lr, &acc, &best_cells)) goto done;
+			continue;
+		}
+		if (brc) { ssw_shim_stream_sync(c->stream); ssw_shim_stream_sync(c->stream2); goto done; }
+		double sel_ms = 0;
+		for (int64_t i = 0; i < nch; ++i) sel_ms += ssw_shim_event_elapsed_ms(sel.ev[2 * i], sel.ev[2 * i + 1]);
+		c->tm.reduce_ms = sel_ms;      /* (include/ssw_gpu.h: the selection's device time) */
+		timing_add(&acc, &c->tm, &best_cells);
+		/* the lists, once */
+		if (ssw_shim_d2h(hst, d_state, sizeof(int32_t) * 2 * (size_t)nb, c->stream) ||
+		    ssw_shim_d2h(hlt, d_lt, sizeof(int32_t) * (size_t)nb * (size_t)k, c->stream) ||
+		    ssw_shim_d2h(hlh, d_lh, sizeof(struct ssw_hit_rec) * (size_t)nb * (size_t)k, c->stream) || ssw_shim_stream_sync(c->stream)) {
+			fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
+		}
+		for (int32_t q = 0; q < nb; ++q) {
+			const int32_t m = hst[2 * q];
+			if (m < 0 || m > k) { fail(c, "top-K search: %s", "corrupt list state"); goto done; }
+			for (int32_t r = 0; r < m; ++r) {      /* a score-only record is what the hit record says (k_filldb writes both from the same values) */
+				const struct ssw_hit_rec* h = &hlh[(int64_t)q * k + r];
+				ssw_gpu_result* o = &lr[(int64_t)q * k + r];
+				lt[(int64_t)q * k + r] = hlt[(int64_t)q * k + r];
+				o->score1 = h->score1; o->score2 = h->score2; o->ref_end1 = h->ref_end1; o->read_end1 = h->read_end1; o->ref_end2 = h->ref_end2;
+			}
+		}
+	}
+	if (prm->flag != 0) {      /* begins, CIGARs, mark_mismatch: the selected pairs through the pair path, with the caller's parameters */
+		int64_t np = 0;
+		for (int64_t i = 0; i < (int64_t)nq * k; ++i) np += tidx[i] >= 0;
+		pq = (int32_t*)malloc(sizeof(int32_t) * (size_t)(np > 0 ? np : 1)); pt = (int32_t*)malloc(sizeof(int32_t) * (size_t)(np > 0 ? np : 1));
+		ppos = (int64_t*)malloc(sizeof(int64_t) * (size_t)(np > 0 ? np : 1)); pres = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)(np > 0 ? np : 1));
+		if (!pq || !pt || !ppos || !pres) { fail(c, "out of host memory (%s)", "top-K pairs"); goto done; }
+		int64_t p = 0;
+		for (int64_t i = 0; i < (int64_t)nq * k; ++i) if (tidx[i] >= 0) { pq[p] = (int32_t)(i / k); pt[p] = tidx[i]; ppos[p] = i; ++p; }
+		if (align_pairs_locked(c, Q, T, pq, pt, np, prm, pres, cigar_pool, cigar_words)) goto done;
+		timing_add(&acc, &c->tm, &best_cells);
+		for (int64_t i = 0; i < np; ++i) results[ppos[i]] = pres[i];
+	}
+	acc.total_ms = wall_ms() - t_start;
+	c->tm = acc;
+	rc = 0;
+done:
+	for (int i = 0; i < sel.nev; ++i) ssw_shim_event_destroy(sel.ev[i]);
+	free(sel.ev); free(hlt); free(hlh); free(hst); free(pq); free(pt); free(ppos); free(pres);
+	return rc;
+}
+
+int ssw_gpu_search_topk(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm, int32_t k, int32_t min_score,
+                        int32_t targets_per_chunk, int32_t* tidx, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "search_topk: NULL context%s", "");
+	if (k < 1 || k > SSW_GPU_TOPK_MAX) return fail(c, "search_topk: k must be 1 .. SSW_GPU_TOPK_MAX%s", "");
+	if (!Q || !T || !prm || !prm->mat || !tidx || !results) return fail(c, "search_topk: NULL argument%s", "");
+	if (Q->ctx != c || T->ctx != c) return fail(c, "search_topk: sequences belong to another context%s", "");
+	if (prm->n < 1) return fail(c, "search_topk: alphabet size must be >= 1%s", "");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "search_topk: score_size must be 0, 1 or 2%s", "");
+	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return SSW_GPU_BUSY;
+	}
+	const int rc = search_topk_locked(c, Q, T, prm, k, min_score, targets_per_chunk, tidx, results, cigar_pool, cigar_words);
 	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
 	return rc;
 }

@@ -3645,6 +3645,159 @@ __global__ void __launch_bounds__(256) k_select(ssw_select_args a)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * k_topk (ssw_topk_args): one wavefront per query row of a streamed database-search chunk merges the row's eligible records into the
+ * query's running top-K list (ssw_gpu_search_topk).  Order: score1 descending, then target ascending, as ONE 64-bit key
+ *   score1 << 48 | ~t << 16 | src      (src: index of the entry in the old list, or TOPK_CHUNK for a record of this chunk)
+ * so that a plain descending sort of keys is the ranking, and a key also says where its record is.
+ *   1. one pass over the row (16-byte loads, lane i reads record j0 + i): eligible records -- ref_end2 != -2, score1 >= max(min_score, 1)
+ *      and, once the list is full, score1 above its admission score -- are compacted into LDS behind the old list's slots by ballot + lane
+ *      prefix (popcount of the ballot below the lane), in target order;
+ *   2. more survivors than the key buffer holds (the first chunk: every record of the row may be eligible): a radix select of the cut
+ *      score S over the two bytes of score1 (two 256-bin LDS histograms, each found by a suffix scan over the lanes' four bins), then the
+ *      row again: everything above S and the first ties at S in target order, exactly k records -- the chunk's own top k;
+ *   3. the old list's keys in front, a bitonic sort (descending) of the next power of two, and the first min(k, total) ranks written back.
+ *      The list is rewritten in place: an old entry can only move DOWN the list (new keys are inserted before it), so ranks are written
+ *      in blocks of 64 from the last block up, each block's sources read before its slots are written.
+ * Ties at the admission score stay with the lower target: chunks come in increasing target order, so a later chunk enters a full list
+ * only with a strictly greater score1.
+ * LDS: cap 8-byte keys (a power of two >= 2 k: the old list + the chunk's survivors; read as ds_read_b64 by consecutive lanes), then the
+ * two histograms (256 x 4 bytes each).
+ * ------------------------------------------------------------------------------------------------ */
+#define TOPK_CHUNK 0xffffu
+
+SSW_DEV unsigned long long topk_ld(const unsigned char* lds, u32 i) { const u32x2 v = lds_ld64(lds, 8u * i); return (unsigned long long)v.x | ((unsigned long long)v.y << 32); }
+SSW_DEV void topk_st(unsigned char* lds, u32 i, unsigned long long v) { lds_st32(lds, 8u * i, (u32)v); lds_st32(lds, 8u * i + 4, (u32)(v >> 32)); }
+SSW_DEV unsigned long long topk_key(u32 score, int t, u32 src) { return ((unsigned long long)score << 48) | ((unsigned long long)(~(u32)t) << 16) | src; }
+
+/* the bin of a 256-bin histogram at which the count from the top first reaches `need` (the histogram holds at least that many);
+   *above = the count of the bins above it.  Lane l owns bins 4 l .. 4 l + 3. */
+SSW_DEV int topk_cut(const unsigned char* lds, u32 base, int need, int lane, int* above)
+{
+	const u32x4 c = lds_ld128(lds, base + 16u * (u32)lane);
+	const int own = (int)(c.x + c.y + c.z + c.w);
+	int suf = own;      /* inclusive suffix sum over the lanes (falls with the lane) */
+	for (int d = 1; d < 64; d <<= 1) {
+		const int v = (int)xl_shfl((u32)suf, lane + d);
+		if (lane + d < 64) suf += v;
+	}
+	const int L = __builtin_popcountll(wave_ballot(suf >= need)) - 1;      /* the last lane whose suffix still reaches `need` */
+	int bin = 0, ab = 0;
+	if (lane == L) {
+		int run = suf - own;
+		const int cw[4] = { (int)c.x, (int)c.y, (int)c.z, (int)c.w };
+		for (int b = 3; b >= 0; --b) {
+			if (run + cw[b] >= need || b == 0) { bin = 4 * lane + b; ab = run; break; }
+			run += cw[b];
+		}
+	}
+	*above = (int)xl_readlane((u32)ab, L);
+	return (int)xl_readlane((u32)bin, L);
+}
+
+__global__ void __launch_bounds__(64) k_topk(ssw_topk_args a)
+{
+	SSW_DYN_LDS(lds);
+	const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+	const int k = a.k, nt = a.nt, cap = a.cap;
+	const u32 hist = 8u * (u32)cap;
+	const ssw_hit_rec* row = a.hits + (int64_t)q * nt;
+	int32_t* lt = a.lst_t + (int64_t)q * k;
+	ssw_hit_rec* lh = a.lst_h + (int64_t)q * k;
+	const int cnt = a.state[2 * (int64_t)q], thr = a.state[2 * (int64_t)q + 1];
+	int lo = a.min_score > 1 ? a.min_score : 1;
+	if (cnt == k && thr + 1 > lo) lo = thr + 1;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	const int room = cap - cnt;
+
+	/* 1. eligible records, compacted in target order behind the old list's slots (counted beyond the room, stored within it) */
+	int m = 0;
+	for (int j0 = 0; j0 < nt; j0 += 64) {
+		const int j = j0 + lane;
+		u32 s = 0; bool ok = false;
+		if (j < nt) { const u32x4 v = *(const u32x4*)(row + j); s = v.x & 0xffffu; ok = (int)v.w != -2 && (int)s >= lo; }
+		const unsigned long long bal = wave_ballot(ok);
+		const int pos = m + __builtin_popcountll(bal & below);
+		if (ok && pos < room) topk_st(lds, (u32)(cnt + pos), topk_key(s, a.tfirst + j, TOPK_CHUNK));
+		m += __builtin_popcountll(bal);
+	}
+	if (m == 0) return;      /* the list stays as it is */
+
+	/* 2. too many: the chunk's own k best (cut score S by a radix select over the high, then the low byte of score1) */
+	if (m > room) {
+		for (int i = lane; i < 512; i += 64) lds_st32(lds, hist + 4u * (u32)i, 0u);
+		__syncthreads();
+		for (int j0 = 0; j0 < nt; j0 += 64) {
+			const int j = j0 + lane;
+			if (j < nt) {
+				const u32x4 v = *(const u32x4*)(row + j); const u32 s = v.x & 0xffffu;
+				if ((int)v.w != -2 && (int)s >= lo) atomicAdd((int*)(lds + hist + 4u * (s >> 8)), 1);
+			}
+		}
+		__syncthreads();
+		int above_hi = 0, above_lo = 0;
+		const int hb = topk_cut(lds, hist, k, lane, &above_hi);
+		for (int j0 = 0; j0 < nt; j0 += 64) {
+			const int j = j0 + lane;
+			if (j < nt) {
+				const u32x4 v = *(const u32x4*)(row + j); const u32 s = v.x & 0xffffu;
+				if ((int)v.w != -2 && (int)s >= lo && (int)(s >> 8) == hb) atomicAdd((int*)(lds + hist + 1024u + 4u * (s & 255u)), 1);
+			}
+		}
+		__syncthreads();
+		const int lb = topk_cut(lds, hist + 1024u, k - above_hi, lane, &above_lo);
+		const u32 S = ((u32)hb << 8) | (u32)lb;
+		const int take = k - above_hi - above_lo;      /* ties at S that make the k: the first ones in target order */
+		int n = 0, ties = 0;
+		for (int j0 = 0; j0 < nt; j0 += 64) {
+			const int j = j0 + lane;
+			u32 s = 0; bool ok = false, tie = false;
+			if (j < nt) { const u32x4 v = *(const u32x4*)(row + j); s = v.x & 0xffffu; ok = (int)v.w != -2 && (int)s >= lo && s >= S; tie = ok && s == S; }
+			const unsigned long long tb = wave_ballot(tie);
+			if (tie && ties + __builtin_popcountll(tb & below) >= take) ok = false;
+			ties += __builtin_popcountll(tb);
+			const unsigned long long bal = wave_ballot(ok);
+			if (ok) topk_st(lds, (u32)(cnt + n + __builtin_popcountll(bal & below)), topk_key(s, a.tfirst + j, TOPK_CHUNK));
+			n += __builtin_popcountll(bal);
+		}
+		m = n;      /* == k */
+	}
+
+	/* 3. the old list in front, sort, write back the first min(k, total) ranks */
+	const int tot = cnt + m;
+	int P = 2;
+	while (P < tot) P <<= 1;
+	for (int r = lane; r < cnt; r += 64) topk_st(lds, (u32)r, topk_key(lh[r].score1, lt[r], (u32)r));
+	for (int r = tot + lane; r < P; r += 64) topk_st(lds, (u32)r, 0ull);
+	__syncthreads();
+	for (int size = 2; size <= P; size <<= 1)
+		for (int stride = size >> 1; stride > 0; stride >>= 1) {
+			for (int i = lane; i < P / 2; i += 64) {
+				const int i0 = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), i1 = i0 + stride;
+				const unsigned long long x = topk_ld(lds, (u32)i0), y = topk_ld(lds, (u32)i1);
+				if ((x < y) == ((i0 & size) == 0)) { topk_st(lds, (u32)i0, y); topk_st(lds, (u32)i1, x); }
+			}
+			__syncthreads();
+		}
+	const int ncnt = tot < k ? tot : k;
+	for (int b = (ncnt - 1) / 64; b >= 0; --b) {
+		const int r = 64 * b + lane;
+		u32x4 rec = { 0u, 0u, 0u, 0u }; int t = 0;
+		if (r < ncnt) {
+			const unsigned long long key = topk_ld(lds, (u32)r);
+			const u32 src = (u32)key & 0xffffu;
+			t = (int)~(u32)(key >> 16);
+			rec = src == TOPK_CHUNK ? *(const u32x4*)(row + (t - a.tfirst)) : *(const u32x4*)(lh + src);
+		}
+		__syncthreads();      /* every source of this block read before any of its slots is written */
+		if (r < ncnt) { lt[r] = t; *(u32x4*)(lh + r) = rec; }
+	}
+	if (lane == 0) {
+		a.state[2 * (int64_t)q] = ncnt;
+		a.state[2 * (int64_t)q + 1] = ncnt == k ? (int)(topk_ld(lds, (u32)(k - 1)) >> 48) : 0;
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------
  * k_selftest: (a) the cross-lane primitives applied to the lane id, so that tests can pin the DPP semantics the
  * chains rely on (and that the CPU emulator assumes) on real hardware; (b) a packed-int16 VALU issue-rate probe
  * (8 independent v_pk_add_i16/v_pk_max_i16/v_pk_sub_u16 chains) whose measured rate is the roofline's "peak".
@@ -4024,6 +4177,15 @@ extern "C" int ssw_shim_launch_select(const ssw_select_args* a, void* stream)
 	const int grid = args.pass == 1 ? 1 : (int)((n + 255) / 256);
 	if (grid <= 0) return 0;
 	SSW_LAUNCH(k_select, ssw_select_args, args, grid, 256, 1024, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream)
+{
+	ssw_topk_args args = *a;
+	if (args.nq <= 0 || args.nt <= 0) return 0;
+	if (args.k < 1 || args.k > 1024 || args.cap < 64 || args.cap < 2 * args.k || (args.cap & (args.cap - 1)) != 0) return -2;
+	SSW_LAUNCH(k_topk, ssw_topk_args, args, args.nq, 64, 8 * (size_t)args.cap + 2048, stream);
 	return SSW_LAUNCH_OK();
 }
 

@@ -40,6 +40,8 @@ typedef struct {
 	ssw_gpu_result* results;
 	block_cigars* cig;           /* per block */
 	int want_cigars;
+	int32_t topk, min_score;     /* topk > 0: ssw_gpu_search_topk per block, rows of topk slots (tidx + results) */
+	int32_t* tidx;
 	int32_t next;                /* the queue: next block index (atomic) */
 	int failed;                  /* first failure stops the hand-out (atomic) */
 	pthread_mutex_t err_lock;
@@ -60,8 +62,12 @@ static void* pool_thread(void* argp)
 		ssw_gpu_seqs* Q = ssw_gpu_seqs_upload(w->ctx, k->qcodes, k->qoff + q0, cnt);   /* offsets are taken relative to their first entry */
 		int rc = Q ? 0 : -1;
 		if (Q) {
-			rc = ssw_gpu_align_batch(w->ctx, Q, w->targets, k->tfirst, k->tcount, k->prm, k->results + (int64_t)q0 * k->tcount,
-			                         k->want_cigars ? &k->cig[b].words : 0, k->want_cigars ? &k->cig[b].n : 0);
+			if (k->topk > 0)
+				rc = ssw_gpu_search_topk(w->ctx, Q, w->targets, k->prm, k->topk, k->min_score, 0, k->tidx + (int64_t)q0 * k->topk,
+				                         k->results + (int64_t)q0 * k->topk, k->want_cigars ? &k->cig[b].words : 0, k->want_cigars ? &k->cig[b].n : 0);
+			else
+				rc = ssw_gpu_align_batch(w->ctx, Q, w->targets, k->tfirst, k->tcount, k->prm, k->results + (int64_t)q0 * k->tcount,
+				                         k->want_cigars ? &k->cig[b].words : 0, k->want_cigars ? &k->cig[b].n : 0);
 			ssw_gpu_seqs_free(Q);
 		}
 		if (rc) {
@@ -145,6 +151,10 @@ int ssw_gpu_pool_stats(const ssw_gpu_pool* p, int worker, ssw_gpu_pool_stat* out
 	return 0;
 }
 
+/* the queue of one call: blocks of `block` queries over the workers, then one CIGAR pool in block order.  Rows of `width` records
+   (target_count, or k of a top-K search) */
+static int pool_run(ssw_gpu_pool* p, pool_call* kk, int32_t block, int32_t width, uint32_t** cigar_pool, int64_t* cigar_words);
+
 int ssw_gpu_pool_align(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int32_t block,
                        int32_t target_first, int32_t target_count, const ssw_gpu_params* prm,
                        ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
@@ -157,14 +167,40 @@ int ssw_gpu_pool_align(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qof
 	if (target_first < 0 || target_count < 0 || target_first + target_count > p->tcount) { snprintf(p->err, sizeof p->err, "pool_align: target range out of bounds"); return -1; }
 	for (int i = 0; i < p->n; ++i) { const int dev = p->w[i].st.device; memset(&p->w[i].st, 0, sizeof p->w[i].st); p->w[i].st.device = dev; }
 	if (nq == 0 || target_count == 0) return 0;
+	pool_call k; memset(&k, 0, sizeof k);
+	k.qcodes = qcodes; k.qoff = qoffsets; k.nq = nq; k.tfirst = target_first; k.tcount = target_count; k.prm = prm; k.results = results;
+	return pool_run(p, &k, block, target_count, cigar_pool, cigar_words);
+}
+
+int ssw_gpu_pool_search_topk(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int32_t block,
+                             const ssw_gpu_params* prm, int32_t k, int32_t min_score, int32_t* tidx, ssw_gpu_result* results,
+                             uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!p) return -1;
+	if (!qoffsets || nq < 0 || !prm || !prm->mat || !tidx || !results) { snprintf(p->err, sizeof p->err, "pool_search_topk: bad arguments"); return -1; }
+	if (k < 1 || k > SSW_GPU_TOPK_MAX) { snprintf(p->err, sizeof p->err, "pool_search_topk: k must be 1 .. SSW_GPU_TOPK_MAX"); return -1; }
+	if (!p->w[0].targets) { snprintf(p->err, sizeof p->err, "pool_search_topk: no target set (ssw_gpu_pool_set_targets)"); return -1; }
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	for (int i = 0; i < p->n; ++i) { const int dev = p->w[i].st.device; memset(&p->w[i].st, 0, sizeof p->w[i].st); p->w[i].st.device = dev; }
+	if (nq == 0) return 0;
+	pool_call c; memset(&c, 0, sizeof c);
+	c.qcodes = qcodes; c.qoff = qoffsets; c.nq = nq; c.tfirst = 0; c.tcount = p->tcount; c.prm = prm; c.results = results;
+	c.topk = k; c.min_score = min_score; c.tidx = tidx;
+	return pool_run(p, &c, block, k, cigar_pool, cigar_words);
+}
+
+static int pool_run(ssw_gpu_pool* p, pool_call* kk, int32_t block, int32_t width, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	pool_call k = *kk;
+	const int32_t nq = k.nq;
+	ssw_gpu_result* results = k.results;
 	if (block < 1) {      /* a few blocks per worker: the tail is one block, the upload of a block hides behind the others' compute */
 		block = (nq + 4 * p->n - 1) / (4 * p->n);
 		if (block < 256) block = 256;
 	}
 	if (block > nq) block = nq;
-	pool_call k; memset(&k, 0, sizeof k);
-	k.pool = p; k.qcodes = qcodes; k.qoff = qoffsets; k.nq = nq; k.block = block; k.nblocks = (nq + block - 1) / block;
-	k.tfirst = target_first; k.tcount = target_count; k.prm = prm; k.results = results;
+	k.pool = p; k.block = block; k.nblocks = (nq + block - 1) / block;
 	k.want_cigars = cigar_pool != 0;
 	k.cig = (block_cigars*)calloc((size_t)k.nblocks, sizeof(block_cigars));
 	pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)p->n);
@@ -192,8 +228,8 @@ int ssw_gpu_pool_align(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qof
 				if (k.cig[b].n > 0) {
 					memcpy(all + base, k.cig[b].words, sizeof(uint32_t) * (size_t)k.cig[b].n);
 					const int32_t q0 = b * block, cnt = nq - q0 < block ? nq - q0 : block;
-					ssw_gpu_result* r = results + (int64_t)q0 * target_count;
-					if (base > 0) for (int64_t i = 0; i < (int64_t)cnt * target_count; ++i) if (r[i].cigar_off >= 0) r[i].cigar_off += base;
+					ssw_gpu_result* r = results + (int64_t)q0 * width;
+					if (base > 0) for (int64_t i = 0; i < (int64_t)cnt * width; ++i) if (r[i].cigar_off >= 0) r[i].cigar_off += base;
 				}
 				base += k.cig[b].n;
 			}

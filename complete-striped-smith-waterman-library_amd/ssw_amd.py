@@ -109,6 +109,14 @@ def load(path=None):
         L.ssw_gpu_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params),
                                           C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_pairs.restype = C.c_int
+    if hasattr(L, "ssw_gpu_search_topk"):
+        L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_search_topk.restype = C.c_int
+    if hasattr(L, "ssw_gpu_pool_search_topk"):
+        L.ssw_gpu_pool_search_topk.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_pool_search_topk.restype = C.c_int
     L.ssw_gpu_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ssw_gpu_last_timing.restype = C.c_int
     L.ssw_gpu_last_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -339,6 +347,30 @@ class Context(object):
             raise RuntimeError("ssw_gpu_search_db: " + self.error())
         return whole if on_chunk is None else rc
 
+    def search_topk(self, queries, targets, k, mat, n, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2,
+                    mark_mismatch=False, min_score=1, chunk=0, want_cigar=True, out=None):
+        """best k targets per query (ssw_gpu_search_topk): -> (tidx int32 [nq, k], records [nq, k] of RESULT_DTYPE, uint32 CIGAR pool
+        in (q, r) order).  Slots past a query's last eligible target hold -1 / the empty record.  `out`: (tidx, records) to fill."""
+        nq = queries.count
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            ti = np.zeros((nq, max(int(k), 0)), dtype=np.int32)
+            res = np.zeros((nq, max(int(k), 0)), dtype=RESULT_DTYPE)
+        else:
+            ti, res = out
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_search_topk(self.h, queries.h, targets.h, C.byref(p), int(k), int(min_score), int(chunk),
+                                          ti.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                          C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_search_topk: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        return ti, res, cig
+
     def result_array(self, nq, nt):
         """[nq, nt] result records in page-locked host memory (freed with the context)"""
         nbytes = int(nq) * int(nt) * RESULT_DTYPE.itemsize
@@ -427,6 +459,27 @@ class Pool(object):
         if want_cigar and pool:
             C.CDLL(None).free(pool)
         return res, cig
+
+    def search_topk(self, reads, k, mat, n, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2,
+                    mark_mismatch=False, min_score=1, block=0, want_cigar=True, packed=None):
+        """best k of the pool's targets per read (ssw_gpu_pool_search_topk) -> (tidx [nq, k], records [nq, k], CIGAR pool)"""
+        codes, off = packed if packed is not None else _pack(reads)
+        nq = len(off) - 1
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        ti = np.zeros((nq, max(int(k), 0)), dtype=np.int32)
+        res = np.zeros((nq, max(int(k), 0)), dtype=RESULT_DTYPE)
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_pool_search_topk(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), nq, block, C.byref(p),
+                                               int(k), int(min_score), ti.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                               C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_pool_search_topk: " + self.error())
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        return ti, res, cig
 
     def stats(self):
         out = []

@@ -69,7 +69,7 @@ typedef struct {
 	int64_t fill_launches; /* (database search: launch groups -- all size classes of one chunk of targets, side by side on several streams) */
 	int64_t fill_cells;    /* DP cells actually evaluated by the fill kernel (padding + halo included) */
 	int64_t cells;         /* sum of readLen*refLen over the batch (the GCUPS numerator) */
-	double reduce_ms;      /* score1/score2/end-position reduction */
+	double reduce_ms;      /* score1/score2/end-position reduction (ssw_gpu_search_topk: the device time of the k_topk selection) */
 	double locate_ms;      /* read_end1 + reverse (begin position) passes */
 	double trace_ms;       /* banded traceback + CIGAR re-score */
 	int64_t n_word;        /* alignments decided under 16-bit semantics */
@@ -181,6 +181,28 @@ int ssw_gpu_search_db(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_g
                       int32_t targets_per_chunk, ssw_gpu_hits_fn fn, void* user);
 
 /*
+ * Database search, best k targets per query -- the reference's loop (src/main.c:462-526) kept to its best hits, without shipping the
+ * nq x nt matrix to the host.  Target t of the whole set is ELIGIBLE for query q when its ssw_gpu_align_batch record has status 0,
+ * score1 > 0 and score1 >= min_score.
+ *   tidx[q * k + r]     the r-th eligible target of query q, ordered by score1 descending, then target index ascending; -1 past the last;
+ *   results[q * k + r]  bit for bit the ssw_gpu_align_batch(ctx, queries, targets, t, 1, params, ...) record at row q (the caller's flag,
+ *                       filters, filterd, maskLen, score_size, mark_mismatch); padding slots hold the record of an empty target (zeros,
+ *                       ref_begin1 = read_begin1 = -1, cigar_off = -1);
+ *   cigar_pool          (optional, malloc()ed, caller frees) the CIGARs in (q, r) order.
+ * targets_per_chunk: 0 = 2048, as ssw_gpu_search_db (the answer does not depend on it).  k outside 1..SSW_GPU_TOPK_MAX, a NULL tidx /
+ * results / params or sequences of another context return -1 with a message before anything is launched or written; nq == 0 returns 0;
+ * nt == 0 fills every slot with padding.  Every phase stays within ssw_gpu_get_budget(ctx).
+ * Inside the fused database search's envelope (queries up to 640 residues, n <= 32, max(mat) <= 49, gapO > gapE) the selection runs on the
+ * device (k_topk, one launch per chunk of targets, beside the next chunk's fill), and the lists come to the host once; elsewhere the chunks'
+ * full records are selected on the host -- exact, slower.  With flag != 0 the selected pairs then go through the ssw_gpu_align_pairs path.
+ * ssw_gpu_last_timing: reduce_ms is the device time of the k_topk selection launches (the other fields as for the search and the pairs).
+ */
+#define SSW_GPU_TOPK_MAX 1024
+int ssw_gpu_search_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                        const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t targets_per_chunk,
+                        int32_t* tidx, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
  * Threads.  A context owns one stream set and its workspaces: ONE call at a time per context (a second thread entering
  * ssw_gpu_align_batch on a busy context gets an error, not a race).  Different contexts -- on the same or on different
  * devices -- are independent and may be driven from different threads concurrently.  The single-pair functions of ssw.h
@@ -211,6 +233,12 @@ int ssw_gpu_pool_set_targets(ssw_gpu_pool* pool, const int8_t* codes, const int6
 int ssw_gpu_pool_align(ssw_gpu_pool* pool, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int32_t block,
                        int32_t target_first, int32_t target_count, const ssw_gpu_params* params,
                        ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
+/* ssw_gpu_search_topk over the pool's target set: blocks of `block` queries (0: a few per worker) go to whichever worker is free, rows
+   tidx[q * k ..] / results[q * k ..] land in place, CIGAR offsets are rebased into one pool in block order -- the same output as one
+   context's ssw_gpu_search_topk over all queries (targets_per_chunk: the default) */
+int ssw_gpu_pool_search_topk(ssw_gpu_pool* pool, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int32_t block,
+                             const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t* tidx, ssw_gpu_result* results,
+                             uint32_t** cigar_pool, int64_t* cigar_words);
 /* per worker, accumulated over the last ssw_gpu_pool_align: blocks taken, DP cells (readLen x refLen), device milliseconds */
 typedef struct { int32_t device; int64_t blocks; int64_t queries; int64_t cells; double busy_ms; } ssw_gpu_pool_stat;
 int ssw_gpu_pool_stats(const ssw_gpu_pool* pool, int worker, ssw_gpu_pool_stat* out);

@@ -174,6 +174,52 @@ class BatchAligner {
     free(pool);
   }
 
+  // A database search kept to its best hits (ssw_gpu_search_topk): (*hits)[i] holds, in rank order (sw_score descending, then reference
+  // index ascending), up to k references of the set whose alignment with queries[i] scores > 0 and >= min_score -- each with the Alignment
+  // and flag that AlignPairs gives for that pair.  maskLen < 15 is raised to 15 like there.
+  struct TopKHit {
+    int32_t target;
+    Alignment alignment;
+    uint16_t flag;
+  };
+  void SearchTopK(const std::vector<std::string>& queries, int32_t k, const Filter& filter, std::vector<std::vector<TopKHit> >* hits,
+                  int32_t maskLen, int32_t min_score = 1) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::SearchTopK: no reference sequences");
+    if (k < 1 || k > SSW_GPU_TOPK_MAX) throw std::runtime_error("BatchAligner::SearchTopK: k must be 1 .. SSW_GPU_TOPK_MAX");
+    const int32_t nq = (int32_t)queries.size();
+    hits->assign(queries.size(), std::vector<TopKHit>());
+    if (nq == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0);
+    for (int32_t i = 0; i < nq; ++i) { text += queries[i]; off.push_back((int64_t)text.size()); }
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nq, table_.data());
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<int32_t> tidx((size_t)nq * (size_t)k);
+    std::vector<ssw_gpu_result> res((size_t)nq * (size_t)k);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_search_topk(ctx_, Q, targets_, &p, k, min_score, 0, tidx.data(), res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_search_topk: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t i = 0; i < nq; ++i)
+      for (int32_t r = 0; r < k; ++r) {
+        const size_t s = (size_t)i * (size_t)k + (size_t)r;
+        if (tidx[s] < 0) break;
+        const ssw_gpu_result& g = res[s];
+        TopKHit h;
+        h.target = tidx[s]; h.flag = g.flag;
+        Alignment& a = h.alignment;
+        a.sw_score = g.score1; a.sw_score_next_best = g.score2; a.ref_begin = g.ref_begin1; a.ref_end = g.ref_end1;
+        a.query_begin = g.read_begin1; a.query_end = g.read_end1; a.ref_end_next_best = g.ref_end2;
+        Expand(a, g.cigarLen > 0 ? pool + g.cigar_off : 0, g.cigarLen, ref_codes_.data() + ref_off_[(size_t)tidx[s]], text.data() + off[(size_t)i],
+               (int)queries[(size_t)i].size());
+        (*hits)[(size_t)i].push_back(h);
+      }
+    free(pool);
+  }
+
  private:
   // soft clips, '=' / 'X' runs and the mismatch count of one alignment: the outcome of the reference's ConvertAlignment +
   // CalculateNumberMismatch (ssw_cpp.cpp:52-89, 123-199).  Like there, the clips are written even when ssw_align returned no CIGAR
