@@ -44,11 +44,20 @@ typedef struct {
    CIGARs: the survivors of the score filter, reference src/main.c:493-506 with flag != 0): the "query index" of a job is then a
    virtual id -- the position of the pair in a compact survivor list.  Records, CIGAR slots and resume state are indexed by the
    virtual id, the sequences are reached through the two maps.  vq == NULL: plain query indices, the args' own `tgt`. */
+/* a window of a resident target set (ssw_gpu_align_windows): columns [start, start + len) of the concatenated target codes.  The start is
+   a 64-bit absolute offset -- any byte address, above 2^31 too; column indices inside the kernels stay relative to it */
+typedef struct {
+	int64_t start;
+	int32_t len;
+	int32_t pad;
+} ssw_win;
+
 typedef struct {
 	const int32_t* vq;       /* virtual id -> query index */
-	const int32_t* vt;       /* virtual id -> target index */
+	const int32_t* vt;       /* virtual id -> target index (win set: -> window index) */
 	const int8_t* tcodes;    /* all target codes */
 	const int64_t* toff;     /* target offsets */
+	const ssw_win* win;      /* optional: the window table; the job's target is then window vt[v] of tcodes instead of target vt[v] */
 } ssw_vmap;
 
 /* forward fill: column maxima of every (pair, tile) of one target */
@@ -336,7 +345,7 @@ typedef struct {
    every register; both queries have the same row class R = ceil(len / 16) */
 typedef struct {
 	int32_t qa, qb;          /* query of the low / high half; qb = -1: the high half is idle */
-	int32_t ta, tb;          /* target of the low / high half (tb = ta when qb = -1) */
+	int32_t ta, tb;          /* target of the low / high half (tb = ta when qb = -1); windows of ssw_fillpairs_args.win when that is set */
 } ssw_pjob;
 
 typedef struct {
@@ -359,7 +368,18 @@ typedef struct {
 	int32_t form;            /* 1: column frame (fr_base / fr_kmask), 0: plain int16 */
 	int32_t fr_base, fr_kmask;
 	int32_t mark_word;       /* records decided under 16-bit rules carry SSW_OUT_WORD in their status (the host reads and clears it) */
+	const ssw_win* win;      /* optional (ssw_gpu_align_windows): ta / tb index this window table instead of toff */
 } ssw_fillpairs_args;
+
+/* the window table of ssw_gpu_align_windows, built on the device from the caller's three arrays: win[i] = { toff[tidx[i]] + tbeg[i], tlen[i] } */
+typedef struct {
+	const int32_t* tidx;
+	const int64_t* tbeg;
+	const int32_t* tlen;
+	const int64_t* toff;     /* offsets of the resident target set */
+	ssw_win* win;            /* count entries */
+	int64_t count;
+} ssw_wintab_args;
 
 /* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
 typedef struct {
@@ -369,6 +389,7 @@ typedef struct {
 	const int64_t* dst_off;  /* count + 1 */
 	int8_t* dst;
 	int32_t count;
+	const int64_t* src_beg;  /* optional: slot i starts src_beg[i] residues into sequence idx[i] (windows of ssw_gpu_align_windows outside the fused kernel) */
 } ssw_seqgather_args;
 
 /* Top-K selection of the database search (ssw_gpu_search_topk): one launch per streamed chunk merges the chunk's compact records
@@ -454,6 +475,7 @@ int ssw_shim_launch_select(const ssw_select_args* a, void* stream);   /* the pas
 int ssw_shim_launch_mark(const ssw_mark_args* a, void* stream);
 int ssw_shim_launch_prep(const ssw_prep_args* a, void* stream);
 int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream);
+int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream);
 int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefront per query */
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 

@@ -95,7 +95,7 @@ struct ssw_gpu_ctx {
 	char err[512];
 	pthread_mutex_t mu;                 /* guards the lazily created streams and the error text: ONE other thread may upload sequences while a batch call runs */
 	ssw_gpu_timing tm;
-	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab;
+	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab, wtab;
 	dbuf sres, svq, svt, scnt;          /* flagged database search: survivor records, their (query, target) maps, counters */
 	dbuf scratch0, need0, list0;        /* traceback: round 0 of the narrow alignments while the wide ones' teams already run (trace_phase "early") */
 	dbuf tk_hits0, tk_hits1, tk_lst;    /* top-K search: the two chunk record buffers, the per-query lists + their state */
@@ -325,7 +325,7 @@ void ssw_gpu_close(ssw_gpu_ctx* c)
 	if (c->stream) ssw_shim_stream_sync(c->stream);
 	for (int i = 0; i < 2; ++i) { ssw_shim_free(c->hits_d[i]); ssw_shim_host_free(c->hits_h[i]); }
 	dbuf_free(&c->mat); dbuf_free(&c->pairs); dbuf_free(&c->qlist); dbuf_free(&c->res); dbuf_free(&c->cm16);
-	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab);
+	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab); dbuf_free(&c->wtab);
 	dbuf_free(&c->sres); dbuf_free(&c->svq); dbuf_free(&c->svt); dbuf_free(&c->scnt);
 	dbuf_free(&c->scratch0); dbuf_free(&c->need0); dbuf_free(&c->list0);
 	dbuf_free(&c->tk_hits0); dbuf_free(&c->tk_hits1); dbuf_free(&c->tk_lst);
@@ -1448,7 +1448,7 @@ static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const
 			dx->hvt = (int32_t*)malloc(sizeof(int32_t) * dx->hcap); dx->hpo = (int64_t*)malloc(sizeof(int64_t) * dx->hcap);
 			if (!dx->hs || !dx->hvq || !dx->hvt || !dx->hpo) { dx->hcap = 0; fail(c, "out of host memory%s", ""); goto out; }
 		}
-		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off;
+		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off; vm.win = 0;
 		/* ---- reverse pass (begin positions), one launch per geometry bucket that has survivors; read_end1 came with the search */
 		win_in wi; memset(&wi, 0, sizeof wi);
 		wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = dx->maxt; wi.d_mat = d_mat; wi.n = prm->n; wi.maxmat = dx->maxmat; wi.minmat = dx->minmat;
@@ -1717,8 +1717,9 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		for (int32_t ti = 0; ti < tcount; ++ti) { int64_t L = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti]; if (L > maxt) maxt = L; }
 		/* (k_filldb takes the column maximum of two rows with a 16-bit float max3, valid below 31744: 640 rows x max(mat) <= 49) */
 		/* flagged batches (begin positions / CIGARs) against several targets: the same fused search + one batched reverse pass and traceback
-		   over the pairs that pass the score filter (dbx_chunk); the survivors' window kernels read from the concatenated targets with 32-bit
-		   column indices, so the target set stays below 2^31 residues here */
+		   over the pairs that pass the score filter (dbx_chunk).  The bound on the target set dates from the window kernels' 32-bit column
+		   indices into the concatenated targets; they take a 64-bit base per job now (the pair lists run above 2^31 residues), but this path has
+		   not been run there, so the bound stays */
 		const int use_dbx = prm->flag != 0 && !ds && !c->kn.no_dbx && tcount >= 4 && T->total < 0x7fff0000;
 		const int db_ok = !literal && (prm->flag == 0 || use_dbx) && any_short && maxt <= 65000 && maxmat <= 49 && !c->kn.no_db;
 		dbx_state dxs; memset(&dxs, 0, sizeof dxs);
@@ -2381,14 +2382,22 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 /* ------------------------------------------------------------------------------------------------
  * Explicit pair lists (ssw_gpu_align_pairs): results[i] = the record of (query qidx[i], target tidx[i]) -- a mapper's
  * "for each read: Align(read, its window)" loop as one call.
- *   envelope (flag 0, gapO > gapE, n <= 32, max(mat) <= 49, queries 1..640 residues, targets 1..65000 columns -- the fused
+ *   envelope (gapO > gapE, n <= 32, max(mat) <= 49, queries 1..640 residues, targets 1..65000 columns -- the fused
  *   database search's gates): k_fillpairs, jobs of two pairs that share the row class R = ceil(len / 16), one chain per job,
  *   final records in one launch per R (and per chunk of the scratch budget).  Planning is a counting sort by (R, target-length
  *   class): O(npairs), no comparison sort.
- *   everything else (flag != 0, empty sequences, longer sequences, gapO <= gapE, wide alphabets, large scores): one internal
+ *   flag != 0: the pairs that pass the score gate then go through one batched reverse pass and traceback (pairs_flagged);
+ *   everything else (empty sequences, longer sequences, gapO <= gapE, wide alphabets, large scores): one internal
  *   batch per distinct target over the subset of its queries, gathered into a temporary set on the device (k_seqgather) --
  *   exact, and slow: a batch call per target.
  * ------------------------------------------------------------------------------------------------ */
+/* where the target of pair i comes from: the whole target tidx[i] (ssw_gpu_align_pairs: tbeg NULL), or its columns [tbeg[i], tbeg[i] +
+   tlen[i]) (ssw_gpu_align_windows).  The kernels name a pair's target by ps_tid: the target index, or -- windows -- the pair's own entry of
+   the device window table d_win. */
+typedef struct { const int32_t* tidx; const int64_t* tbeg; const int32_t* tlen; const ssw_win* d_win; const char* who; } pair_src;
+static inline int64_t ps_tlen(const pair_src* s, const ssw_gpu_seqs* T, int64_t i) { return s->tbeg ? (int64_t)s->tlen[i] : T->h_off[s->tidx[i] + 1] - T->h_off[s->tidx[i]]; }
+static inline int32_t ps_tid(const pair_src* s, int64_t i) { return s->tbeg ? (int32_t)i : s->tidx[i]; }
+
 #define PJ_TCLS 2048      /* target-length classes of the planner: 32 columns each (65000 columns: 2031 classes) */
 
 static double wall_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
@@ -2397,7 +2406,7 @@ static void timing_add(ssw_gpu_timing* acc, const ssw_gpu_timing* t, int64_t* be
 {
 	acc->fill_ms += t->fill_ms; acc->fill_launches += t->fill_launches; acc->fill_cells += t->fill_cells; acc->cells += t->cells;
 	acc->reduce_ms += t->reduce_ms; acc->locate_ms += t->locate_ms; acc->trace_ms += t->trace_ms; acc->n_word += t->n_word; acc->n_byte += t->n_byte;
-	acc->db_repeats += t->db_repeats; acc->fill_pipelined += t->fill_pipelined;
+	acc->db_repeats += t->db_repeats; acc->fill_pipelined += t->fill_pipelined; acc->win_copied += t->win_copied;
 	if (t->fill_cells > *best_cells) {
 		*best_cells = t->fill_cells;
 		memcpy(acc->fill_kernel, t->fill_kernel, sizeof acc->fill_kernel);
@@ -2452,7 +2461,7 @@ static int pairs_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_s
 		ssw_gpu_seqs* G = seqs_new(c, goff, (int32_t)cnt);
 		if (!G) goto out;
 		int32_t* d_idx = (int32_t*)ssw_shim_malloc(sizeof(int32_t) * (size_t)cnt);
-		ssw_seqgather_args ga; ga.src = Q->d_codes; ga.src_off = Q->d_off; ga.idx = d_idx; ga.dst_off = G->d_off; ga.dst = G->d_codes; ga.count = (int32_t)cnt;
+		ssw_seqgather_args ga; ga.src_beg = 0; ga.src = Q->d_codes; ga.src_off = Q->d_off; ga.idx = d_idx; ga.dst_off = G->d_off; ga.dst = G->d_codes; ga.count = (int32_t)cnt;
 		const int ok = d_idx && !ssw_shim_h2d(d_idx, gidx, sizeof(int32_t) * (size_t)cnt, c->stream) &&
 		               !ssw_shim_h2d(G->d_off, G->h_off, sizeof(int64_t) * ((size_t)cnt + 1), c->stream) &&
 		               !ssw_shim_launch_seqgather(&ga, c->stream) && !ssw_shim_stream_sync(c->stream);
@@ -2498,7 +2507,7 @@ out:
    (window_pass) and the traceback (trace_phase, k_mark included) run over it as (query, target) jobs through an ssw_vmap -- the flagged
    database search's phases (dbx_chunk) over a pair list.  rec[0 .. nrec) are the fill's records of the pairs pix[]; they are completed in
    place, CIGARs appended to the staging pool (always, like align_batch does). */
-static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
                          const int64_t* pix, ssw_gpu_result* rec, int64_t nrec, const ssw_gpu_params* prm, const int8_t* d_mat,
                          int32_t maxmat, int32_t minmat, uint32_t** spool, int64_t* swords, int64_t* scap,
                          double* locate_ms, double* trace_ms)
@@ -2529,7 +2538,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		if (o->status != 0 || o->score1 == 0 || (prm->flag == 2 && (int)o->score1 < prm->filters)) continue;      /* ssw.c:900-903, 916 */
 		const int64_t i = pix[k];
 		const int32_t len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]), P16q = (len + 15) / 16 * 16;
-		const int64_t tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		const int64_t tl = ps_tlen(src, T, i);
 		int32_t kk;
 		if (len <= 16 * SSW_RMAX) kk = P16q / 16;
 		else { const int32_t st = (P16q + rows - 1) / rows, Rq = (P16q + xlanes * st - 1) / (xlanes * st); kk = st == 1 ? SSW_RMAX + 1 + Rq : SSW_RMAX + 64 + P16q / 16; }
@@ -2541,7 +2550,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		++ns;
 	}
 	if (ns == 0) { rc = 0; goto out; }
-	if (ns > 0x7fffff00) { fail(c, "align_pairs: %s", "more than 2^31 flagged pairs in one call"); goto out; }
+	if (ns > 0x7fffff00) { fail(c, "%s: more than 2^31 flagged pairs in one call", src->who); goto out; }
 	for (int b = 0; b < NKEY; ++b) kfirst[b + 1] += kfirst[b];
 	{
 		int64_t pos[SSW_RMAX + 64 + 41];
@@ -2557,7 +2566,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		memset(r, 0, sizeof *r);
 		r->score1 = o->score1; r->score2 = o->score2; r->ref_begin1 = -1; r->ref_end1 = o->ref_end1; r->read_begin1 = -1; r->read_end1 = o->read_end1;
 		r->ref_end2 = o->ref_end2; r->word = (key[k] >> 30) & 1; r->want_begin = 1; r->loc_done = 1;      /* (as k_select writes them) */
-		hvq[v] = qidx[i]; hvt[v] = tidx[i]; hvq[2 * ns + v] = (int32_t)v;
+		hvq[v] = qidx[i]; hvt[v] = ps_tid(src, i); hvq[2 * ns + v] = (int32_t)v;
 	}
 	{
 		ssw_dres* d_sres = (ssw_dres*)ensure(c, &c->sres, sizeof(ssw_dres) * (size_t)ns);
@@ -2568,7 +2577,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		if (ssw_shim_h2d(d_sres, hs, sizeof(ssw_dres) * (size_t)ns, c->stream) || ssw_shim_h2d(d_maps, hvq, sizeof(int32_t) * 3 * (size_t)ns, c->stream)) {
 			fail(c, "upload failed: %s", ssw_shim_last_error()); goto out;
 		}
-		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off;
+		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off; vm.win = src->d_win;
 		win_in wi; memset(&wi, 0, sizeof wi);
 		wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = (int32_t)maxt; wi.d_mat = d_mat; wi.n = n; wi.maxmat = maxmat; wi.minmat = minmat;
 		wi.fill_form = c->kn.fill_plain ? 0 : -1; wi.xlanes = xlanes; wi.xrmax = xrmax; wi.xrcap = xrcap;
@@ -2653,19 +2662,16 @@ out:
 	return rc;
 }
 
-static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
-                              int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
+                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
+                            uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells);
+
+/* The pair list of both entry points, arguments checked by the caller: planning, launch loop, flagged phases, fallback and pool assembly.
+   They differ only in where a pair's target starts and how long it is (pair_src). */
+static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src,
+                      int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !results))) return fail(c, "align_pairs: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "align_pairs: sequences belong to another context%s", "");
-	if (prm->n < 1) return fail(c, "align_pairs: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_pairs: score_size must be 0, 1 or 2%s", "");
-	for (int64_t i = 0; i < np; ++i)
-		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
-			char msg[160];
-			snprintf(msg, sizeof msg, "pair %lld: query %d of %d, target %d of %d", (long long)i, qidx[i], Q->count, tidx[i], T->count);
-			return fail(c, "align_pairs: index out of range (%s)", msg);
-		}
+	const int32_t* const tidx = src->tidx;
 	if (cigar_pool) *cigar_pool = 0;
 	if (cigar_words) *cigar_words = 0;
 	memset(&c->tm, 0, sizeof c->tm);
@@ -2678,8 +2684,9 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	for (int64_t i = 0; i < (int64_t)prm->n * prm->n; ++i) { if (prm->mat[i] < minmat) minmat = prm->mat[i]; if (prm->mat[i] > maxmat) maxmat = prm->mat[i]; }
 	const int32_t bias = (prm->score_size == 0 || prm->score_size == 2) ? -minmat : 0;
 	const int32_t n = prm->n;
-	/* (flagged pairs: the window kernels address the concatenated targets with 32-bit column indices, like the flagged database search) */
-	const int kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db && (prm->flag == 0 || T->total < 0x7fff0000);
+	/* (flagged pairs: the window kernels reach a job's target through a 64-bit base and keep their column indices relative to it, so the size
+	   of the resident set does not matter -- unlike the flagged database search's survivors) */
+	const int kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db;
 
 	/* ---- plan: counting sort of the kernel's pairs by (R, target-length class); the rest to the fallback list */
 	const int64_t nkeys = (int64_t)40 * PJ_TCLS;
@@ -2694,7 +2701,7 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	int rc = -1;
 	if (!kcount || !key || !perm) { fail(c, "out of host memory%s", ""); goto done; }
 	for (int64_t i = 0; i < np; ++i) {
-		const int64_t ql = Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]], tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		const int64_t ql = Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]], tl = ps_tlen(src, T, i);
 		const int R = (int)((ql + 15) / 16);
 		if (!kern_ok || ql < 1 || ql > 640 || tl < 1 || tl > 65000 || (int64_t)n * ((R + 3) / 4) * 256 > 65535) { key[i] = 0xffffffffu; ++nfb; continue; }
 		key[i] = (uint32_t)((R - 1) * PJ_TCLS + (tl >> 5 < PJ_TCLS ? tl >> 5 : PJ_TCLS - 1));
@@ -2721,10 +2728,10 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 			for (int64_t k = lo; k < hi; k += 2) {
 				const int64_t pa = perm[k], pb = k + 1 < hi ? perm[k + 1] : -1;
 				ssw_pjob* j = &jobs[nj];
-				j->qa = qidx[pa]; j->ta = tidx[pa];
-				j->qb = pb >= 0 ? qidx[pb] : -1; j->tb = pb >= 0 ? tidx[pb] : tidx[pa];
+				j->qa = qidx[pa]; j->ta = ps_tid(src, pa);
+				j->qb = pb >= 0 ? qidx[pb] : -1; j->tb = ps_tid(src, pb >= 0 ? pb : pa);
 				jix[2 * nj] = pa; jix[2 * nj + 1] = pb;
-				const int64_t L = T->h_off[tidx[pa] + 1] - T->h_off[tidx[pa]], Lb = pb >= 0 ? T->h_off[tidx[pb] + 1] - T->h_off[tidx[pb]] : 0;
+				const int64_t L = ps_tlen(src, T, pa), Lb = pb >= 0 ? ps_tlen(src, T, pb) : 0;
 				if (L > maxt[R - 1]) maxt[R - 1] = L;
 				if (Lb > maxt[R - 1]) maxt[R - 1] = Lb;
 				++nj;
@@ -2744,13 +2751,26 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		ssw_shim_event_record(c->ev_t0, c->stream);
 		if (ssw_shim_h2d(d_mat, prm->mat, (size_t)n * n, c->stream) || ssw_shim_h2d(d_jobs, jobs, sizeof(ssw_pjob) * (size_t)nj, c->stream) ||
 		    ssw_shim_memset(d_cnt, 0, DB_COUNTERS * sizeof(int32_t), c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+		if (src->tbeg) {
+			/* the window table: the caller's three arrays go up as they are (16 bytes per pair), k_wintab adds the resident offsets */
+			unsigned char* d_w = (unsigned char*)ensure(c, &c->wtab, 32 * (size_t)np);
+			if (!d_w) goto done;
+			ssw_wintab_args wa; memset(&wa, 0, sizeof wa);
+			wa.win = (ssw_win*)d_w; wa.tbeg = (const int64_t*)(d_w + 16 * (size_t)np); wa.tidx = (const int32_t*)(d_w + 24 * (size_t)np);
+			wa.tlen = (const int32_t*)(d_w + 28 * (size_t)np); wa.toff = T->d_off; wa.count = np;
+			if (ssw_shim_h2d((void*)wa.tbeg, src->tbeg, 8 * (size_t)np, c->stream) || ssw_shim_h2d((void*)wa.tidx, src->tidx, 4 * (size_t)np, c->stream) ||
+			    ssw_shim_h2d((void*)wa.tlen, src->tlen, 4 * (size_t)np, c->stream) || ssw_shim_launch_wintab(&wa, c->stream)) {
+				fail(c, "window table failed: %s", ssw_shim_last_error()); goto done;
+			}
+			src->d_win = wa.win;
+		}
 		const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
 		int64_t kcells = 0, kbest = 0;
 		for (int R = 1; R <= 40; ++R) {
 			const int64_t j0 = rfirst[R - 1], jn = rfirst[R] - j0;
 			if (jn == 0) continue;
 			const int nch = ssw_shim_fillpairs_nch(R, n);
-			if (nch < 1) { fail(c, "align_pairs: %s", "no k_fillpairs geometry for this alphabet"); goto done; }
+			if (nch < 1) { fail(c, "%s: no k_fillpairs geometry for this alphabet", src->who); goto done; }
 			const int64_t stride = (maxt[R - 1] + 15) / 16 * 16 + 16;
 			/* scratch of a job: its two column-maximum rows + two records; jobs per launch: what half the budget holds, whole workgroups */
 			const int64_t per_job = 8 * stride + 2 * (int64_t)sizeof(ssw_gpu_result);
@@ -2768,7 +2788,7 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 			int64_t rcells = 0;
 			for (int64_t a0 = 0; a0 < jn; a0 += jpl) {
 				ssw_fillpairs_args fa; memset(&fa, 0, sizeof fa);
-				fa.qcodes = Q->d_codes; fa.qoff = Q->d_off; fa.tcodes = T->d_codes; fa.toff = T->d_off; fa.jobs = d_jobs + j0 + a0;
+				fa.qcodes = Q->d_codes; fa.qoff = Q->d_off; fa.tcodes = T->d_codes; fa.toff = T->d_off; fa.win = src->d_win; fa.jobs = d_jobs + j0 + a0;
 				fa.njobs = jn - a0 < jpl ? jn - a0 : jpl; fa.mat = d_mat; fa.n = n; fa.gapO2 = gapO2; fa.gapE2 = gapE2;
 				fa.cm16 = d_cm16; fa.cm8 = d_cm8; fa.cm_stride = stride; fa.maskLen = prm->maskLen; fa.bias = bias; fa.score_size = prm->score_size;
 				fa.out = d_out; fa.counters = d_cnt; fa.form = fr; fa.fr_base = fr_base; fa.fr_kmask = fr_kmask;
@@ -2781,8 +2801,7 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 				if (ssw_shim_d2h(stage + 2 * (j0 + a0), d_out, sizeof(struct ssw_out_rec) * 2 * (size_t)fa.njobs, c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
 				c->tm.fill_launches++;
 				for (int64_t j = j0 + a0; j < j0 + a0 + fa.njobs; ++j) {
-					const ssw_pjob* jb = &jobs[j];
-					const int64_t La = T->h_off[jb->ta + 1] - T->h_off[jb->ta], Lb = jb->qb >= 0 ? T->h_off[jb->tb + 1] - T->h_off[jb->tb] : 0;
+					const int64_t La = ps_tlen(src, T, jix[2 * j]), Lb = jix[2 * j + 1] >= 0 ? ps_tlen(src, T, jix[2 * j + 1]) : 0;
 					rcells += (int64_t)16 * R * 2 * (La > Lb ? La : Lb);
 				}
 			}
@@ -2800,12 +2819,13 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		int64_t nrec = 0;
 		for (int64_t j = 0; j < nj; ++j)
 			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
-		if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, tidx, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
+		if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
 		                                    &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
 		for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
 		timing_add(&acc, &c->tm, &best_cells);
 	}
-	if (nfb > 0 && pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+	if (nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)
+	                          : pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells))) goto done;
 	if (swords > 0) {      /* the pool in pair order (offsets as the caller's pool would have them, also when it asked for none) */
 		uint32_t* pool = cigar_pool ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)swords) : 0;
 		if (cigar_pool && !pool) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto done; }
@@ -2821,13 +2841,31 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		if (cigar_words) *cigar_words = w;
 	}
 	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
-		const int64_t i = perm[k]; acc.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * (T->h_off[tidx[i] + 1] - T->h_off[tidx[i]]); }
+		const int64_t i = perm[k]; acc.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
 	acc.total_ms = wall_ms() - t_start;
 	c->tm = acc;
 	rc = 0;
 done:
 	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(spool);
 	return rc;
+}
+
+static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                              int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !results))) return fail(c, "align_pairs: NULL argument%s", "");
+	if (Q->ctx != c || T->ctx != c) return fail(c, "align_pairs: sequences belong to another context%s", "");
+	if (prm->n < 1) return fail(c, "align_pairs: alphabet size must be >= 1%s", "");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_pairs: score_size must be 0, 1 or 2%s", "");
+	for (int64_t i = 0; i < np; ++i)
+		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
+			char msg[160];
+			snprintf(msg, sizeof msg, "pair %lld: query %d of %d, target %d of %d", (long long)i, qidx[i], Q->count, tidx[i], T->count);
+			return fail(c, "align_pairs: index out of range (%s)", msg);
+		}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.who = "align_pairs";
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words);
 }
 
 int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx, int64_t npairs,
@@ -2840,6 +2878,140 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seq
 		return SSW_GPU_BUSY;
 	}
 	const int rc = align_pairs_locked(c, Q, T, qidx, tidx, npairs, prm, results, cigar_pool, cigar_words);
+	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
+	return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Windows of resident targets (ssw_gpu_align_windows): pair i = query qidx[i] against columns [tbeg[i], tbeg[i] + tlen[i]) of target
+ * tidx[i].  Inside the fused kernel's envelope nothing of the targets is copied: k_wintab turns the caller's three arrays into a device
+ * table of (64-bit start, length), and k_fillpairs, the reverse pass, the traceback and k_mark read every window where it lies.
+ * The windows outside the envelope are gathered on the device into temporary sets (identical windows once; a set holds at most
+ * max(budget / 8, 1 MiB) residues, or one window) and go through the pair path: exact, slow.  win_copied counts their residues.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct { int32_t t, l; int64_t b, i; } wkey;
+static int wkey_cmp(const void* pa, const void* pb)
+{
+	const wkey* a = (const wkey*)pa; const wkey* b = (const wkey*)pb;
+	if (a->t != b->t) return a->t < b->t ? -1 : 1;
+	if (a->b != b->b) return a->b < b->b ? -1 : 1;
+	if (a->l != b->l) return a->l < b->l ? -1 : 1;
+	return a->i < b->i ? -1 : a->i > b->i;
+}
+
+static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
+                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
+                            uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+{
+	wkey* wk = (wkey*)malloc(sizeof(wkey) * (size_t)nl);
+	int32_t* q2 = 0; int32_t* t2 = 0; int32_t* gidx = 0; int64_t* gbeg = 0; int64_t* goff = 0; ssw_gpu_result* tmp = 0;
+	int rc = -1;
+	if (!wk) { fail(c, "out of host memory%s", ""); goto out; }
+	for (int64_t k = 0; k < nl; ++k) { const int64_t i = list[k]; wk[k].t = src->tidx[i]; wk[k].b = src->tbeg[i]; wk[k].l = src->tlen[i]; wk[k].i = i; }
+	qsort(wk, (size_t)nl, sizeof(wkey), wkey_cmp);
+	int64_t lim = (int64_t)(c->cm_budget / 8); if (lim < ((int64_t)1 << 20)) lim = (int64_t)1 << 20;
+	for (int64_t k0 = 0; k0 < nl; ) {
+		/* a chunk: the pairs of consecutive distinct windows whose residues stay within `lim` (one window at the least) */
+		int64_t k1 = k0, nd = 0, sum = 0;
+		while (k1 < nl) {
+			int64_t e = k1 + 1;
+			while (e < nl && wk[e].t == wk[k1].t && wk[e].b == wk[k1].b && wk[e].l == wk[k1].l) ++e;
+			if (nd > 0 && (sum + wk[k1].l > lim || nd >= 0x7fffff00 || e - k0 > 0x7fffff00)) break;
+			sum += wk[k1].l; ++nd; k1 = e;
+		}
+		const int64_t m = k1 - k0;
+		if (m > 0x7fffffff) { fail(c, "align_windows: %s", "more than 2^31 pairs against one window outside the fused kernel's envelope"); goto out; }
+		free(q2); free(gidx); free(gbeg); free(goff); free(tmp);
+		q2 = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)m); t2 = q2 ? q2 + m : 0;
+		gidx = (int32_t*)malloc(sizeof(int32_t) * (size_t)nd); gbeg = (int64_t*)malloc(sizeof(int64_t) * (size_t)nd);
+		goff = (int64_t*)malloc(sizeof(int64_t) * ((size_t)nd + 1)); tmp = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)m);
+		if (!q2 || !gidx || !gbeg || !goff || !tmp) { fail(c, "out of host memory%s", ""); goto out; }
+		int64_t d = -1;
+		goff[0] = 0;
+		for (int64_t k = k0; k < k1; ++k) {
+			if (k == k0 || wk[k].t != wk[k - 1].t || wk[k].b != wk[k - 1].b || wk[k].l != wk[k - 1].l) {
+				++d; gidx[d] = wk[k].t; gbeg[d] = wk[k].b; goff[d + 1] = goff[d] + wk[k].l;
+			}
+			q2[k - k0] = qidx[wk[k].i]; t2[k - k0] = (int32_t)d;
+		}
+		ssw_gpu_seqs* G = seqs_new(c, goff, (int32_t)nd);
+		if (!G) goto out;
+		unsigned char* d_g = (unsigned char*)ssw_shim_malloc(12 * (size_t)nd);
+		ssw_seqgather_args ga; memset(&ga, 0, sizeof ga);
+		ga.src = T->d_codes; ga.src_off = T->d_off; ga.src_beg = (const int64_t*)d_g; ga.idx = (const int32_t*)(d_g + 8 * (size_t)nd);
+		ga.dst_off = G->d_off; ga.dst = G->d_codes; ga.count = (int32_t)nd;
+		const int ok = d_g && !ssw_shim_h2d((void*)ga.src_beg, gbeg, 8 * (size_t)nd, c->stream) && !ssw_shim_h2d((void*)ga.idx, gidx, 4 * (size_t)nd, c->stream) &&
+		               !ssw_shim_h2d(G->d_off, G->h_off, sizeof(int64_t) * ((size_t)nd + 1), c->stream) &&
+		               !ssw_shim_launch_seqgather(&ga, c->stream) && !ssw_shim_stream_sync(c->stream);
+		ssw_shim_free(d_g);
+		if (!ok) { fail(c, "align_windows: window gather failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(G); goto out; }
+		uint32_t* pool = 0; int64_t words = 0;
+		if (align_pairs_locked(c, Q, G, q2, t2, m, prm, tmp, &pool, &words)) { ssw_gpu_seqs_free(G); goto out; }
+		ssw_gpu_seqs_free(G);
+		timing_add(acc, &c->tm, best_cells);
+		acc->win_copied += sum;
+		if (words > 0) {
+			if (*swords + words > *scap) {
+				const int64_t ncap = (*swords + words) * 2 + 1024;
+				uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
+				if (!np2) { free(pool); fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
+				*spool = np2; *scap = ncap;
+			}
+			memcpy(*spool + *swords, pool, sizeof(uint32_t) * (size_t)words);
+		}
+		free(pool);
+		for (int64_t k = 0; k < m; ++k) {
+			ssw_gpu_result r = tmp[k];
+			if (r.cigarLen > 0 && r.cigar_off >= 0) r.cigar_off += *swords;
+			results[wk[k0 + k].i] = r;
+		}
+		*swords += words;
+		k0 = k1;
+	}
+	rc = 0;
+out:
+	free(wk); free(q2); free(gidx); free(gbeg); free(goff); free(tmp);
+	return rc;
+}
+
+static int align_windows_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                                const int64_t* tbeg, const int32_t* tlen, int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results,
+                                uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !tbeg || !tlen || !results))) return fail(c, "align_windows: NULL argument%s", "");
+	if (Q->ctx != c || T->ctx != c) return fail(c, "align_windows: sequences belong to another context%s", "");
+	if (prm->n < 1) return fail(c, "align_windows: alphabet size must be >= 1%s", "");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_windows: score_size must be 0, 1 or 2%s", "");
+	if (np > 0x7fffff00) return fail(c, "align_windows: %s", "more than 2^31 pairs in one call");      /* (a pair's window is named by a 32-bit index) */
+	for (int64_t i = 0; i < np; ++i) {
+		char msg[200];
+		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
+			snprintf(msg, sizeof msg, "pair %lld: query %d of %d, target %d of %d", (long long)i, qidx[i], Q->count, tidx[i], T->count);
+			return fail(c, "align_windows: index out of range (%s)", msg);
+		}
+		const int64_t tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		if (tbeg[i] < 0 || tlen[i] < 0 || tbeg[i] > tl || (int64_t)tlen[i] > tl - tbeg[i]) {      /* no clamping: a window that leaves its target is the caller's bug */
+			snprintf(msg, sizeof msg, "pair %lld: columns [%lld, %lld + %d) of target %d, which has %lld", (long long)i, (long long)tbeg[i], (long long)tbeg[i],
+			         tlen[i], tidx[i], (long long)tl);
+			return fail(c, "align_windows: window out of range (%s)", msg);
+		}
+	}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows";
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words);
+}
+
+int ssw_gpu_align_windows(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                          const int64_t* tbeg, const int32_t* tlen, int64_t npairs, const ssw_gpu_params* prm, ssw_gpu_result* results,
+                          uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows: NULL context%s", "");
+	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return SSW_GPU_BUSY;
+	}
+	const int rc = align_windows_locked(c, Q, T, qidx, tidx, tbeg, tlen, npairs, prm, results, cigar_pool, cigar_words);
 	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
 	return rc;
 }

@@ -37,7 +37,7 @@
 
 /* virtual ids (ssw_vmap, ssw_dev.h): the query whose residues job id `v` uses, and the start of its target */
 SSW_DEV int vm_query(const ssw_vmap& m, int v) { return m.vq ? m.vq[v] : v; }
-SSW_DEV const int8_t* vm_target(const ssw_vmap& m, const int8_t* tgt, int v) { return m.vq ? m.tcodes + m.toff[m.vt[v]] : tgt; }
+SSW_DEV const int8_t* vm_target(const ssw_vmap& m, const int8_t* tgt, int v) { return m.vq ? m.tcodes + (m.win ? m.win[m.vt[v]].start : m.toff[m.vt[v]]) : tgt; }
 
 /* ------------------------------------------------------------------------------------------------
  * LDS map of one chain-group kernel:
@@ -788,6 +788,10 @@ SSW_DEV void pj_rows(const unsigned char* lds, u32 pa_next, u32 pb_next, u32x4 (
 	}
 }
 
+/* start (in tcodes) and column count of target / window t of a k_fillpairs launch */
+SSW_DEV int64_t pj_tstart(const ssw_fillpairs_args& a, int t) { return a.win ? a.win[t].start : a.toff[t]; }
+SSW_DEV int pj_tcols(const ssw_fillpairs_args& a, int t) { return a.win ? a.win[t].len : (int)(a.toff[t + 1] - a.toff[t]); }
+
 template <int R, bool FR, int UNROLL>
 SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
 {
@@ -809,10 +813,12 @@ SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
 	build_profile<R, FR ? 3 : 0>(lds, pbase, l16, 16, a.mat, a.n, a.qcodes + a.qoff[jb.qa], lena, 0,
 	                             jb.qb >= 0 ? a.qcodes + a.qoff[jb.qb] : (const int8_t*)0, lenb, 0x7fffffff, 0x7fffffff, gapEi);
 
-	const int8_t* tga = a.tcodes + a.toff[jb.ta];
-	const int8_t* tgb = jb.qb >= 0 ? a.tcodes + a.toff[jb.tb] : tga;
-	const int ncola = active ? (int)(a.toff[jb.ta + 1] - a.toff[jb.ta]) : 0;
-	const int ncolb = active && jb.qb >= 0 ? (int)(a.toff[jb.tb + 1] - a.toff[jb.tb]) : 0;
+	/* (a.win: the halves' targets are windows of the resident set -- any byte address; the loads below are bytewise and stop at the half's
+	   own column count, so a window's neighbours in its chromosome never enter the rings) */
+	const int8_t* tga = a.tcodes + pj_tstart(a, jb.ta);
+	const int8_t* tgb = jb.qb >= 0 ? a.tcodes + pj_tstart(a, jb.tb) : tga;
+	const int ncola = active ? pj_tcols(a, jb.ta) : 0;
+	const int ncolb = active && jb.qb >= 0 ? pj_tcols(a, jb.tb) : 0;
 	const int ncols = ncola > ncolb ? ncola : ncolb;      /* columns whose maxima this chain keeps (both halves stand in the same column) */
 	uint32_t* o16 = a.cm16 + (active ? job : 0) * a.cm_stride;
 	uint32_t* o8 = a.cm8 + (active ? job : 0) * a.cm_stride;
@@ -822,8 +828,8 @@ SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
 		const int64_t jj = (int64_t)blockIdx.x * nch + k;
 		if (jj >= a.njobs) break;
 		const ssw_pjob o = a.jobs[jj];
-		int L = (int)(a.toff[o.ta + 1] - a.toff[o.ta]);
-		if (o.qb >= 0) { const int Lb = (int)(a.toff[o.tb + 1] - a.toff[o.tb]); L = Lb > L ? Lb : L; }
+		int L = pj_tcols(a, o.ta);
+		if (o.qb >= 0) { const int Lb = pj_tcols(a, o.tb); L = Lb > L ? Lb : L; }
 		maxcols = L > maxcols ? L : maxcols;
 	}
 	const int nsteps = (maxcols + 16 + 15) & ~15;
@@ -1501,6 +1507,7 @@ struct StripCtx {
 	u32 prof, ring, ringb, bin, bout, nulloff;
 	int l16, ncols, nsteps, c_edge, dirstep, store_from, row0;
 	int ncols2[2], c_edge2[2];   /* capture: the two query halves have their own windows of the target */
+	const int8_t* tg2[2];        /* capture: ... reached through a 64-bit base per half (pair jobs: the half's own target or window of a resident set) */
 	bool mine, first, last;
 	const int8_t* tg;
 	u32* bnd;          /* this job's boundary records */
@@ -1517,7 +1524,8 @@ struct StripCtx {
 template <int PS> SSW_DEV u32 strip_code_off(const StripCtx& x, int h, int tc, bool capture)
 {
 	const int nc = capture ? x.ncols2[h] : x.ncols, ce = capture ? x.c_edge2[h] : x.c_edge;
-	int code = tc < nc ? x.tg[ce + x.dirstep * tc] : x.n;
+	const int8_t* tg = capture ? x.tg2[h] : x.tg;
+	int code = tc < nc ? tg[ce + x.dirstep * tc] : x.n;
 	if (code < 0 || code > x.n) code = x.n;
 	return (u32)code * (u32)PS;
 }
@@ -1801,6 +1809,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 /* capture mode: one query half of a job (see k_chainx) */
 struct CapHalf {
 	int q, qlen, lena, rows, ncols, c_edge;
+	const int8_t* tg;      /* column 0 of this half's target: a.tgt, or the job's own target / window (ssw_vmap) */
 	int band;      /* > 0: capped reverse pass on a diagonal band -- a strip of rows [r0, r0 + n) only visits columns [r0 - band, r0 + n + band) */
 	bool active, capped;
 	ssw_dres r;
@@ -1809,7 +1818,7 @@ struct CapHalf {
 
 SSW_DEV void cap_half_setup(CapHalf& h, const ssw_chainx_args& a, int q)
 {
-	h.q = q; h.active = false; h.capped = false; h.qlen = 0; h.lena = 0; h.rows = 0; h.ncols = 0; h.c_edge = 0; h.qc = a.qcodes; h.band = 0;
+	h.q = q; h.active = false; h.capped = false; h.qlen = 0; h.lena = 0; h.rows = 0; h.ncols = 0; h.c_edge = 0; h.qc = a.qcodes; h.band = 0; h.tg = a.tgt;
 	if (q < 0) return;
 	h.r = a.res[q];
 	h.active = h.r.status == 0 && h.r.score1 > 0 && (a.reverse ? h.r.want_begin == 1 : !h.r.loc_done);
@@ -1845,7 +1854,7 @@ SSW_DEV void cap_half_setup(CapHalf& h, const ssw_chainx_args& a, int q)
 	}
 	h.ncols = (int)w + 1;
 	h.c_edge = a.reverse ? h.r.ref_end1 : h.r.ref_end1 - (int)w;
-	if (a.vm.vq) h.c_edge += (int)a.vm.toff[a.vm.vt[q]];      /* pair jobs: the chain reads from the concatenated targets (the host keeps them below 2^31 residues) */
+	h.tg = vm_target(a.vm, a.tgt, q);      /* pair jobs: a 64-bit base into the concatenated targets; c_edge stays relative to the job's target / window */
 }
 
 /* the window's best cell of one half -> the result record (same contract as k_capture) */
@@ -1890,7 +1899,7 @@ __global__ void __launch_bounds__(64) k_chainx(ssw_chainx_args a)
 	x.prof = (u32)grp * (prof_bytes + G::EXTRA); x.ring = x.prof + prof_bytes; x.ringb = x.ring + G::RINGB; x.bin = x.ringb + G::RINGB;
 	x.bout = x.bin + BND_RING_BYTES; x.nulloff = (u32)a.n * G::PSTRIDE;
 	const u32 red = x.bout + BND_RING_BYTES;
-	x.l16 = l16; x.gapO2 = a.gapO2; x.gapE2 = a.gapE2; x.n = a.n; x.tg = CAPTURE && a.vm.vq ? a.vm.tcodes : a.tgt; x.bmask = 63u;
+	x.l16 = l16; x.gapO2 = a.gapO2; x.gapE2 = a.gapE2; x.n = a.n; x.tg = a.tgt; x.bmask = 63u;
 	x.fr_base = 0; x.fr_kmask = 0; x.gapEi = 0;
 	const int job = (int)blockIdx.x * (64 / GL) + grp;
 	const bool valid = job < a.njobs;
@@ -1900,7 +1909,7 @@ __global__ void __launch_bounds__(64) k_chainx(ssw_chainx_args a)
 	bool active = false;
 	CapHalf ch[2];
 	x.ncols = 0; x.c_edge = 0; x.dirstep = 1; x.store_from = 0; x.o16 = 0; x.o8 = 0; x.g16 = 0; x.g8 = 0; x.col_shift = 0;
-	x.ncols2[0] = x.ncols2[1] = 0; x.c_edge2[0] = x.c_edge2[1] = 0;
+	x.ncols2[0] = x.ncols2[1] = 0; x.c_edge2[0] = x.c_edge2[1] = 0; x.tg2[0] = x.tg2[1] = a.tgt;
 	if (!CAPTURE) {
 		if (valid) {
 			const int pair = job / a.ntiles, t = job - pair * a.ntiles;
@@ -1926,7 +1935,7 @@ __global__ void __launch_bounds__(64) k_chainx(ssw_chainx_args a)
 		if (ch[0].active) { qa = ch[0].qc; lena = ch[0].lena; rowsa = ch[0].rows; }
 		if (ch[1].active) { qb = ch[1].qc; lenb = ch[1].lena; rowsb = ch[1].rows; }
 		rows_total = rowsa > rowsb ? rowsa : rowsb;
-		for (int h = 0; h < 2; ++h) { x.ncols2[h] = ch[h].active ? ch[h].ncols : 0; x.c_edge2[h] = ch[h].c_edge; }
+		for (int h = 0; h < 2; ++h) { x.ncols2[h] = ch[h].active ? ch[h].ncols : 0; x.c_edge2[h] = ch[h].c_edge; x.tg2[h] = ch[h].tg; }
 		x.ncols = x.ncols2[0] > x.ncols2[1] ? x.ncols2[0] : x.ncols2[1];
 	}
 	const int S = active ? (rows_total + GL * R - 1) / (GL * R) : 0;
@@ -2033,7 +2042,7 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 	x.prof = 0; x.ring = prof_bytes; x.ringb = x.ring + (CAPTURE ? QG::RINGB : 0u); x.bin = x.ringb + QG::RINGB;
 	x.bout = x.bin + BND_RING_BYTES; x.nulloff = (u32)a.n * G::PSTRIDE; x.bmask = 31u;
 	const u32 red = x.bin;
-	x.l16 = l16; x.gapO2 = a.gapO2; x.gapE2 = a.gapE2; x.n = a.n; x.tg = CAPTURE && a.vm.vq ? a.vm.tcodes : a.tgt;
+	x.l16 = l16; x.gapO2 = a.gapO2; x.gapE2 = a.gapE2; x.n = a.n; x.tg = a.tgt;
 	x.fr_base = a.fr_base; x.fr_kmask = a.fr_kmask; x.gapEi = (int)(a.gapE2 & 0xffffu);
 	const int S = a.strips, nitems = a.njobs * S;
 	int* const ticket = a.queue; int* const flags = a.queue + 1;
@@ -2057,7 +2066,7 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 		bool active = false;
 		CapHalf ch[2];
 		x.ncols = 0; x.c_edge = 0; x.dirstep = 1; x.store_from = 0; x.o16 = 0; x.o8 = 0; x.g16 = 0; x.g8 = 0; x.col_shift = 0;
-		x.ncols2[0] = x.ncols2[1] = 0; x.c_edge2[0] = x.c_edge2[1] = 0;
+		x.ncols2[0] = x.ncols2[1] = 0; x.c_edge2[0] = x.c_edge2[1] = 0; x.tg2[0] = x.tg2[1] = a.tgt;
 		if (sidx > 0) {   /* everything the strip above wrote -- boundary records, its best cell, and (window passes) the records */
 			if (!a.whole_jobs && tid == 0 && !dev_flag_wait(flags + (int64_t)job * S + sidx - 1)) atomicAdd(a.err, 1);   /* error word: the host fails the call */
 			dev_fence();
@@ -2085,7 +2094,7 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 			if (ch[0].active) { qa = ch[0].qc; lena = ch[0].lena; rowsa = ch[0].rows; }
 			if (ch[1].active) { qb = ch[1].qc; lenb = ch[1].lena; rowsb = ch[1].rows; }
 			rows_total = rowsa > rowsb ? rowsa : rowsb;
-			for (int h = 0; h < 2; ++h) { x.ncols2[h] = ch[h].active ? ch[h].ncols : 0; x.c_edge2[h] = ch[h].c_edge; }
+			for (int h = 0; h < 2; ++h) { x.ncols2[h] = ch[h].active ? ch[h].ncols : 0; x.c_edge2[h] = ch[h].c_edge; x.tg2[h] = ch[h].tg; }
 			x.ncols = x.ncols2[0] > x.ncols2[1] ? x.ncols2[0] : x.ncols2[1];
 		}
 		/* fill jobs of a launch with a.tail_R > 0 (all of the same padded length): S - 1 strips of R rows per lane and a LAST strip of
@@ -3580,10 +3589,21 @@ __global__ void __launch_bounds__(256) k_seqgather(ssw_seqgather_args a)
 {
 	const int i = (int)blockIdx.x;
 	if (i >= a.count) return;
-	const int8_t* src = a.src + a.src_off[a.idx[i]];
+	const int8_t* src = a.src + a.src_off[a.idx[i]] + (a.src_beg ? a.src_beg[i] : 0);
 	int8_t* dst = a.dst + a.dst_off[i];
 	const int64_t len = a.dst_off[i + 1] - a.dst_off[i];
 	for (int64_t k = threadIdx.x; k < len; k += blockDim.x) dst[k] = src[k];
+}
+
+/* k_wintab (ssw_wintab_args): the per-pair window table of ssw_gpu_align_windows from the caller's (target, begin, length) arrays and the
+   resident offsets -- the host uploads 16 bytes per pair and nothing else about the targets.  One thread per window, one 16-byte store. */
+__global__ void __launch_bounds__(256) k_wintab(ssw_wintab_args a)
+{
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= a.count) return;
+	ssw_win w;
+	w.start = a.toff[a.tidx[i]] + a.tbeg[i]; w.len = a.tlen[i]; w.pad = 0;
+	a.win[i] = w;
 }
 
 /* k_select (ssw_select_args): the pairs of a database-search chunk that go on to the reverse pass, compacted in (bucket-ordered
@@ -3949,6 +3969,14 @@ extern "C" int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stre
 	ssw_seqgather_args args = *a;
 	if (args.count <= 0) return 0;
 	SSW_LAUNCH(k_seqgather, ssw_seqgather_args, args, args.count, 256, 0, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream)
+{
+	ssw_wintab_args args = *a;
+	if (args.count <= 0) return 0;
+	SSW_LAUNCH(k_wintab, ssw_wintab_args, args, (args.count + 255) / 256, 256, 0, stream);
 	return SSW_LAUNCH_OK();
 }
 

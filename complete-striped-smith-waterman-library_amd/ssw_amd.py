@@ -50,7 +50,7 @@ class Timing(C.Structure):
                 ("fill_cells", C.c_int64), ("cells", C.c_int64), ("reduce_ms", C.c_double), ("locate_ms", C.c_double),
                 ("trace_ms", C.c_double), ("n_word", C.c_int64), ("n_byte", C.c_int64), ("fill_kernel", C.c_char * 48),
                 ("fill_ops_per_row", C.c_double), ("fill_rows_per_lane", C.c_int32), ("fill_strips", C.c_int32),
-                ("db_repeats", C.c_int64), ("fill_pipelined", C.c_int64)]
+                ("db_repeats", C.c_int64), ("fill_pipelined", C.c_int64), ("win_copied", C.c_int64)]
 
 
 HIT_DTYPE = np.dtype([("score1", "<u2"), ("score2", "<u2"), ("ref_end1", "<i4"), ("read_end1", "<i4"), ("ref_end2", "<i4")], align=True)
@@ -109,6 +109,10 @@ def load(path=None):
         L.ssw_gpu_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params),
                                           C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_pairs.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows"):
+        L.ssw_gpu_align_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.POINTER(Params), C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -307,6 +311,48 @@ class Context(object):
             cig = np.zeros(0, dtype=np.uint32)
         if want_cigar and pool:
             C.CDLL(None).free(pool)
+        return res, cig
+
+    def align_windows(self, queries, targets, qidx, tidx, tbeg, tlen, mat, n, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1,
+                      score_size=2, want_cigar=True, mark_mismatch=False, out=None, rebase=False):
+        """windows of resident targets (ssw_gpu_align_windows): record i is the alignment of query qidx[i] against residues
+        [tbeg[i], tbeg[i] + tlen[i]) of target tidx[i], positions relative to the window
+        -> (numpy record array [npairs] of RESULT_DTYPE, numpy uint32 CIGAR pool in pair order).
+        rebase=True adds tbeg[i] to ref_begin1, ref_end1 and ref_end2 where they are >= 0 (target coordinates, what a mapper writes into
+        SAM; -1 sentinels stay).  The fields are int32: a target is below 2^31 residues (ref_end1 is an int32 for align_batch too), and a
+        position inside a window of it is below the target's length, so the sums fit."""
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        npairs = int(qi.shape[0])
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            res = np.zeros(npairs, dtype=RESULT_DTYPE)
+        else:
+            res = out
+            if res.dtype != RESULT_DTYPE or res.shape != (npairs,) or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a C-contiguous [npairs] array of RESULT_DTYPE")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_align_windows(self.h, queries.h, targets.h, qi.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                                            tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p), npairs, C.byref(p),
+                                            res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_align_windows: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        if want_cigar and words.value > 0:
+            cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy()
+        else:
+            cig = np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase:
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                v = res[f]
+                res[f] = np.where(v >= 0, v + tb, v).astype(np.int32)
         return res, cig
 
     def search_db(self, queries, targets, mat, n, gapO=3, gapE=1, maskLen=-1, score_size=2, chunk=0, on_chunk=None):

@@ -82,6 +82,8 @@ typedef struct {
 	int64_t db_repeats;    /* (rounds 1-2: workgroups of the database search that repeated in the int16 form; always 0 since the column-frame form) */
 	int64_t fill_pipelined; /* fill launches of the call that ran as a PIPELINED series (main stream / a second stream alternately, two launches in flight, round 6): they overlap,
 	                           fill_ms brackets each series as a whole -- fill_ms / fill_launches is then the series' time per launch, not a kernel's duration */
+	int64_t win_copied;    /* ssw_gpu_align_windows: target residues copied into temporary sets by the call (0 when every pair took the fast path;
+	                          always 0 for the other entry points) */
 	/* new fields are only ever appended here; ssw_gpu_last_timing_sized lets a caller built against an older header keep its layout */
 } ssw_gpu_timing;
 
@@ -129,7 +131,7 @@ int ssw_gpu_align_batch(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
  *
  * Fast path (one fused kernel, k_fillpairs: two pairs per 16-lane chain, each half of a register against its own target): gapO > gapE,
  * n <= 32, max(mat) <= 49, queries of 1..640 residues (n x ceil(ceil(len/16)/4) x 256 < 64 KiB), targets of 1..65 000 columns; with
- * flag != 0 the pairs that pass src/ssw.c:916 then go through ONE batched reverse pass and traceback (targets below 2^31 residues in all).
+ * flag != 0 the pairs that pass src/ssw.c:916 then go through ONE batched reverse pass and traceback (whatever the size of the target set).
  * Every other pair -- empty sequences, longer ones, gapO <= gapE, wider alphabets, larger scores -- is answered exactly but SLOWLY: one
  * internal ssw_gpu_align_batch per distinct target over the subset of its queries (gathered on the device).
  */
@@ -137,6 +139,35 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
                         const int32_t* qidx, const int32_t* tidx, int64_t npairs,
                         const ssw_gpu_params* params, ssw_gpu_result* results,
                         uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Align a list of (query, WINDOW of a resident target) pairs: results[i] is, bit for bit, the record ssw_gpu_align_pairs gives for query
+ * qidx[i] against a target that consists of residues [tbeg[i], tbeg[i] + tlen[i]) of target tidx[i] uploaded as a sequence of its own -- and
+ * through it the reference's ssw_init + ssw_align(profile, ref + tbeg, tlen, ...) answer.  The loop of a mapper, variant caller or
+ * assembler whose reference genome stays on the device while every batch of reads brings a fresh list of (read, chromosome, position,
+ * length) candidates: the host uploads 16 bytes per pair and nothing else about the targets.  All positions (ref_begin1, ref_end1, ref_end2)
+ * are WINDOW-RELATIVE (add tbeg[i] for target coordinates); -1 sentinels stay -1.  The CIGAR pool (optional, malloc()ed, caller frees) holds
+ * the CIGARs in pair order, as for ssw_gpu_align_pairs.
+ * Pairs in any order; repeats, overlapping windows, identical windows and windows of different targets are all allowed.  tlen[i] == 0 gives
+ * the record of an empty target.  npairs == 0 returns 0 with *cigar_words = 0.  qidx / tidx out of range, tbeg[i] < 0, tlen[i] < 0 or
+ * tbeg[i] + tlen[i] beyond the end of target tidx[i] return -1 with a message that names the pair, before anything is launched or written:
+ * nothing is clamped, a window that leaves its chromosome is a caller's bug.  SSW_GPU_BUSY, the context lock and ssw_gpu_last_timing behave
+ * as for ssw_gpu_align_pairs; every phase stays within ssw_gpu_get_budget(ctx) (the window table, 32 bytes per pair, is an input of the call
+ * like the job list, not scratch).
+ *
+ * Fast path: ssw_gpu_align_pairs' envelope with "target" read as "window" (gapO > gapE, n <= 32, max(mat) <= 49, queries of 1..640
+ * residues, windows of 1..65 000 columns), for EVERY flag and whatever the size of the resident target set (2^31 residues and more).  On
+ * that path no target residue is copied: the fill, the reverse pass, the traceback and mark_mismatch read the window where it lies, through
+ * a per-pair (64-bit start, length) table built on the device.  Everything else -- longer windows or queries, empty ones, gapO <= gapE,
+ * wider alphabets, larger scores -- is answered exactly and may be slow: those windows are gathered on the device into temporary sets
+ * (identical windows once) and handed to ssw_gpu_align_pairs' path; ssw_gpu_timing.win_copied counts their residues.
+ * Not provided (yet): a multi-device pool variant, a CLI option, a strand flag per pair (both strands: ssw_gpu_seqs_with_revcomp on the
+ * reads and qidx = count + i), a wider envelope (queries over 640 residues, windows over 65 000 columns on the fast path).
+ */
+int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                          const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                          int64_t npairs, const ssw_gpu_params* params, ssw_gpu_result* results,
+                          uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against

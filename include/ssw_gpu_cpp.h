@@ -174,6 +174,61 @@ class BatchAligner {
     free(pool);
   }
 
+  // Reads against windows of the resident reference sequences (ssw_gpu_align_windows): alignments[i] is what AlignPairs gives for
+  // queries[i] against a reference that consists of residues [begin, begin + length) of reference windows[i].reference -- nothing of the
+  // references is copied or uploaded again.  Positions are relative to the window; rebase = true adds windows[i].begin to ref_begin,
+  // ref_end and ref_end_next_best where they are >= 0 (reference coordinates).  A window that leaves its reference throws.
+  struct Window {
+    int32_t reference;
+    int64_t begin;
+    int32_t length;
+  };
+  void AlignWindows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const Filter& filter,
+                    std::vector<Alignment>* alignments, int32_t maskLen, bool rebase = false, std::vector<uint16_t>* flags = 0) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::AlignWindows: no reference sequences");
+    if (windows.size() != queries.size()) throw std::runtime_error("BatchAligner::AlignWindows: one window per query");
+    const int32_t nq = (int32_t)queries.size();
+    alignments->assign(queries.size(), Alignment());
+    if (flags) flags->assign(queries.size(), 0);
+    if (nq == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0);
+    for (int32_t i = 0; i < nq; ++i) { text += queries[i]; off.push_back((int64_t)text.size()); }
+    std::vector<int32_t> qidx((size_t)nq), tidx((size_t)nq), tlen((size_t)nq);
+    std::vector<int64_t> tbeg((size_t)nq);
+    for (int32_t i = 0; i < nq; ++i) {
+      const Window& w = windows[(size_t)i];
+      if (w.reference < 0 || w.reference >= n_targets_) throw std::runtime_error("BatchAligner::AlignWindows: no such reference sequence");
+      qidx[(size_t)i] = i; tidx[(size_t)i] = w.reference; tbeg[(size_t)i] = w.begin; tlen[(size_t)i] = w.length;
+    }
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nq, table_.data());
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<ssw_gpu_result> res((size_t)nq);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_align_windows(ctx_, Q, targets_, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), nq, &p, res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_windows: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t i = 0; i < nq; ++i) {
+      const ssw_gpu_result& r = res[(size_t)i];
+      Alignment& a = (*alignments)[(size_t)i];
+      a.sw_score = r.score1; a.sw_score_next_best = r.score2; a.ref_begin = r.ref_begin1; a.ref_end = r.ref_end1;
+      a.query_begin = r.read_begin1; a.query_end = r.read_end1; a.ref_end_next_best = r.ref_end2;
+      if (flags) (*flags)[(size_t)i] = r.flag;
+      const int8_t* ref = ref_codes_.data() + ref_off_[(size_t)tidx[(size_t)i]] + tbeg[(size_t)i];      // column 0 of the window
+      Expand(a, r.cigarLen > 0 ? pool + r.cigar_off : 0, r.cigarLen, ref, text.data() + off[(size_t)i], (int)queries[(size_t)i].size());
+      if (rebase) {      // a reference is below 2^31 residues and a position lies inside it: the sums fit
+        const int32_t b = (int32_t)tbeg[(size_t)i];
+        if (a.ref_begin >= 0) a.ref_begin += b;
+        if (a.ref_end >= 0) a.ref_end += b;
+        if (a.ref_end_next_best >= 0) a.ref_end_next_best += b;
+      }
+    }
+    free(pool);
+  }
+
   // A database search kept to its best hits (ssw_gpu_search_topk): (*hits)[i] holds, in rank order (sw_score descending, then reference
   // index ascending), up to k references of the set whose alignment with queries[i] scores > 0 and >= min_score -- each with the Alignment
   // and flag that AlignPairs gives for that pair.  maskLen < 15 is raised to 15 like there.
