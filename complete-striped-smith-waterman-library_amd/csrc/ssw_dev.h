@@ -381,6 +381,25 @@ typedef struct {
 	int64_t count;
 } ssw_wintab_args;
 
+/* Best candidate window per read (ssw_gpu_align_windows_best): a segmented top-2 selection over the records k_fillpairs left on the device.
+   Group g = candidates [cand_off[g], cand_off[g + 1]); the record of candidate i is rec[slot[i]] (slot 2 j + h: half h of fill job j; the
+   candidates outside the fused kernel's envelope follow the jobs, their flag-0 records uploaded by the host).  Eligible: status 0 (SSW_OUT_WORD
+   masked out), score1 >= max(min_score, 1).  Order: score1 descending, then position in the group ascending. */
+struct ssw_best_rec {        /* byte-for-byte the layout of ssw_gpu_best (include/ssw_gpu.h) */
+	int32_t best, second, n_eligible;
+	uint16_t second_score1, pad;
+};
+typedef struct {
+	const struct ssw_out_rec* rec;
+	const int32_t* slot;         /* candidate -> index into rec */
+	const int64_t* cand_off;     /* ngroups + 1 */
+	int64_t ngroups;
+	int32_t min_score;
+	struct ssw_best_rec* sel;    /* [ngroups] */
+	struct ssw_out_rec* out;     /* [ngroups]: the winner's record as the fill wrote it (SSW_OUT_WORD kept: the host's flagged stage reads it), or the
+	                                record of an empty target (zeros, ref_begin1 = read_begin1 = -1, cigar_off = -1) when the group has no eligible candidate */
+} ssw_groupbest_args;
+
 /* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
 typedef struct {
 	const int8_t* src;
@@ -477,6 +496,7 @@ int ssw_shim_launch_prep(const ssw_prep_args* a, void* stream);
 int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream);
 int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream);
 int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefront per query */
+int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream);   /* one DPP row of 16 lanes per group */
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

@@ -27,6 +27,7 @@
 #include "ssw_dev.h"
 
 _Static_assert(sizeof(struct ssw_out_rec) == sizeof(ssw_gpu_result), "device record layout must equal ssw_gpu_result");
+_Static_assert(sizeof(struct ssw_best_rec) == sizeof(ssw_gpu_best) && sizeof(ssw_gpu_best) == 16, "device record layout must equal ssw_gpu_best");
 
 struct _profile {
 	const int8_t* read;    /* borrowed, like the reference (src/ssw.c:842-843) */
@@ -95,7 +96,7 @@ struct ssw_gpu_ctx {
 	char err[512];
 	pthread_mutex_t mu;                 /* guards the lazily created streams and the error text: ONE other thread may upload sequences while a batch call runs */
 	ssw_gpu_timing tm;
-	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab, wtab;
+	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab, wtab, brec, bmap;
 	dbuf sres, svq, svt, scnt;          /* flagged database search: survivor records, their (query, target) maps, counters */
 	dbuf scratch0, need0, list0;        /* traceback: round 0 of the narrow alignments while the wide ones' teams already run (trace_phase "early") */
 	dbuf tk_hits0, tk_hits1, tk_lst;    /* top-K search: the two chunk record buffers, the per-query lists + their state */
@@ -325,7 +326,7 @@ void ssw_gpu_close(ssw_gpu_ctx* c)
 	if (c->stream) ssw_shim_stream_sync(c->stream);
 	for (int i = 0; i < 2; ++i) { ssw_shim_free(c->hits_d[i]); ssw_shim_host_free(c->hits_h[i]); }
 	dbuf_free(&c->mat); dbuf_free(&c->pairs); dbuf_free(&c->qlist); dbuf_free(&c->res); dbuf_free(&c->cm16);
-	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab); dbuf_free(&c->wtab);
+	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab); dbuf_free(&c->wtab); dbuf_free(&c->brec); dbuf_free(&c->bmap);
 	dbuf_free(&c->sres); dbuf_free(&c->svq); dbuf_free(&c->svt); dbuf_free(&c->scnt);
 	dbuf_free(&c->scratch0); dbuf_free(&c->need0); dbuf_free(&c->list0);
 	dbuf_free(&c->tk_hits0); dbuf_free(&c->tk_hits1); dbuf_free(&c->tk_lst);
@@ -2666,10 +2667,38 @@ static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu
                             const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
                             uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells);
 
-/* The pair list of both entry points, arguments checked by the caller: planning, launch loop, flagged phases, fallback and pool assembly.
-   They differ only in where a pair's target starts and how long it is (pair_src). */
+/* select mode of the pair list (ssw_gpu_align_windows_best): the pairs are candidates in groups, `results` has one record per GROUP */
+typedef struct { const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel; } best_mode;
+
+/* windows_fallback over the candidates list[0 .. nl) of a select-mode call, records to out[0 .. nl) in list order (the candidates' four
+   arrays are compacted, so that the fallback's "pair index" is the position in the list) */
+static int best_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
+                         const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* out,
+                         uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+{
+	int64_t* b2 = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)nl);
+	int32_t* q2 = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)nl);
+	int rc = -1;
+	if (!b2 || !q2) { fail(c, "out of host memory%s", ""); goto out; }
+	int64_t* id = b2 + nl; int32_t* t2 = q2 + nl; int32_t* l2 = q2 + 2 * nl;
+	for (int64_t k = 0; k < nl; ++k) { const int64_t i = list[k]; q2[k] = qidx[i]; t2[k] = src->tidx[i]; b2[k] = src->tbeg[i]; l2[k] = src->tlen[i]; id[k] = k; }
+	pair_src s2 = *src;
+	s2.tidx = t2; s2.tbeg = b2; s2.tlen = l2; s2.d_win = 0;
+	rc = windows_fallback(c, Q, T, q2, &s2, id, nl, prm, out, spool, swords, scap, acc, best_cells);
+out:
+	free(b2); free(q2);
+	return rc;
+}
+
+/* The pair list of the entry points, arguments checked by the caller: planning, launch loop, flagged phases, fallback and pool assembly.
+   They differ only in where a pair's target starts and how long it is (pair_src) -- and, with `bm` (select mode), in what happens to the
+   fill's records: they stay on the device in one call-long array, k_groupbest selects per group after the last fill launch, one record and
+   one selection per group come to the host, and only the winners go on to the flagged phases.  The candidates outside the envelope take
+   the fallback at flag 0 FIRST (their records join the device array, so that the selection happens in one place) and, where they win and
+   flag != 0, once more with the caller's flag. */
 static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src,
-                      int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+                      int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words,
+                      const best_mode* bm)
 {
 	const int32_t* const tidx = src->tidx;
 	if (cigar_pool) *cigar_pool = 0;
@@ -2695,6 +2724,9 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	int64_t* perm = (int64_t*)malloc(sizeof(int64_t) * (size_t)np);
 	int64_t* fb = 0; int64_t nfb = 0;
 	ssw_pjob* jobs = 0; int64_t* jix = 0; ssw_gpu_result* stage = 0;
+	ssw_gpu_result* fbrec = 0; int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0;      /* select mode */
+	unsigned char* d_brec = 0; int8_t* d_mat = 0; int64_t nj = 0;
+	const int64_t nout = bm ? bm->ngroups : np;
 	uint32_t* spool = 0; int64_t swords = 0, scap = 0;
 	ssw_gpu_timing acc; memset(&acc, 0, sizeof acc);
 	int64_t best_cells = 0;
@@ -2715,13 +2747,20 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		for (int64_t i = 0; i < np; ++i) { if (key[i] == 0xffffffffu) fb[f++] = i; else perm[kcount[key[i]]++] = i; }      /* kcount[k] ends as the end of class k */
 	}
 
+	if (bm && nfb > 0) {      /* select mode: what the candidates outside the envelope score, before the device holds anything of this call */
+		ssw_gpu_params p0 = *prm; p0.flag = 0;
+		fbrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nfb);
+		if (!fbrec) { fail(c, "out of host memory%s", ""); goto done; }
+		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+		memset(&c->tm, 0, sizeof c->tm);
+	}
 	if (nk > 0) {
 		/* jobs: neighbours of one R (sorted by target length: the two halves and the chains of a workgroup finish together) */
 		const int64_t njmax = nk / 2 + 40;
 		jobs = (ssw_pjob*)malloc(sizeof(ssw_pjob) * (size_t)njmax);
 		jix = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)njmax);
 		if (!jobs || !jix) { fail(c, "out of host memory%s", ""); goto done; }
-		int64_t rfirst[41], maxt[40]; int64_t nj = 0;
+		int64_t rfirst[41], maxt[40];
 		for (int R = 1; R <= 40; ++R) {
 			const int64_t lo = R == 1 ? 0 : kcount[(int64_t)(R - 1) * PJ_TCLS - 1], hi = kcount[(int64_t)R * PJ_TCLS - 1];
 			rfirst[R - 1] = nj; maxt[R - 1] = 0;
@@ -2742,10 +2781,13 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		const size_t hdr_mat = ((size_t)n * n + 15) / 16 * 16;
 		unsigned char* d_hdr = (unsigned char*)ensure(c, &c->pairs, hdr_mat + sizeof(ssw_pjob) * (size_t)nj);
 		int32_t* d_cnt = (int32_t*)ensure(c, &c->need, DB_COUNTERS * sizeof(int32_t));
-		stage = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * 2 * (size_t)nj);
+		if (!bm) stage = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * 2 * (size_t)nj);
 		if (!d_hdr || !d_cnt) goto done;
-		if (!stage) { fail(c, "out of host memory%s", ""); goto done; }
-		int8_t* d_mat = (int8_t*)d_hdr;
+		if (!bm && !stage) { fail(c, "out of host memory%s", ""); goto done; }
+		/* select mode: the records of ALL fill launches stay on the device (two per job, then the fallback's), followed by the per-group output.
+		   An input / output of the call like the window table, not scratch under the budget: 48 bytes per candidate */
+		if (bm && !(d_brec = (unsigned char*)ensure(c, &c->brec, sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb) + 64 * (size_t)bm->ngroups))) goto done;
+		d_mat = (int8_t*)d_hdr;
 		ssw_pjob* d_jobs = (ssw_pjob*)(d_hdr + hdr_mat);
 		c->nev = 0;
 		ssw_shim_event_record(c->ev_t0, c->stream);
@@ -2781,7 +2823,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			if (jpl > jn) jpl = jn;
 			uint32_t* d_cm16 = (uint32_t*)ensure(c, &c->cm16, (size_t)(4 * stride * jpl));
 			uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
-			struct ssw_out_rec* d_out = (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
+			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
 			if (!d_cm16 || !d_cm8 || !d_out) goto done;
 			int32_t fr_base = 0, fr_kmask = 0;
 			const int fr = !c->kn.db_plain && ssw_frame_params(&c->kn, (int64_t)16 * R * maxmat, prm->gapO, prm->gapE, minmat, 16, &fr_base, &fr_kmask);
@@ -2791,14 +2833,14 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 				fa.qcodes = Q->d_codes; fa.qoff = Q->d_off; fa.tcodes = T->d_codes; fa.toff = T->d_off; fa.win = src->d_win; fa.jobs = d_jobs + j0 + a0;
 				fa.njobs = jn - a0 < jpl ? jn - a0 : jpl; fa.mat = d_mat; fa.n = n; fa.gapO2 = gapO2; fa.gapE2 = gapE2;
 				fa.cm16 = d_cm16; fa.cm8 = d_cm8; fa.cm_stride = stride; fa.maskLen = prm->maskLen; fa.bias = bias; fa.score_size = prm->score_size;
-				fa.out = d_out; fa.counters = d_cnt; fa.form = fr; fa.fr_base = fr_base; fa.fr_kmask = fr_kmask;
+				fa.out = bm ? d_out + 2 * (j0 + a0) : d_out; fa.counters = d_cnt; fa.form = fr; fa.fr_base = fr_base; fa.fr_kmask = fr_kmask;
 				fa.nch = nch_l; fa.mark_word = prm->flag != 0;
 				void* e0 = next_event(c); void* e1 = next_event(c);
 				ssw_shim_event_record(e0, c->stream);
 				if (ssw_shim_launch_fillpairs(R, &fa, c->stream)) { fail(c, "fillpairs launch failed: %s", ssw_shim_last_error()); goto done; }
 				ssw_shim_event_record(e1, c->stream);
 				/* same stream: the next launch of the loop reuses d_out / d_cm* only after this download */
-				if (ssw_shim_d2h(stage + 2 * (j0 + a0), d_out, sizeof(struct ssw_out_rec) * 2 * (size_t)fa.njobs, c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+				if (!bm && ssw_shim_d2h(stage + 2 * (j0 + a0), d_out, sizeof(struct ssw_out_rec) * 2 * (size_t)fa.njobs, c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
 				c->tm.fill_launches++;
 				for (int64_t j = j0 + a0; j < j0 + a0 + fa.njobs; ++j) {
 					const int64_t La = ps_tlen(src, T, jix[2 * j]), Lb = jix[2 * j + 1] >= 0 ? ps_tlen(src, T, jix[2 * j + 1]) : 0;
@@ -2815,22 +2857,74 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (ssw_shim_d2h(cnt, d_cnt, sizeof cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
 		for (int e = 0; e + 1 < c->nev; e += 2) c->tm.fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
 		c->tm.fill_cells = kcells; c->tm.n_word = cnt[0]; c->tm.n_byte = cnt[1];      /* (the reduction is fused into the fill: reduce_ms stays 0) */
-		/* the records of the pairs in job order (stage holds two per job; an idle high half is dropped) */
-		int64_t nrec = 0;
-		for (int64_t j = 0; j < nj; ++j)
-			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
-		if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
-		                                    &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
-		for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
-		timing_add(&acc, &c->tm, &best_cells);
+		if (!bm) {
+			/* the records of the pairs in job order (stage holds two per job; an idle high half is dropped) */
+			int64_t nrec = 0;
+			for (int64_t j = 0; j < nj; ++j)
+				for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
+			if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
+			                                    &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
+			for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
+			timing_add(&acc, &c->tm, &best_cells);
+		}
 	}
-	if (nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)
+	if (bm) {
+		/* ---- select: candidate -> record slot, k_groupbest, one selection + one record per group to the host */
+		const int64_t ng = bm->ngroups;
+		const size_t rec_bytes = sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb);
+		if (!d_brec && !(d_brec = (unsigned char*)ensure(c, &c->brec, rec_bytes + 64 * (size_t)ng))) goto done;
+		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + 4 * (size_t)np);      /* (4 bytes per candidate, 8 per group) */
+		slot = (int32_t*)malloc(sizeof(int32_t) * (size_t)np);
+		if (!d_map) goto done;
+		if (!slot) { fail(c, "out of host memory%s", ""); goto done; }
+		for (int64_t j = 0; j < nj; ++j)
+			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) slot[jix[2 * j + h]] = (int32_t)(2 * j + h);
+		for (int64_t f = 0; f < nfb; ++f) slot[fb[f]] = (int32_t)(2 * nj + f);
+		ssw_groupbest_args ga; memset(&ga, 0, sizeof ga);
+		ga.rec = (const struct ssw_out_rec*)d_brec; ga.cand_off = (const int64_t*)d_map; ga.slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1));
+		ga.ngroups = ng; ga.min_score = bm->min_score;
+		ga.out = (struct ssw_out_rec*)(d_brec + rec_bytes); ga.sel = (struct ssw_best_rec*)(d_brec + rec_bytes + sizeof(struct ssw_out_rec) * (size_t)ng);
+		if ((nfb > 0 && ssw_shim_h2d((void*)(ga.rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
+		    ssw_shim_h2d((void*)ga.cand_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)ga.slot, slot, 4 * (size_t)np, c->stream)) {
+			fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
+		}
+		ssw_shim_event_record(c->ev_a, c->stream);
+		if (ssw_shim_launch_groupbest(&ga, c->stream)) { fail(c, "groupbest launch failed: %s", ssw_shim_last_error()); goto done; }
+		ssw_shim_event_record(c->ev_b, c->stream);
+		if (ssw_shim_d2h(results, ga.out, sizeof(ssw_gpu_result) * (size_t)ng, c->stream) || ssw_shim_d2h(bm->sel, ga.sel, sizeof(ssw_gpu_best) * (size_t)ng, c->stream) ||
+		    ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+		c->tm.reduce_ms = ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+		/* ---- the winners alone go on: the fused path's through the reverse pass and the traceback (their fill records reused), the others
+		   through the fallback once more with the caller's flag */
+		int64_t nin = 0, nfw = 0; int64_t* wg = 0;
+		if (prm->flag != 0) {
+			wlist = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)ng); wrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)ng);
+			if (!wlist || !wrec) { fail(c, "out of host memory%s", ""); goto done; }
+			wg = wlist + ng;      /* wlist: the fused path's winners from the front, the fallback's from the back; wg: their groups */
+			for (int64_t g = 0; g < ng; ++g) {
+				if (bm->sel[g].best < 0) continue;
+				const int64_t i = bm->cand_off[g] + bm->sel[g].best;
+				if (key[i] == 0xffffffffu) { ++nfw; wlist[ng - nfw] = i; wg[ng - nfw] = g; }
+				else { wlist[nin] = i; wg[nin] = g; wrec[nin] = results[g]; ++nin; }
+			}
+			if (nin > 0 && pairs_flagged(c, Q, T, qidx, src, wlist, wrec, nin, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
+			                             &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
+			for (int64_t k = 0; k < nin; ++k) results[wg[k]] = wrec[k];
+		}
+		timing_add(&acc, &c->tm, &best_cells);
+		if (nfw > 0) {
+			if (best_fallback(c, Q, T, qidx, src, wlist + (ng - nfw), nfw, prm, wrec, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+			for (int64_t k = 0; k < nfw; ++k) results[wg[ng - nfw + k]] = wrec[k];
+		}
+		acc.best_flagged = nin + nfw;
+	}
+	if (!bm && nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)
 	                          : pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells))) goto done;
 	if (swords > 0) {      /* the pool in pair order (offsets as the caller's pool would have them, also when it asked for none) */
 		uint32_t* pool = cigar_pool ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)swords) : 0;
 		if (cigar_pool && !pool) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto done; }
 		int64_t w = 0;
-		for (int64_t i = 0; i < np; ++i) {
+		for (int64_t i = 0; i < nout; ++i) {
 			ssw_gpu_result* r = &results[i];
 			if (r->cigarLen > 0 && r->cigar_off >= 0) {
 				if (pool) memcpy(pool + w, spool + r->cigar_off, sizeof(uint32_t) * (size_t)r->cigarLen);
@@ -2847,6 +2941,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	rc = 0;
 done:
 	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(spool);
+	free(fbrec); free(slot); free(wlist); free(wrec);
 	return rc;
 }
 
@@ -2865,7 +2960,7 @@ static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		}
 	pair_src src; memset(&src, 0, sizeof src);
 	src.tidx = tidx; src.who = "align_pairs";
-	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words);
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, 0);
 }
 
 int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx, int64_t npairs,
@@ -2974,6 +3069,26 @@ out:
 	return rc;
 }
 
+/* every pair's indices and window inside its target, or -1 with a message that names the first pair that is not */
+static int windows_check(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
+                         const int64_t* tbeg, const int32_t* tlen, int64_t np)
+{
+	for (int64_t i = 0; i < np; ++i) {
+		char msg[240];
+		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
+			snprintf(msg, sizeof msg, "%s: index out of range (pair %lld: query %d of %d, target %d of %d)", who, (long long)i, qidx[i], Q->count, tidx[i], T->count);
+			return fail(c, "%s", msg);
+		}
+		const int64_t tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
+		if (tbeg[i] < 0 || tlen[i] < 0 || tbeg[i] > tl || (int64_t)tlen[i] > tl - tbeg[i]) {      /* no clamping: a window that leaves its target is the caller's bug */
+			snprintf(msg, sizeof msg, "%s: window out of range (pair %lld: columns [%lld, %lld + %d) of target %d, which has %lld)", who, (long long)i,
+			         (long long)tbeg[i], (long long)tbeg[i], tlen[i], tidx[i], (long long)tl);
+			return fail(c, "%s", msg);
+		}
+	}
+	return 0;
+}
+
 static int align_windows_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
                                 const int64_t* tbeg, const int32_t* tlen, int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results,
                                 uint32_t** cigar_pool, int64_t* cigar_words)
@@ -2983,22 +3098,10 @@ static int align_windows_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
 	if (prm->n < 1) return fail(c, "align_windows: alphabet size must be >= 1%s", "");
 	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_windows: score_size must be 0, 1 or 2%s", "");
 	if (np > 0x7fffff00) return fail(c, "align_windows: %s", "more than 2^31 pairs in one call");      /* (a pair's window is named by a 32-bit index) */
-	for (int64_t i = 0; i < np; ++i) {
-		char msg[200];
-		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
-			snprintf(msg, sizeof msg, "pair %lld: query %d of %d, target %d of %d", (long long)i, qidx[i], Q->count, tidx[i], T->count);
-			return fail(c, "align_windows: index out of range (%s)", msg);
-		}
-		const int64_t tl = T->h_off[tidx[i] + 1] - T->h_off[tidx[i]];
-		if (tbeg[i] < 0 || tlen[i] < 0 || tbeg[i] > tl || (int64_t)tlen[i] > tl - tbeg[i]) {      /* no clamping: a window that leaves its target is the caller's bug */
-			snprintf(msg, sizeof msg, "pair %lld: columns [%lld, %lld + %d) of target %d, which has %lld", (long long)i, (long long)tbeg[i], (long long)tbeg[i],
-			         tlen[i], tidx[i], (long long)tl);
-			return fail(c, "align_windows: window out of range (%s)", msg);
-		}
-	}
+	if (windows_check(c, "align_windows", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
 	pair_src src; memset(&src, 0, sizeof src);
 	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows";
-	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words);
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, 0);
 }
 
 int ssw_gpu_align_windows(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
@@ -3012,6 +3115,63 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_s
 		return SSW_GPU_BUSY;
 	}
 	const int rc = align_windows_locked(c, Q, T, qidx, tidx, tbeg, tlen, npairs, prm, results, cigar_pool, cigar_words);
+	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
+	return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Best candidate window per read (ssw_gpu_align_windows_best): ssw_gpu_align_windows' pair list in groups, pairs_core in select mode.
+ * ------------------------------------------------------------------------------------------------ */
+static void topk_pad(ssw_gpu_result* o);
+
+static int align_windows_best_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t ng,
+                                     const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, const ssw_gpu_params* prm,
+                                     int32_t min_score, ssw_gpu_best* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	char msg[200];
+	if (!Q || !T || !prm || !prm->mat || ng < 0 || (ng > 0 && (!cand_off || !sel || !results))) return fail(c, "align_windows_best: NULL argument%s", "");
+	if (Q->ctx != c || T->ctx != c) return fail(c, "align_windows_best: sequences belong to another context%s", "");
+	if (prm->n < 1) return fail(c, "align_windows_best: alphabet size must be >= 1%s", "");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_windows_best: score_size must be 0, 1 or 2%s", "");
+	if (ng == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }
+	if (cand_off[0] != 0) {
+		snprintf(msg, sizeof msg, "group 0 starts at candidate %lld", (long long)cand_off[0]);
+		return fail(c, "align_windows_best: cand_off[0] must be 0 (%s)", msg);
+	}
+	for (int64_t g = 0; g < ng; ++g)
+		if (cand_off[g + 1] < cand_off[g]) {
+			snprintf(msg, sizeof msg, "group %lld: candidates [%lld, %lld)", (long long)g, (long long)cand_off[g], (long long)cand_off[g + 1]);
+			return fail(c, "align_windows_best: cand_off decreases (%s)", msg);
+		}
+	const int64_t np = cand_off[ng];
+	if (np > 0x7fffff00) return fail(c, "align_windows_best: %s", "more than 2^31 candidates in one call");
+	if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) return fail(c, "align_windows_best: NULL argument%s", "");
+	if (windows_check(c, "align_windows_best", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
+	if (np == 0) {      /* empty groups only */
+		memset(&c->tm, 0, sizeof c->tm);
+		for (int64_t g = 0; g < ng; ++g) { topk_pad(&results[g]); sel[g].best = sel[g].second = -1; sel[g].n_eligible = 0; sel[g].second_score1 = 0; sel[g].pad = 0; }
+		return 0;
+	}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows_best";
+	best_mode bm; bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.sel = sel;
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
+}
+
+int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t ngroups,
+                               const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                               const ssw_gpu_params* prm, int32_t min_score, ssw_gpu_best* sel, ssw_gpu_result* results,
+                               uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows_best: NULL context%s", "");
+	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return SSW_GPU_BUSY;
+	}
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	const int rc = align_windows_best_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, min_score, sel, results, cigar_pool, cigar_words);
 	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
 	return rc;
 }

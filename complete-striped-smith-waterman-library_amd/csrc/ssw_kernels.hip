@@ -3818,6 +3818,67 @@ __global__ void __launch_bounds__(64) k_topk(ssw_topk_args a)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * k_groupbest (ssw_groupbest_args): the best two eligible candidates of every group of a candidate list (ssw_gpu_align_windows_best).
+ * One DPP row of 16 lanes per group, four groups per wavefront, sixteen per workgroup.  The lanes stride over the group's candidates
+ * (lane l takes positions l, l + 16, ...): per candidate one 4-byte load of the slot map (consecutive lanes, consecutive words) and two
+ * 4-byte loads of its record (score1; flag | status) wherever the planner's length sort put it.  A lane keeps its two best 64-bit keys
+ *   score1 << 32 | ~position
+ * (0: none -- an eligible candidate has score1 >= 1), so that a plain maximum is the ranking; the 16 lanes' pairs are merged by four row
+ * rotations (8, 4, 2, 1: the sets that meet at every step are disjoint, every lane ends with the row's result).  Lane 0 stores the
+ * 16-byte selection record, lanes 0..2 copy the winner's 48-byte record (or the padding record) 16 bytes each.  No LDS, no atomics.
+ * ------------------------------------------------------------------------------------------------ */
+template <int N> SSW_DEV unsigned long long gb_ror(unsigned long long v)
+{
+	return (unsigned long long)xl_row_ror<N>((u32)v) | ((unsigned long long)xl_row_ror<N>((u32)(v >> 32)) << 32);
+}
+/* the row's lanes N apart merge their (best, second) pairs and their counts */
+template <int N> SSW_DEV void gb_merge(unsigned long long& k1, unsigned long long& k2, u32& cnt)
+{
+	const unsigned long long o1 = gb_ror<N>(k1), o2 = gb_ror<N>(k2);
+	const unsigned long long n2 = k1 > o1 ? (k2 > o1 ? k2 : o1) : (k1 > o2 ? k1 : o2);
+	k1 = k1 > o1 ? k1 : o1; k2 = n2;
+	cnt += xl_row_ror<N>(cnt);
+}
+
+__global__ void __launch_bounds__(256) k_groupbest(ssw_groupbest_args a)
+{
+	const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;      /* (a row is inside the list or outside it as a whole) */
+	const int l = (int)threadIdx.x & 15;
+	const bool live = g < a.ngroups;
+	const int lo = a.min_score > 1 ? a.min_score : 1;
+	unsigned long long k1 = 0, k2 = 0;
+	u32 cnt = 0;
+	int64_t c0 = 0;
+	if (live) {
+		c0 = a.cand_off[g];
+		const int64_t n = a.cand_off[g + 1] - c0;
+		for (int64_t p = l; p < n; p += 16) {
+			const u32* r = (const u32*)(a.rec + a.slot[c0 + p]);
+			const u32 s = r[0] & 0xffffu, st = (r[10] >> 16) & ~(u32)SSW_OUT_WORD;      /* word 0: score1 | score2 << 16; word 10: flag | status << 16 */
+			if (st == 0 && (int)s >= lo) {
+				const unsigned long long k = ((unsigned long long)s << 32) | (u32)~(u32)p;
+				if (k > k1) { k2 = k1; k1 = k; } else if (k > k2) k2 = k;
+				++cnt;
+			}
+		}
+	}
+	gb_merge<8>(k1, k2, cnt); gb_merge<4>(k1, k2, cnt); gb_merge<2>(k1, k2, cnt); gb_merge<1>(k1, k2, cnt);
+	if (!live) return;
+	const int best = k1 ? (int)~(u32)k1 : -1, second = k2 ? (int)~(u32)k2 : -1;
+	if (l == 0) {
+		const u32x4 v = { (u32)best, (u32)second, cnt, (u32)(k2 >> 32) & 0xffffu };
+		*(u32x4*)(a.sel + g) = v;
+	}
+	if (l < 3) {
+		u32x4 v = { 0u, 0u, 0u, 0u };
+		if (best >= 0) v = ((const u32x4*)(a.rec + a.slot[c0 + best]))[l];
+		else if (l == 0) { v.y = 0xffffffffu; v.w = 0xffffffffu; }      /* ref_begin1, read_begin1 */
+		else if (l == 2) { v.x = 0xffffffffu; v.y = 0xffffffffu; }      /* cigar_off */
+		((u32x4*)(a.out + g))[l] = v;
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------
  * k_selftest: (a) the cross-lane primitives applied to the lane id, so that tests can pin the DPP semantics the
  * chains rely on (and that the CPU emulator assumes) on real hardware; (b) a packed-int16 VALU issue-rate probe
  * (8 independent v_pk_add_i16/v_pk_max_i16/v_pk_sub_u16 chains) whose measured rate is the roofline's "peak".
@@ -3977,6 +4038,14 @@ extern "C" int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream)
 	ssw_wintab_args args = *a;
 	if (args.count <= 0) return 0;
 	SSW_LAUNCH(k_wintab, ssw_wintab_args, args, (args.count + 255) / 256, 256, 0, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream)
+{
+	ssw_groupbest_args args = *a;
+	if (args.ngroups <= 0) return 0;
+	SSW_LAUNCH(k_groupbest, ssw_groupbest_args, args, (args.ngroups + 15) / 16, 256, 0, stream);
 	return SSW_LAUNCH_OK();
 }
 

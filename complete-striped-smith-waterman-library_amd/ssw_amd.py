@@ -50,7 +50,7 @@ class Timing(C.Structure):
                 ("fill_cells", C.c_int64), ("cells", C.c_int64), ("reduce_ms", C.c_double), ("locate_ms", C.c_double),
                 ("trace_ms", C.c_double), ("n_word", C.c_int64), ("n_byte", C.c_int64), ("fill_kernel", C.c_char * 48),
                 ("fill_ops_per_row", C.c_double), ("fill_rows_per_lane", C.c_int32), ("fill_strips", C.c_int32),
-                ("db_repeats", C.c_int64), ("fill_pipelined", C.c_int64), ("win_copied", C.c_int64)]
+                ("db_repeats", C.c_int64), ("fill_pipelined", C.c_int64), ("win_copied", C.c_int64), ("best_flagged", C.c_int64)]
 
 
 HIT_DTYPE = np.dtype([("score1", "<u2"), ("score2", "<u2"), ("ref_end1", "<i4"), ("read_end1", "<i4"), ("ref_end2", "<i4")], align=True)
@@ -66,6 +66,9 @@ RESULT_DTYPE = np.dtype([("score1", "<u2"), ("score2", "<u2"), ("ref_begin1", "<
                          ("read_begin1", "<i4"), ("read_end1", "<i4"), ("ref_end2", "<i4"), ("cigarLen", "<i4"),
                          ("edit_distance", "<i4"), ("cigar_off", "<i8"), ("flag", "<u2"), ("status", "<u2")], align=True)
 assert RESULT_DTYPE.itemsize == C.sizeof(Result)
+# ssw_gpu_best (include/ssw_gpu.h): the selection record of ssw_gpu_align_windows_best
+BEST_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("n_eligible", "<i4"), ("second_score1", "<u2"), ("pad", "<u2")], align=True)
+assert BEST_DTYPE.itemsize == 16
 
 
 def load(path=None):
@@ -98,6 +101,8 @@ def load(path=None):
     L.ssw_gpu_seqs_upload_ascii.restype = C.c_void_p
     L.ssw_gpu_seqs_revcomp.argtypes = [C.c_void_p, C.c_void_p]
     L.ssw_gpu_seqs_revcomp.restype = C.c_void_p
+    L.ssw_gpu_seqs_with_revcomp.argtypes = [C.c_void_p, C.c_void_p]
+    L.ssw_gpu_seqs_with_revcomp.restype = C.c_void_p
     L.ssw_gpu_seqs_download.argtypes = [C.c_void_p, C.c_void_p, _i8p]
     L.ssw_gpu_seqs_download.restype = C.c_int
     L.ssw_gpu_seqs_free.argtypes = [C.c_void_p]
@@ -113,6 +118,10 @@ def load(path=None):
         L.ssw_gpu_align_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                             C.POINTER(Params), C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_windows.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows_best"):
+        L.ssw_gpu_align_windows_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_best.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -223,6 +232,19 @@ class Seqs(object):
         self.h = ctx.lib.ssw_gpu_seqs_upload(ctx.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), self.count)
         if not self.h:
             raise RuntimeError("ssw_gpu_seqs_upload: " + ctx.error())
+
+    def with_revcomp(self):
+        """a new set: these sequences followed by their reverse complements (ssw_gpu_seqs_with_revcomp; DNA codes 0..3) -- sequence
+        count + i is the reverse complement of sequence i, which is how a candidate list names the reverse strand of a read"""
+        lib = self.ctx.lib
+        both = object.__new__(Seqs)
+        both.ctx = self.ctx
+        both.count = 2 * self.count
+        both.lengths = np.concatenate([self.lengths, self.lengths])
+        both.h = lib.ssw_gpu_seqs_with_revcomp(self.ctx.h, self.h)
+        if not both.h:
+            raise RuntimeError("ssw_gpu_seqs_with_revcomp: " + self.ctx.error())
+        return both
 
     def free(self):
         if self.h:
@@ -354,6 +376,55 @@ class Context(object):
                 v = res[f]
                 res[f] = np.where(v >= 0, v + tb, v).astype(np.int32)
         return res, cig
+
+    def align_windows_best(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, mat, n, min_score=0, rebase=False, gapO=3, gapE=1, flag=0,
+                           filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None):
+        """best candidate window per read (ssw_gpu_align_windows_best): group g is candidates [cand_off[g], cand_off[g + 1]) of the four
+        per-candidate arrays, a candidate being what a pair of align_windows is
+        -> (sel [ngroups] of BEST_DTYPE, records [ngroups] of RESULT_DTYPE -- the winner's, or the empty record where sel["best"] is -1 --,
+        uint32 CIGAR pool in group order).  rebase=True adds the winner's tbeg to ref_begin1, ref_end1 and ref_end2 where they are >= 0.
+        `out`: (sel, records) to fill."""
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1:
+            raise ValueError("cand_off must be a 1-D array of ngroups + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        ng = int(co.shape[0]) - 1
+        if ng > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[ngroups] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            sel = np.zeros(ng, dtype=BEST_DTYPE)
+            res = np.zeros(ng, dtype=RESULT_DTYPE)
+        else:
+            sel, res = out
+            if sel.dtype != BEST_DTYPE or res.dtype != RESULT_DTYPE or sel.shape != (ng,) or res.shape != (ng,) or not sel.flags["C_CONTIGUOUS"] or \
+                    not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be C-contiguous [ngroups] arrays of BEST_DTYPE and RESULT_DTYPE")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_align_windows_best(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), ng, qi.ctypes.data_as(C.c_void_p),
+                                                 ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                 C.byref(p), int(min_score), sel.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                                 C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_align_windows_best: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase and ng > 0:
+            won = sel["best"] >= 0
+            wb = np.zeros(ng, dtype=np.int64)
+            wb[won] = tb[co[:-1][won] + sel["best"][won]]
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                v = res[f]
+                res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
+        return sel, res, cig
 
     def search_db(self, queries, targets, mat, n, gapO=3, gapE=1, maskLen=-1, score_size=2, chunk=0, on_chunk=None):
         """streamed database search (ssw_gpu_search_db): on_chunk(target_first, hits[nq, target_count] of HIT_DTYPE) is called for

@@ -69,7 +69,8 @@ typedef struct {
 	int64_t fill_launches; /* (database search: launch groups -- all size classes of one chunk of targets, side by side on several streams) */
 	int64_t fill_cells;    /* DP cells actually evaluated by the fill kernel (padding + halo included) */
 	int64_t cells;         /* sum of readLen*refLen over the batch (the GCUPS numerator) */
-	double reduce_ms;      /* score1/score2/end-position reduction (ssw_gpu_search_topk: the device time of the k_topk selection) */
+	double reduce_ms;      /* score1/score2/end-position reduction (ssw_gpu_search_topk: the device time of the k_topk selection;
+	                          ssw_gpu_align_windows_best: of the k_groupbest selection) */
 	double locate_ms;      /* read_end1 + reverse (begin position) passes */
 	double trace_ms;       /* banded traceback + CIGAR re-score */
 	int64_t n_word;        /* alignments decided under 16-bit semantics */
@@ -84,6 +85,8 @@ typedef struct {
 	                           fill_ms brackets each series as a whole -- fill_ms / fill_launches is then the series' time per launch, not a kernel's duration */
 	int64_t win_copied;    /* ssw_gpu_align_windows: target residues copied into temporary sets by the call (0 when every pair took the fast path;
 	                          always 0 for the other entry points) */
+	int64_t best_flagged;  /* ssw_gpu_align_windows_best: pairs the call handed to the reverse pass and the traceback -- the winners, never more than ngroups;
+	                          0 with flag 0 and for the other entry points */
 	/* new fields are only ever appended here; ssw_gpu_last_timing_sized lets a caller built against an older header keep its layout */
 } ssw_gpu_timing;
 
@@ -168,6 +171,53 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const s
                           const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
                           int64_t npairs, const ssw_gpu_params* params, ssw_gpu_result* results,
                           uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Best candidate window per read: ssw_gpu_align_windows over candidates in GROUPS, kept to the best candidate of every group -- what a
+ * mapper with a resident genome does with the candidate windows of a read (one per surviving seed chain, usually on both strands): which
+ * one is best, how close the runner-up is (the input of a mapping quality), and begin positions + CIGAR of the winner alone.
+ * Group g is candidates [cand_off[g], cand_off[g + 1]) of the four per-candidate arrays (cand_off[0] == 0, cand_off[ngroups] = the number of
+ * candidates); candidate i means exactly what pair i of ssw_gpu_align_windows means.  qidx is per candidate: a read's forward and
+ * reverse-complement candidates share a group (ssw_gpu_seqs_with_revcomp on the reads, qidx = count + i for the reverse strand).
+ * A candidate is ELIGIBLE when its ssw_gpu_align_windows record has status 0, score1 > 0 and score1 >= min_score (ssw_gpu_search_topk's rule).
+ * Ranking: score1 descending, then position in the group ascending; two identical windows in one group are two candidates.
+ *   sel[g]      best / second: positions (relative to cand_off[g]) of the first two of that order, -1 where there is none; n_eligible;
+ *               second_score1.  These do not depend on params->flag.
+ *   results[g]  bit for bit the record ssw_gpu_align_windows gives for the single pair `best` with the caller's flag, filters, filterd,
+ *               maskLen, score_size and mark_mismatch (window-relative positions); a group without an eligible candidate -- an empty group
+ *               too -- gets ssw_gpu_search_topk's padding record (zeros, ref_begin1 = read_begin1 = -1, cigar_off = -1);
+ *   cigar_pool  (optional, malloc()ed, caller frees) the winners' CIGARs in group order.
+ * The forward fill runs once over all candidates (k_fillpairs, as for ssw_gpu_align_windows: no target residue is copied inside the
+ * envelope); the selection runs on the device (k_groupbest); one record per GROUP comes to the host; the reverse pass, the traceback and
+ * mark_mismatch run over the winners only (ssw_gpu_timing.best_flagged), their fill records reused.
+ * Candidates outside the fast-path envelope (empty ones, reads over 640 residues, windows over 65 000 columns, gapO <= gapE, alphabets over
+ * 32 letters, max(mat) > 49) are exact in any mix, inside one group too: they take ssw_gpu_align_windows' fallback at flag 0 first, their
+ * records are uploaded beside the fill's, the DEVICE selects over everything, and those of them that win take the fallback once more
+ * with the caller's flag.
+ * Memory: the state that outlives a fill launch -- 48 bytes of record and 4 bytes of slot map per candidate, 64 bytes of output (record +
+ * selection) and 8 of offsets per group -- is an input / output of the call like the window table, not scratch under ssw_gpu_get_budget: 52 bytes per
+ * candidate (within the 64 this entry point allows itself) beyond what ssw_gpu_align_windows needs.  Fill launches are cut to the budget
+ * as there.
+ * Errors (-1 with a message that names the group or the pair, before anything is launched or written): a NULL array, cand_off[0] != 0, a
+ * decreasing cand_off, more than 0x7fffff00 candidates, an index or window out of range (ssw_gpu_align_windows' text), sequences of
+ * another context.  ngroups == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for ssw_gpu_align_windows.
+ * ssw_gpu_last_timing: reduce_ms is the device time of k_groupbest; best_flagged the winners handed to the reverse pass / traceback.
+ * Not provided (yet): a multi-device pool variant, a CLI option, more than the best two per group, building the survivor list of the
+ * flagged stage on the device (the winners' records make one round trip to the host).
+ */
+typedef struct {
+	int32_t best;          /* position in the candidate list of the group's best eligible candidate; -1: none */
+	int32_t second;        /* the runner-up under the same ranking; -1: fewer than two eligible */
+	int32_t n_eligible;    /* eligible candidates of the group */
+	uint16_t second_score1;/* score1 of `second` (0 when second == -1) */
+	uint16_t pad;          /* 0 */
+} ssw_gpu_best;
+int ssw_gpu_align_windows_best(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                               const int64_t* cand_off, int64_t ngroups,
+                               const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                               const ssw_gpu_params* params, int32_t min_score,
+                               ssw_gpu_best* sel, ssw_gpu_result* results,
+                               uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against

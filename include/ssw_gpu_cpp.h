@@ -229,6 +229,76 @@ class BatchAligner {
     free(pool);
   }
 
+  // The best candidate window of every read (ssw_gpu_align_windows_best): candidates[i] are the windows a mapper holds for queries[i]
+  // (forward strand only here: a caller with both strands passes the reverse complement as a query of its own group, or uses the C ABI).
+  // alignments[i] is what AlignWindows gives for queries[i] against the chosen window; (*best)[i].candidate is its index in
+  // candidates[i] (-1: no candidate scored > 0 and >= min_score -- alignments[i] is then a default Alignment), runner_up / runner_up_score
+  // the second of the ranking (sw_score descending, then index ascending; -1 / 0 when there is none), eligible how many qualified.
+  // The forward fill runs once over all candidates, the selection on the device, begin positions and CIGARs for the winners only.
+  struct BestWindow {
+    int32_t candidate;
+    int32_t runner_up;
+    uint16_t runner_up_score;
+    int32_t eligible;
+    uint16_t flag;
+  };
+  void AlignWindowsBest(const std::vector<std::string>& queries, const std::vector<std::vector<Window> >& candidates, const Filter& filter,
+                        std::vector<Alignment>* alignments, std::vector<BestWindow>* best, int32_t maskLen, int32_t min_score = 0,
+                        bool rebase = false) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::AlignWindowsBest: no reference sequences");
+    if (candidates.size() != queries.size()) throw std::runtime_error("BatchAligner::AlignWindowsBest: one candidate list per query");
+    const int32_t nq = (int32_t)queries.size();
+    alignments->assign(queries.size(), Alignment());
+    BestWindow none; none.candidate = -1; none.runner_up = -1; none.runner_up_score = 0; none.eligible = 0; none.flag = 0;
+    best->assign(queries.size(), none);
+    if (nq == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0), cand_off(1, 0), tbeg;
+    std::vector<int32_t> qidx, tidx, tlen;
+    for (int32_t i = 0; i < nq; ++i) {
+      text += queries[i]; off.push_back((int64_t)text.size());
+      for (size_t k = 0; k < candidates[(size_t)i].size(); ++k) {
+        const Window& w = candidates[(size_t)i][k];
+        if (w.reference < 0 || w.reference >= n_targets_) throw std::runtime_error("BatchAligner::AlignWindowsBest: no such reference sequence");
+        qidx.push_back(i); tidx.push_back(w.reference); tbeg.push_back(w.begin); tlen.push_back(w.length);
+      }
+      cand_off.push_back((int64_t)qidx.size());
+    }
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nq, table_.data());
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<ssw_gpu_result> res((size_t)nq);
+    std::vector<ssw_gpu_best> sel((size_t)nq);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_align_windows_best(ctx_, Q, targets_, cand_off.data(), nq, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), &p, min_score,
+                                              sel.data(), res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_windows_best: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t i = 0; i < nq; ++i) {
+      const ssw_gpu_best& s = sel[(size_t)i];
+      BestWindow& b = (*best)[(size_t)i];
+      b.candidate = s.best; b.runner_up = s.second; b.runner_up_score = s.second_score1; b.eligible = s.n_eligible;
+      if (s.best < 0) continue;
+      const ssw_gpu_result& r = res[(size_t)i];
+      const size_t c = (size_t)(cand_off[(size_t)i] + s.best);
+      Alignment& a = (*alignments)[(size_t)i];
+      a.sw_score = r.score1; a.sw_score_next_best = r.score2; a.ref_begin = r.ref_begin1; a.ref_end = r.ref_end1;
+      a.query_begin = r.read_begin1; a.query_end = r.read_end1; a.ref_end_next_best = r.ref_end2;
+      b.flag = r.flag;
+      Expand(a, r.cigarLen > 0 ? pool + r.cigar_off : 0, r.cigarLen, ref_codes_.data() + ref_off_[(size_t)tidx[c]] + tbeg[c], text.data() + off[(size_t)i],
+             (int)queries[(size_t)i].size());
+      if (rebase) {
+        const int32_t sh = (int32_t)tbeg[c];
+        if (a.ref_begin >= 0) a.ref_begin += sh;
+        if (a.ref_end >= 0) a.ref_end += sh;
+        if (a.ref_end_next_best >= 0) a.ref_end_next_best += sh;
+      }
+    }
+    free(pool);
+  }
+
   // A database search kept to its best hits (ssw_gpu_search_topk): (*hits)[i] holds, in rank order (sw_score descending, then reference
   // index ascending), up to k references of the set whose alignment with queries[i] scores > 0 and >= min_score -- each with the Alignment
   // and flag that AlignPairs gives for that pair.  maskLen < 15 is raised to 15 like there.
