@@ -524,10 +524,171 @@ static void* next_event(ssw_gpu_ctx* c)
 	return c->ev[c->nev++];
 }
 
+/* ---- what every batch entry point shares ---- */
+
+/* The context's streams, events and workspaces serve one call at a time (include/ssw_gpu.h "Threads").  SSW_GPU_BUSY: another thread is
+   inside this context -- its error text is the running call's and is left alone (ssw_gpu_strerror names the code); the pool outputs of
+   the refused call read as empty. */
+static int ctx_enter(ssw_gpu_ctx* c, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) return 0;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	return SSW_GPU_BUSY;
+}
+static int ctx_leave(ssw_gpu_ctx* c, int rc) { __atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE); return rc; }
+
+static int fail_who(ssw_gpu_ctx* c, const char* who, const char* what)
+{
+	char msg[160];
+	snprintf(msg, sizeof msg, "%s: %s", who, what);
+	return fail(c, "%s", msg);
+}
+/* The argument checks of the batch entry points, in the order they fire: NULL arguments (an entry point checks its own further pointers
+   first, with the same text), sequences of another context -- check_seqs --, then the alphabet size and score_size -- check_scoring.
+   Only align_batch has a check of its own in between (its target range). */
+static int check_seqs(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm)
+{
+	if (!Q || !T || !prm || !prm->mat) return fail_who(c, who, "NULL argument");
+	if (Q->ctx != c || T->ctx != c) return fail_who(c, who, "sequences belong to another context");
+	return 0;
+}
+static int check_scoring(ssw_gpu_ctx* c, const char* who, const ssw_gpu_params* prm)
+{
+	if (prm->n < 1) return fail_who(c, who, "alphabet size must be >= 1");
+	if (prm->score_size < 0 || prm->score_size > 2) return fail_who(c, who, "score_size must be 0, 1 or 2");
+	return 0;
+}
+static int check_common(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm)
+{
+	return check_seqs(c, who, Q, T, prm) || check_scoring(c, who, prm) ? -1 : 0;
+}
+
+/* smallest (<= 0) and largest (>= 0) entry of the WHOLE scoring matrix, and the 8-bit bias as ssw_init computes it (src/ssw.c:834-836) */
+static void mat_range(const ssw_gpu_params* prm, int32_t* minmat, int32_t* maxmat, int32_t* bias)
+{
+	int32_t lo = 0, hi = 0;
+	for (int64_t i = 0; i < (int64_t)prm->n * prm->n; ++i) { if (prm->mat[i] < lo) lo = prm->mat[i]; if (prm->mat[i] > hi) hi = prm->mat[i]; }
+	*minmat = lo; *maxmat = hi;
+	if (bias) *bias = (prm->score_size == 0 || prm->score_size == 2) ? -lo : 0;
+}
+
+/* the empty record: score 0, no begin positions, no CIGAR (what the reference gives an empty sequence, src/ssw.c:900-903) */
+static void topk_pad(ssw_gpu_result* o) { memset(o, 0, sizeof *o); o->ref_begin1 = -1; o->read_begin1 = -1; o->cigar_off = -1; }
+
+/* Host CIGAR staging pool of a call: every batch of CIGARs that comes off the device is appended here; records name their CIGAR by its
+   word offset in the pool. */
+typedef struct { uint32_t* words; int64_t n, cap; } cigar_stage;
+static int stage_reserve(ssw_gpu_ctx* c, cigar_stage* st, int64_t extra)
+{
+	if (st->n + extra <= st->cap) return 0;
+	const int64_t ncap = (st->n + extra) * 2 + 1024;
+	uint32_t* nw = (uint32_t*)realloc(st->words, sizeof(uint32_t) * (size_t)ncap);
+	if (!nw) return fail(c, "out of host memory (%s)", "CIGAR pool");
+	st->words = nw; st->cap = ncap;
+	return 0;
+}
+/* What a fallback does after a nested call: the nested call's pool (`pool`, `words`; freed here) joins the stage, its m records rec[] go to
+   results[] at the indices idx[0], idx[1], .. (`idx_stride` bytes apart) with cigar_off shifted to the stage */
+static int stage_append_batch(ssw_gpu_ctx* c, cigar_stage* st, uint32_t* pool, int64_t words, const ssw_gpu_result* rec, int64_t m,
+                              const int64_t* idx, size_t idx_stride, ssw_gpu_result* results)
+{
+	if (words > 0) {
+		if (stage_reserve(c, st, words)) { free(pool); return -1; }
+		memcpy(st->words + st->n, pool, sizeof(uint32_t) * (size_t)words);
+	}
+	free(pool);
+	for (int64_t k = 0; k < m; ++k) {
+		ssw_gpu_result r = rec[k];
+		if (r.cigarLen > 0 && r.cigar_off >= 0) r.cigar_off += st->n;
+		results[*(const int64_t*)((const char*)idx + idx_stride * (size_t)k)] = r;
+	}
+	st->n += words;
+	return 0;
+}
+
+/* sums the timing records of the nested calls of one call; the fill kernel named is the one of the nested call with the most cells */
+typedef struct { ssw_gpu_timing t; int64_t best_cells; } call_acc;
+static void timing_add(call_acc* acc, const ssw_gpu_timing* t)
+{
+	ssw_gpu_timing* a = &acc->t;
+	a->fill_ms += t->fill_ms; a->fill_launches += t->fill_launches; a->fill_cells += t->fill_cells; a->cells += t->cells;
+	a->reduce_ms += t->reduce_ms; a->locate_ms += t->locate_ms; a->trace_ms += t->trace_ms; a->n_word += t->n_word; a->n_byte += t->n_byte;
+	a->db_repeats += t->db_repeats; a->fill_pipelined += t->fill_pipelined; a->win_copied += t->win_copied;
+	if (t->fill_cells > acc->best_cells) {
+		acc->best_cells = t->fill_cells;
+		memcpy(a->fill_kernel, t->fill_kernel, sizeof a->fill_kernel);
+		a->fill_ops_per_row = t->fill_ops_per_row; a->fill_rows_per_lane = t->fill_rows_per_lane; a->fill_strips = t->fill_strips;
+	}
+}
+
 /* queries that share a chain geometry: short queries (<= 384 residues) by R = ceil(len/16) rows per lane, one strip;
    longer ones by their padded length P16, cut into `strips` row strips of lanes*R rows (k_chainx; lanes = 64: the
    wavefront is one chain, 16: four chains per wavefront) */
 typedef struct { int32_t R, strips, P16, lanes, use_x; int32_t first_pair, npairs; int32_t first_q, nq; int32_t tailR; /* k_chainq: rows per lane of the last strip (0: R) */ } bucket;
+
+/* Geometry of the strip kernel and its window passes for an alphabet of n letters.  The forward pass of a batch and the reverse pass over
+   flagged survivors (of a database search or of a pair list) must bucket a query length the same way: both take it from here. */
+typedef struct {
+	int32_t xlanes;      /* lanes of a chain of long queries: 64, the wavefront is one chain (16: four chains per wavefront) */
+	int32_t xrmax;       /* most rows per lane of a strip */
+	int32_t xrcap;       /* ... of a strip of the window passes */
+	int32_t rows;        /* rows of one full strip */
+	int no_tail;         /* SSW_GPU_NO_TAIL: equal strips */
+} win_geom;
+static void win_geom_fill(win_geom* g, const ssw_knobs* kn, int32_t n)
+{
+	/* long queries: the wavefront is one chain of 64 lanes; rows per lane bounded so that one profile stays near 24 KiB
+	   of LDS (several waves per CU).  SSW_GPU_XLANES=16 / SSW_GPU_XR=<rows per lane> override (experiments). */
+	g->xlanes = 64; g->xrmax = 4 * (24 / (n + 1) < 1 ? 1 : 24 / (n + 1) > 3 ? 3 : 24 / (n + 1));
+	/* measured on 10-kb DNA reads: fill 1462 / 1514 / 1550 / 1604 / 1568 ms at 12 / 11 / 10 / 9 / 8 rows per lane (9..12 share an LDS
+	   footprint -- three 16-byte profile chunks per lane and residue --, and the more rows a step has, the less its fixed part
+	   weighs; before the record branch was deferred by a step 10 was ahead of 12, profiles/round2_sweep_d_config4_xr*.json vs
+	   round2_sweep_o_config4_xr*.json).  The window passes carry two target rings and more registers; round 2 found them fastest at 8 rows per lane.  Measured again in
+	   round 6 -- since round 4 the reverse pass walks a diagonal band, where every strip pays 2 x band columns beside its own rows, so fewer, taller strips win: config 4's
+	   window passes 138.0 / 112.7 / 101.2 / 86.5 / 85.4 ms at 4 / 6 / 8 / 10 / 12 rows per lane (profiles/round6_experiments.json): 12 */
+	g->xrcap = 12;
+	if (kn->xlanes16) g->xlanes = 16;
+	if (kn->xr) { g->xrmax = kn->xr; g->xrcap = g->xrmax; }
+	if (kn->xr_window) g->xrcap = kn->xr_window;
+	/* the target rings hold profile offsets as 16-bit values: residue n (the null column) x ceil(R/4) KiB must stay below 64 KiB */
+	while (g->xlanes == 64 && g->xrmax > 4 && (int64_t)n * ((g->xrmax + 3) / 4) * 1024 > 65535) g->xrmax -= 4;
+	g->rows = g->xlanes * (g->xlanes == 64 ? g->xrmax : SSW_RMAX);
+	g->no_tail = kn->no_tail;
+}
+/* Bucket key of a query of `len` residues, its padded length in *P16q.  Short queries (<= 384): rows per lane R = ceil(len / 16), all queries
+   of a bucket have the same padded length.  Long queries of ONE strip (up to 64 x 12 rows): SSW_RMAX + 1 + the rows per lane -- queries of
+   DIFFERENT padded lengths share a bucket and its launch (every job of the strip kernel takes its rows from its own queries; rows below a
+   query's padded length are dead for its half), sorted by length so that the two queries of a pair mostly have the same one; longer ones:
+   SSW_RMAX + 64 + the padded length / 16.  One launch per padded length (round 3) made a batch of mixed long reads a series of small,
+   latency-bound launches. */
+static int32_t win_bucket_key(const win_geom* g, int32_t len, int32_t* P16q)
+{
+	const int32_t P = (len + 15) / 16 * 16;
+	*P16q = P;
+	if (len <= 16 * SSW_RMAX) return P / 16;
+	const int32_t st = (P + g->rows - 1) / g->rows, Rq = (P + g->xlanes * st - 1) / (g->xlanes * st);
+	/* (only single-strip queries share a bucket across padded lengths: with several strips the 16-bit-rule column maximum -- rows below
+	   P8 -- is masked in the job's LAST strip only, which both queries of a pair must then end in) */
+	return st == 1 ? SSW_RMAX + 1 + Rq : SSW_RMAX + 64 + P / 16;
+}
+/* the strip shape of the bucket `key` whose longest query has the padded length P16 */
+static void win_bucket_shape(bucket* b, const win_geom* g, int32_t key, int32_t P16)
+{
+	b->tailR = 0;
+	if (key <= SSW_RMAX) { b->R = key; b->strips = 1; b->P16 = 16 * key; b->lanes = 16; b->use_x = 0; return; }
+	b->P16 = P16; b->lanes = g->xlanes; b->use_x = 1;
+	b->strips = (P16 + g->rows - 1) / g->rows;
+	b->R = (P16 + b->lanes * b->strips - 1) / (b->lanes * b->strips);        /* balanced strips */
+	/* ... unless full strips and a SHORT last one (1, 2 or 4 rows per lane) compute fewer rows: 10 000 rows are 13 strips of 768 and one
+	   of 64 (10 048 rows) instead of 14 of 768 (10 752).  The last strip pays a step's fixed part (boundary records, hand-offs) again,
+	   which is what a strip of 12 rows per lane pays too. */
+	if (b->lanes == 64 && b->strips > 1 && g->xrmax > 4 && !g->no_tail) {
+		const int32_t rem = P16 - (b->strips - 1) * 64 * g->xrmax, need = (rem + 63) / 64, tr = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 0;
+		if (rem > 0 && tr > 0 && g->xrmax * (b->strips - 1) + tr < b->R * b->strips) { b->R = g->xrmax; b->tailR = tr; }
+	}
+}
+
 /* tile geometry and scratch of one bucket against the current target (planned before anything is launched: buckets whose launches all
    fit the budget together run side by side on the side streams, each in its own slice of the scratch buffers) */
 typedef struct {
@@ -670,9 +831,9 @@ typedef struct {
 	const int32_t* order; int32_t nqa;     /* non-empty queries in bucket order (host), and ... */
 	const int32_t* d_order;                /* ... on the device */
 	int32_t maxlen, maxmat, minmat, maxt;
-	int32_t xlanes, xrmax, xrcap;
+	win_geom g;
 	int fill_form;
-	uint32_t** pool; int64_t* pool_words; int64_t* pool_cap;      /* the call's host CIGAR pool */
+	cigar_stage* stage;                    /* the call's host CIGAR pool */
 	double locate_ms, trace_ms;
 	int64_t survivors;
 	/* survivors of the current chunk, on the host after dbx_chunk */
@@ -738,8 +899,8 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 	/* column-frame form of the recurrence wherever a size class's scores leave room for the frame offsets below 31744 (always, for the
 	   matrices and lengths this path admits with sane gap penalties); SSW_GPU_DB_FORM=0 (tests) keeps the plain int16 form */
 	const int use_fr = !c->kn.db_plain;
-	int32_t db_minmat = 0, db_maxmat = 0;
-	for (int32_t i = 0; i < n * n; ++i) { if (prm->mat[i] < db_minmat) db_minmat = prm->mat[i]; if (prm->mat[i] > db_maxmat) db_maxmat = prm->mat[i]; }
+	int32_t db_minmat, db_maxmat;
+	mat_range(prm, &db_minmat, &db_maxmat, 0);
 	int db_form[64]; memset(db_form, 0, sizeof db_form);
 	if (!d_tl_all || (ds && (!d_cnt_s || ssw_shim_memset(d_cnt_s, 0, DB_COUNTERS * sizeof(int32_t), c->stream)))) { fail(c, "device allocation failed: %s", ssw_shim_last_error()); goto done; }
 	int32_t prev_t0 = -1, prev_nt = 0, chunk_i = 0;
@@ -964,7 +1125,7 @@ done:
 /* ------------------------------------------------------------------------------------------------
  * Window passes of one geometry bucket over the jobs in d_list[0 .. cnt): pass 0 locates read_end1 where the fill did not track it
  * (reference src/ssw.c:342-351), pass 1 is the reverse pass that finds the begin position (ssw_align 919-935).  Used by the
- * per-target path (jobs = queries against d_tgt) and by the flagged database search (jobs = survivor pairs, vm set).
+ * per-target path (jobs = queries against d_tgt) and by the flagged survivors' phases (survivor_phases: jobs = survivor pairs, vm set).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
 	const ssw_gpu_seqs* Q; const ssw_gpu_params* prm;
@@ -973,7 +1134,7 @@ typedef struct {
 	const int8_t* d_mat; int32_t n, maxmat, minmat;
 	int fill_form;
 	ssw_dres* d_res;
-	int32_t xlanes, xrmax, xrcap;
+	win_geom g;
 } win_in;
 
 /* short-query buckets whose four per-chain profiles would not fit the LDS of a workgroup (alphabets near 32 symbols with many rows per
@@ -989,9 +1150,9 @@ static int window_pass(ssw_gpu_ctx* c, const win_in* wi, const bucket* B, int pa
 	const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
 	if (cnt <= 0) return 0;
 	const int cap_x = window_on_strips(B, n);
-	const int32_t capRmax = wi->xrcap < wi->xrmax ? wi->xrcap : wi->xrmax;
+	const int32_t capRmax = wi->g.xrcap < wi->g.xrmax ? wi->g.xrcap : wi->g.xrmax;
 	const int32_t capR = B->use_x ? (B->lanes == 64 && B->R > capRmax ? capRmax : B->R) : ((B->P16 + 63) / 64 < capRmax ? (B->P16 + 63) / 64 : capRmax),
-	              capL = B->use_x ? B->lanes : wi->xlanes;
+	              capL = B->use_x ? B->lanes : wi->g.xlanes;
 	if (cap_x) {
 		const int32_t hw = halo_for(B->P16, maxmat, prm->gapE);
 		const int64_t wcols = (((int64_t)(hw < refLen ? hw : refLen) + 1) + 31) / 16 * 16;
@@ -1047,7 +1208,7 @@ static int window_pass(ssw_gpu_ctx* c, const win_in* wi, const bucket* B, int pa
 /* ------------------------------------------------------------------------------------------------
  * Traceback phase (banded_sw + re-score + band retry, reference src/ssw.c:941-973) over the records d_res[0 .. nslots): the ids in
  * `ids` are offered to the kernels (which skip records without want_cigar), CIGAR slots / resume state are indexed by id.
- * Used by the per-target path (ids = queries against d_tgt) and by the flagged database search (ids = survivor pairs, vm set).
+ * Used by the per-target path (ids = queries against d_tgt) and by the flagged survivors' phases (survivor_phases: ids = survivor pairs, vm set).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
 	const ssw_gpu_seqs* Q; const ssw_gpu_params* prm;
@@ -1395,6 +1556,97 @@ static int trace_phase(ssw_gpu_ctx* c, const trace_in* ti, trace_out* to)
 	return 0;
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * The phases of flagged survivors: (query, target) pairs whose forward pass is done and passed the reference's gate (src/ssw.c:916), as
+ * ssw_dres records on the device.  One batched reverse pass per geometry bucket (begin positions; read_end1 came with the forward
+ * pass), then the traceback over slabs of survivors (a slab = the CIGAR slots that fit half the budget), the completed records to the
+ * host and the CIGARs into the call's staging pool.  Used by the flagged database search (dbx_chunk: survivors compacted by k_select)
+ * and by the flagged pair lists (pairs_flagged: survivors chosen on the host).  The caller records c->ev_a on the main stream where its
+ * locate phase begins (before its own selection / upload).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct { bucket b; int64_t first, count; } surv_range;      /* survivors [first, first + count) share the bucket b */
+typedef struct {
+	const ssw_gpu_seqs* Q; const ssw_gpu_seqs* T; const ssw_gpu_params* prm;
+	const int8_t* d_mat; int32_t maxmat, minmat;
+	const win_geom* g; int fill_form;
+	int32_t maxlen; int64_t maxt;          /* longest query, longest target (window) among the survivors */
+	ssw_dres* d_sres; int64_t ns;          /* the survivors' records, ordered by bucket */
+	int32_t* d_maps;                       /* four arrays of ns ints: query and target of every survivor (ssw_vmap), the identity list, scratch for the traceback's job lists */
+	const ssw_win* d_win;                  /* targets are windows: the device window table (else NULL) */
+	const surv_range* rg; int nrg;
+	int check_queue;                       /* look at the work queue's error word before returning (chainq_check: one more download and synchronisation) */
+} surv_in;
+/* hs[0 .. ns): the completed records; pool_off[v]: where survivor v's CIGAR starts in the staging pool (meaningful when it has one) */
+static int survivor_phases(ssw_gpu_ctx* c, const surv_in* si, ssw_dres* hs, cigar_stage* st, int64_t* pool_off, double* locate_ms, double* trace_ms)
+{
+	const ssw_gpu_seqs* Q = si->Q; const ssw_gpu_seqs* T = si->T; const ssw_gpu_params* prm = si->prm;
+	const int64_t ns = si->ns;
+	int32_t* const d_vq = si->d_maps; int32_t* const d_vt = si->d_maps + ns; int32_t* const d_vl = si->d_maps + 2 * (size_t)ns; int32_t* const d_tl = si->d_maps + 3 * (size_t)ns;
+	ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off; vm.win = si->d_win;
+	int32_t* ids = 0; int32_t* hneed = 0; int64_t* goffs = 0;
+	int rc = -1;
+	/* ---- reverse pass (begin positions), one launch per geometry bucket that has survivors */
+	win_in wi; memset(&wi, 0, sizeof wi);
+	wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = (int32_t)si->maxt; wi.d_mat = si->d_mat; wi.n = prm->n; wi.maxmat = si->maxmat; wi.minmat = si->minmat;
+	wi.fill_form = si->fill_form; wi.g = *si->g;
+	for (int b = 0; b < si->nrg; ++b) {
+		const int64_t f0 = si->rg[b].first;
+		if (si->rg[b].count <= 0) continue;
+		wi.d_res = si->d_sres + f0; wi.vm = vm; wi.vm.vq = d_vq + f0; wi.vm.vt = d_vt + f0;
+		if (window_pass(c, &wi, &si->rg[b].b, 1, d_vl, (int32_t)si->rg[b].count, 0)) goto out;
+	}
+	ssw_shim_event_record(c->ev_b, c->stream);
+	/* ---- traceback over slabs of survivors, CIGARs into the host pool */
+	const int32_t halo_max = halo_for((si->maxlen + 15) / 16 * 16, si->maxmat, prm->gapE);
+	const int64_t ref_span = halo_max < si->maxt ? halo_max : si->maxt;
+	const int64_t slot_bytes = 8 * ((int64_t)si->maxlen + ref_span + 16) + 4 * (int64_t)si->maxlen + 256;
+	int64_t slab = (int64_t)(c->cm_budget / 2) / slot_bytes;
+	if (slab < 1024) slab = 1024;
+	if (c->kn.dbx_slab) slab = c->kn.dbx_slab;
+	const int64_t sl = ns < slab ? ns : slab;
+	ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)sl);
+	if (!ids || !hneed || !goffs) { fail(c, "out of host memory%s", ""); goto out; }
+	for (int64_t s0 = 0; s0 < ns; s0 += slab) {
+		const int32_t cnt = (int32_t)(ns - s0 < slab ? ns - s0 : slab);
+		trace_out tro; memset(&tro, 0, sizeof tro);
+		if ((prm->flag & 7) != 0) {
+			for (int32_t k = 0; k < cnt; ++k) ids[k] = k;
+			trace_in tri; memset(&tri, 0, sizeof tri);
+			tri.Q = Q; tri.prm = prm; tri.d_tgt = T->d_codes; tri.vm = vm; tri.vm.vq = d_vq + s0; tri.vm.vt = d_vt + s0; tri.d_mat = si->d_mat; tri.n = prm->n;
+			tri.d_res = si->d_sres + s0; tri.nslots = cnt; tri.ids = ids; tri.nids = cnt; tri.d_list = d_tl; tri.hneed = hneed; tri.maxlen = si->maxlen; tri.ref_span = ref_span;
+			if (trace_phase(c, &tri, &tro)) goto out;
+		}
+		if (ssw_shim_d2h(hs + s0, si->d_sres + s0, sizeof(ssw_dres) * (size_t)cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto out; }
+		int64_t gwords = 0;
+		for (int32_t k = 0; k < cnt; ++k) {
+			const ssw_dres* r = &hs[s0 + k];
+			if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); goto out; }
+			goffs[k] = gwords; pool_off[s0 + k] = st->n + gwords;
+			if (r->cigarLen > 0 && r->status == 0) gwords += r->cigarLen;
+		}
+		if (gwords > 0) {
+			int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
+			uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
+			if (!d_goff || !d_gpool || stage_reserve(c, st, gwords)) goto out;
+			ssw_gather_args ga; ga.src = tro.d_cig; ga.res = si->d_sres + s0; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
+			if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
+			    ssw_shim_d2h(st->words + st->n, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream) || ssw_shim_stream_sync(c->stream)) {
+				fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); goto out;
+			}
+			st->n += gwords;
+		}
+	}
+	ssw_shim_event_record(c->ev_c, c->stream);
+	if (ssw_shim_stream_sync(c->stream)) { fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto out; }
+	if (si->check_queue && chainq_check(c)) goto out;
+	*locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+	*trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
+	rc = 0;
+out:
+	free(ids); free(hneed); free(goffs);
+	return rc;
+}
+
 static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm, const bucket* bk, int nb,
                      const int8_t* d_mat, struct ssw_out_rec* d_out, int32_t tbase, int32_t nt)
 {
@@ -1415,6 +1667,7 @@ static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const
 	for (int b = 0; b < nb; ++b) hlin[b] = (int64_t)bk[b].first_q * nt;
 	hlin[nb] = npairs;
 	int rc = -1;
+	surv_range* rg = 0;
 	ssw_select_args sa; memset(&sa, 0, sizeof sa);
 	sa.out = d_out; sa.order = dx->d_order; sa.nk = nk; sa.nt = nt; sa.tbase = tbase; sa.flag = prm->flag; sa.filters = prm->filters;
 	sa.blk = d_cnt; sa.nblk = nblk; sa.bucket_lin = d_lin; sa.nbk = nb; sa.bucket_first = d_first;
@@ -1431,7 +1684,7 @@ static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const
 		ssw_dres* d_sres = (ssw_dres*)ensure(c, &c->sres, sizeof(ssw_dres) * (size_t)(ns > 0 ? ns : 1));
 		int32_t* d_maps = (int32_t*)ensure(c, &c->svq, sizeof(int32_t) * 4 * (size_t)(ns > 0 ? ns : 1));      /* vq, vt, identity list, traceback job lists */
 		if (!d_sres || !d_maps) goto out;
-		int32_t* d_vq = d_maps; int32_t* d_vt = d_maps + ns; int32_t* d_vl = d_maps + 2 * (size_t)ns; int32_t* d_tl = d_maps + 3 * (size_t)ns;
+		int32_t* d_vq = d_maps; int32_t* d_vt = d_maps + ns; int32_t* d_vl = d_maps + 2 * (size_t)ns;
 		sa.pass = 2; sa.sres = d_sres; sa.svq = d_vq; sa.svt = d_vt; sa.vlist = d_vl; sa.cap = ns;
 		if (ssw_shim_launch_select(&sa, c->stream) || ssw_shim_d2h(hfirst, d_first, sizeof(int32_t) * ((size_t)nb + 1), c->stream) || ssw_shim_stream_sync(c->stream)) {
 			fail(c, "select launch failed: %s", ssw_shim_last_error()); goto out;
@@ -1449,99 +1702,23 @@ static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const
 			dx->hvt = (int32_t*)malloc(sizeof(int32_t) * dx->hcap); dx->hpo = (int64_t*)malloc(sizeof(int64_t) * dx->hcap);
 			if (!dx->hs || !dx->hvq || !dx->hvt || !dx->hpo) { dx->hcap = 0; fail(c, "out of host memory%s", ""); goto out; }
 		}
-		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off; vm.win = 0;
-		/* ---- reverse pass (begin positions), one launch per geometry bucket that has survivors; read_end1 came with the search */
-		win_in wi; memset(&wi, 0, sizeof wi);
-		wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = dx->maxt; wi.d_mat = d_mat; wi.n = prm->n; wi.maxmat = dx->maxmat; wi.minmat = dx->minmat;
-		wi.fill_form = dx->fill_form; wi.xlanes = dx->xlanes; wi.xrmax = dx->xrmax; wi.xrcap = dx->xrcap;
-		for (int b = 0; b < nb; ++b) {
-			const int32_t f0 = hfirst[b], cntb = hfirst[b + 1] - hfirst[b];
-			if (cntb <= 0) continue;
-			wi.d_res = d_sres + f0; wi.vm = vm; wi.vm.vq = d_vq + f0; wi.vm.vt = d_vt + f0;
-			if (window_pass(c, &wi, &bk[b], 1, d_vl, cntb, 0)) goto out;
-		}
-		ssw_shim_event_record(c->ev_b, c->stream);
-		/* ---- traceback over slabs of survivors (a slab = the CIGAR slots that fit half the budget), CIGARs into the host pool */
+		/* (the survivors' maps for the caller: complete with the first synchronisation of the phases) */
 		if (ssw_shim_d2h(dx->hvq, d_vq, sizeof(int32_t) * (size_t)ns, c->stream) || ssw_shim_d2h(dx->hvt, d_vt, sizeof(int32_t) * (size_t)ns, c->stream)) {
 			fail(c, "download failed: %s", ssw_shim_last_error()); goto out;
 		}
-		const int32_t halo_max = halo_for((dx->maxlen + 15) / 16 * 16, dx->maxmat, prm->gapE);
-		const int64_t ref_span = halo_max < dx->maxt ? halo_max : dx->maxt;
-		const int64_t slot_bytes = 8 * ((int64_t)dx->maxlen + ref_span + 16) + 4 * (int64_t)dx->maxlen + 256;
-		int64_t slab = (int64_t)(c->cm_budget / 2) / slot_bytes;
-		if (slab < 1024) slab = 1024;
-		if (c->kn.dbx_slab) slab = c->kn.dbx_slab;
-		int32_t* ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)(ns < slab ? ns : slab));
-		int32_t* hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)(ns < slab ? ns : slab));
-		int64_t* goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)(ns < slab ? ns : slab));
-		int ok = ids && hneed && goffs;
-		if (!ok) fail(c, "out of host memory%s", "");
-		for (int32_t s0 = 0; ok && s0 < ns; s0 += (int32_t)slab) {
-			const int32_t cnt = ns - s0 < slab ? ns - s0 : (int32_t)slab;
-			trace_out tro; memset(&tro, 0, sizeof tro);
-			if ((prm->flag & 7) != 0) {
-				for (int32_t k = 0; k < cnt; ++k) ids[k] = k;
-				trace_in tri; memset(&tri, 0, sizeof tri);
-				tri.Q = Q; tri.prm = prm; tri.d_tgt = T->d_codes; tri.vm = vm; tri.vm.vq = d_vq + s0; tri.vm.vt = d_vt + s0; tri.d_mat = d_mat; tri.n = prm->n;
-				tri.d_res = d_sres + s0; tri.nslots = cnt; tri.ids = ids; tri.nids = cnt; tri.d_list = d_tl; tri.hneed = hneed; tri.maxlen = dx->maxlen; tri.ref_span = ref_span;
-				if (trace_phase(c, &tri, &tro)) { ok = 0; break; }
-			}
-			if (ssw_shim_d2h(dx->hs + s0, d_sres + s0, sizeof(ssw_dres) * (size_t)cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); ok = 0; break; }
-			int64_t gwords = 0;
-			for (int32_t k = 0; k < cnt; ++k) {
-				const ssw_dres* r = &dx->hs[s0 + k];
-				if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); ok = 0; break; }
-				goffs[k] = gwords; dx->hpo[s0 + k] = *dx->pool_words + gwords;
-				if (r->cigarLen > 0 && r->status == 0) gwords += r->cigarLen;
-			}
-			if (!ok) break;
-			if (gwords > 0) {
-				int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
-				uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
-				if (!d_goff || !d_gpool) { ok = 0; break; }
-				if (*dx->pool_words + gwords > *dx->pool_cap) {
-					*dx->pool_cap = (*dx->pool_words + gwords) * 2 + 1024;
-					uint32_t* npool = (uint32_t*)realloc(*dx->pool, sizeof(uint32_t) * (size_t)*dx->pool_cap);
-					if (!npool) { fail(c, "out of host memory (%s)", "CIGAR pool"); ok = 0; break; }
-					*dx->pool = npool;
-				}
-				ssw_gather_args ga; ga.src = tro.d_cig; ga.res = d_sres + s0; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
-				if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
-				    ssw_shim_d2h(*dx->pool + *dx->pool_words, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream) || ssw_shim_stream_sync(c->stream)) {
-					fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); ok = 0; break;
-				}
-				*dx->pool_words += gwords;
-			}
-		}
-		free(ids); free(hneed); free(goffs);
-		if (!ok) goto out;
-		ssw_shim_event_record(c->ev_c, c->stream);
-		if (ssw_shim_stream_sync(c->stream)) { fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto out; }
-		dx->locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
-		dx->trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
+		rg = (surv_range*)malloc(sizeof(surv_range) * (size_t)nb);
+		if (!rg) { fail(c, "out of host memory%s", ""); goto out; }
+		for (int b = 0; b < nb; ++b) { rg[b].b = bk[b]; rg[b].first = hfirst[b]; rg[b].count = hfirst[b + 1] - hfirst[b]; }
+		surv_in si; memset(&si, 0, sizeof si);
+		si.Q = Q; si.T = T; si.prm = prm; si.d_mat = d_mat; si.maxmat = dx->maxmat; si.minmat = dx->minmat; si.g = &dx->g; si.fill_form = dx->fill_form;
+		si.maxlen = dx->maxlen; si.maxt = dx->maxt; si.d_sres = d_sres; si.d_maps = d_maps; si.ns = ns; si.d_win = 0; si.rg = rg; si.nrg = nb;
+		si.check_queue = 0;      /* (this path has never looked at the work queue's error word itself: the context's next chainq_check does) */
+		if (survivor_phases(c, &si, dx->hs, dx->stage, dx->hpo, &dx->locate_ms, &dx->trace_ms)) goto out;
 		dx->ns = ns;
 	}
 	rc = 0;
 out:
-	free(hlin); free(hfirst);
-	return rc;
-}
-
-static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
-                              const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds);
-
-int ssw_gpu_align_batch(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
-                        const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
-{
-	if (!c) return fail(0, "align_batch: NULL context%s", "");
-	/* the context's streams, events and workspaces serve one call at a time (include/ssw_gpu.h "Threads") */
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
-		if (cigar_pool) *cigar_pool = 0;
-		if (cigar_words) *cigar_words = 0;
-		return SSW_GPU_BUSY;      /* another thread is inside this context (its error text is the running call's: left alone; ssw_gpu_strerror names the code) */
-	}
-	const int rc = align_batch_locked(c, Q, T, tfirst, tcount, prm, results, cigar_pool, cigar_words, 0);
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
+	free(hlin); free(hfirst); free(rg);
 	return rc;
 }
 
@@ -1550,11 +1727,10 @@ int ssw_gpu_align_batch(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seq
 static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
                               const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds)
 {
-	if (!Q || !T || !prm || (!results && !ds) || !prm->mat) return fail(c, "align_batch: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "align_batch: sequences belong to another context%s", "");
+	if (!results && !ds) return fail(c, "align_batch: NULL argument%s", "");
+	if (check_seqs(c, "align_batch", Q, T, prm)) return -1;
 	if (tfirst < 0 || tcount < 0 || tfirst + tcount > T->count) return fail(c, "align_batch: target range out of bounds%s", "");
-	if (prm->n < 1) return fail(c, "align_batch: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_batch: score_size must be 0, 1 or 2%s", "");
+	if (check_scoring(c, "align_batch", prm)) return -1;
 	/* Alphabets.  The reference takes any int32 n (src/ssw.h:86, ssw.c:826-847).  Up to 32 letters the per-residue score profile of a query
 	   lives in LDS (the profile kernels); 33 .. 128 letters -- every value an int8 code can take -- run on the lane-model kernel, which looks
 	   its scores up in the MATRIX (n x n bytes of LDS) and is exact in every gap regime, and on the thread traceback, which reads the matrix
@@ -1571,10 +1747,8 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	const int32_t nq = Q->count, n = prm->n > SSW_MAX_N_WIDE ? SSW_MAX_N_WIDE : prm->n;
 	if (nq == 0 || tcount == 0) return 0;
 
-	int32_t bias = 0, maxmat = 0;
-	for (int64_t i = 0; i < (int64_t)prm->n * prm->n; ++i) { if (prm->mat[i] < bias) bias = prm->mat[i]; if (prm->mat[i] > maxmat) maxmat = prm->mat[i]; }
-	const int32_t minmat = bias;      /* <= 0 */
-	bias = (prm->score_size == 0 || prm->score_size == 2) ? -bias : 0;
+	int32_t minmat, maxmat, bias;
+	mat_range(prm, &minmat, &maxmat, &bias);
 
 	/* bucket the queries by chain geometry, pair neighbours inside a bucket.  Empty queries take no part: the reference gives
 	   them the empty record (score 0, begins -1; src/ssw.c:900-903), which is what an untouched result record reads as. */
@@ -1599,46 +1773,15 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	}
 	if (nqa == 0 && ds) { free(order); free(pairs); free(keys); free(qdone); return SSW_NOT_STREAMABLE; }
 	if (nqa == 0) {     /* nothing but empty queries */
-		for (int64_t k = 0; k < (int64_t)nq * tcount; ++k) {
-			ssw_gpu_result* o = &results[k];
-			memset(o, 0, sizeof *o); o->ref_begin1 = -1; o->read_begin1 = -1; o->cigar_off = -1;
-		}
+		for (int64_t k = 0; k < (int64_t)nq * tcount; ++k) topk_pad(&results[k]);
 		memset(&c->tm, 0, sizeof c->tm);
 		free(order); free(pairs); free(keys); free(qdone);
 		return 0;
 	}
-	/* long queries: the wavefront is one chain of 64 lanes; rows per lane bounded so that one profile stays near 24 KiB
-	   of LDS (several waves per CU).  SSW_GPU_XLANES=16 / SSW_GPU_XR=<rows per lane> override (experiments). */
-	int32_t xlanes = 64, xrmax = 4 * (24 / (n + 1) < 1 ? 1 : 24 / (n + 1) > 3 ? 3 : 24 / (n + 1));
-	/* measured on 10-kb DNA reads: fill 1462 / 1514 / 1550 / 1604 / 1568 ms at 12 / 11 / 10 / 9 / 8 rows per lane (9..12 share an LDS
-	   footprint -- three 16-byte profile chunks per lane and residue --, and the more rows a step has, the less its fixed part
-	   weighs; before the record branch was deferred by a step 10 was ahead of 12, profiles/round2_sweep_d_config4_xr*.json vs
-	   round2_sweep_o_config4_xr*.json).  The window passes carry two target rings and more registers; round 2 found them fastest at 8 rows per lane.  Measured again in
-	   round 6 -- since round 4 the reverse pass walks a diagonal band, where every strip pays 2 x band columns beside its own rows, so fewer, taller strips win: config 4's
-	   window passes 138.0 / 112.7 / 101.2 / 86.5 / 85.4 ms at 4 / 6 / 8 / 10 / 12 rows per lane (profiles/round6_experiments.json): 12 */
-	int32_t xrcap = 12;
-	{
-		if (c->kn.xlanes16) xlanes = 16;
-		if (c->kn.xr) { xrmax = c->kn.xr; xrcap = xrmax; }
-		if (c->kn.xr_window) xrcap = c->kn.xr_window;
-		/* the target rings hold profile offsets as 16-bit values: residue n (the null column) x ceil(R/4) KiB must stay below 64 KiB */
-		while (xlanes == 64 && xrmax > 4 && (int64_t)n * ((xrmax + 3) / 4) * 1024 > 65535) xrmax -= 4;
-	}
-	/* Bucket keys.  Short queries (<= 384): rows per lane R = ceil(len / 16), all queries of a bucket have the same padded length.  Long
-	   queries of ONE strip (up to 64 x 12 rows): the rows per lane -- queries of DIFFERENT padded lengths share a bucket and its launch (every
-	   job of the strip kernel takes its rows from its own queries; rows below a query's padded length are dead for its half), sorted by
-	   length so that the two queries of a pair mostly have the same one; longer ones: the padded length as before.  One launch per padded length (round 3) made a
-	   batch of mixed long reads a series of small, latency-bound launches. */
-	for (int32_t k = 0; k < nqa; ++k) {
-		const int32_t len = keys[k].key, P16q = (len + 15) / 16 * 16;
-		if (len <= 16 * SSW_RMAX) { keys[k].key = P16q / 16; keys[k].sub = 0; }
-		else {
-			const int32_t rows = xlanes * (xlanes == 64 ? xrmax : SSW_RMAX), st = (P16q + rows - 1) / rows, Rq = (P16q + xlanes * st - 1) / (xlanes * st);
-			/* (only single-strip queries share a bucket across padded lengths: with several strips the 16-bit-rule column maximum -- rows below
-			   P8 -- is masked in the job's LAST strip only, which both queries of a pair must then end in) */
-			keys[k].key = st == 1 ? SSW_RMAX + 1 + Rq : SSW_RMAX + 64 + P16q / 16; keys[k].sub = P16q;
-		}
-	}
+	/* bucket keys (the strip geometry decides them: win_bucket_key) */
+	win_geom geom;
+	win_geom_fill(&geom, &c->kn, n);
+	for (int32_t k = 0; k < nqa; ++k) keys[k].key = win_bucket_key(&geom, keys[k].key, &keys[k].sub);
 	qsort(keys, (size_t)nqa, sizeof(keyed), keyed_cmp);
 	for (int32_t i = 0; i < nqa; ) {
 		int32_t j = i;
@@ -1646,22 +1789,8 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		bucket* nbk = (bucket*)realloc(bk, sizeof(bucket) * (size_t)(nb + 1));
 		if (!nbk) { free(bk); free(order); free(pairs); free(keys); free(qdone); return fail(c, "out of host memory%s", ""); }
 		bk = nbk;
-		bucket b; b.tailR = 0;
-		if (keys[i].key <= SSW_RMAX) { b.R = keys[i].key; b.strips = 1; b.P16 = 16 * b.R; b.lanes = 16; b.use_x = 0; }
-		else {
-			b.P16 = keys[j - 1].sub;       /* the longest of the bucket (sorted by padded length) */
-			b.lanes = xlanes; b.use_x = 1;
-			const int32_t rows = b.lanes * (b.lanes == 64 ? xrmax : SSW_RMAX);
-			b.strips = (b.P16 + rows - 1) / rows;
-			b.R = (b.P16 + b.lanes * b.strips - 1) / (b.lanes * b.strips);        /* balanced strips */
-			/* ... unless full strips and a SHORT last one (1, 2 or 4 rows per lane) compute fewer rows: 10 000 rows are 13 strips of 768 and one
-			   of 64 (10 048 rows) instead of 14 of 768 (10 752).  The last strip pays a step's fixed part (boundary records, hand-offs) again,
-			   which is what a strip of 12 rows per lane pays too. */
-			if (b.lanes == 64 && b.strips > 1 && xrmax > 4 && !c->kn.no_tail) {
-				const int32_t rem = b.P16 - (b.strips - 1) * 64 * xrmax, need = (rem + 63) / 64, tr = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 0;
-				if (rem > 0 && tr > 0 && xrmax * (b.strips - 1) + tr < b.R * b.strips) { b.R = xrmax; b.tailR = tr; }
-			}
-		}
+		bucket b;
+		win_bucket_shape(&b, &geom, keys[i].key, keys[j - 1].sub);       /* (sorted by padded length: the last is the longest of the bucket) */
 		b.first_q = i; b.nq = j - i; b.first_pair = npairs_total;
 		for (int32_t k = i; k < j; ++k) order[k] = keys[k].q;
 		for (int32_t k = i; k < j; k += 2) {
@@ -1681,7 +1810,7 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	struct fill_defer { ssw_fill_args fa; int R, group; int64_t wgs; } *defer = 0;      /* short-query buckets that join a multi-bucket grid */
 	ssw_reduce_args* rdefer = 0;                                                          /* ... and the reductions of all buckets of a side-by-side group */
 	int* border = (int*)malloc(sizeof(int) * (size_t)(nb > 0 ? nb : 1));      /* buckets by size (side-by-side launches go largest first) */
-	uint32_t* pool = 0; int64_t pool_words = 0, pool_cap = 0;
+	cigar_stage pool; memset(&pool, 0, sizeof pool);
 	ssw_dres* hres = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)nq);
 	int32_t* hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
 	memset(&c->tm, 0, sizeof c->tm);
@@ -1718,7 +1847,7 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		for (int32_t ti = 0; ti < tcount; ++ti) { int64_t L = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti]; if (L > maxt) maxt = L; }
 		/* (k_filldb takes the column maximum of two rows with a 16-bit float max3, valid below 31744: 640 rows x max(mat) <= 49) */
 		/* flagged batches (begin positions / CIGARs) against several targets: the same fused search + one batched reverse pass and traceback
-		   over the pairs that pass the score filter (dbx_chunk).  The bound on the target set dates from the window kernels' 32-bit column
+		   over the pairs that pass the score filter (dbx_chunk, survivor_phases).  The bound on the target set dates from the window kernels' 32-bit column
 		   indices into the concatenated targets; they take a 64-bit base per job now (the pair lists run above 2^31 residues), but this path has
 		   not been run there, so the bound stays */
 		const int use_dbx = prm->flag != 0 && !ds && !c->kn.no_dbx && tcount >= 4 && T->total < 0x7fff0000;
@@ -1726,8 +1855,7 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		dbx_state dxs; memset(&dxs, 0, sizeof dxs);
 		if (use_dbx) {
 			dxs.order = order; dxs.nqa = nqa; dxs.d_order = d_qlist; dxs.maxmat = maxmat; dxs.minmat = minmat; dxs.maxt = (int32_t)(maxt > 0x7fffffff ? 0x7fffffff : maxt);
-			dxs.xlanes = xlanes; dxs.xrmax = xrmax; dxs.xrcap = xrcap; dxs.fill_form = fill_form;
-			dxs.pool = &pool; dxs.pool_words = &pool_words; dxs.pool_cap = &pool_cap;
+			dxs.g = geom; dxs.fill_form = fill_form; dxs.stage = &pool;
 		}
 		if (ds && (!db_ok || any_long)) { rc = SSW_NOT_STREAMABLE; goto done; }
 		if (db_ok && (tcount >= 4 || ds)) {
@@ -1754,8 +1882,8 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 				c->tm.total_ms = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_d); c->tm.fill_ms = fill_ms;
 				c->tm.locate_ms = dxs.locate_ms; c->tm.trace_ms = dxs.trace_ms;
 				c->tm.reduce_ms = c->tm.total_ms - fill_ms - dxs.locate_ms - dxs.trace_ms; if (c->tm.reduce_ms < 0) c->tm.reduce_ms = 0;
-				if (cigar_pool) { *cigar_pool = pool; pool = 0; }
-				if (cigar_words) *cigar_words = pool_words;
+				if (cigar_pool) { *cigar_pool = pool.words; pool.words = 0; }
+				if (cigar_words) *cigar_words = pool.n;
 				rc = 0;
 				goto done;
 			}
@@ -2196,7 +2324,7 @@ plan_again:
 		if (refLen > 0 && !literal) {   /* read_end1 always (ssw.c:342-351); begin position only when asked for (ssw.c:916) */
 			win_in wi; memset(&wi, 0, sizeof wi);
 			wi.Q = Q; wi.prm = prm; wi.d_tgt = d_tgt; wi.refLen = refLen; wi.d_mat = d_mat; wi.n = n; wi.maxmat = maxmat; wi.minmat = minmat;
-			wi.fill_form = fill_form; wi.d_res = d_res; wi.xlanes = xlanes; wi.xrmax = xrmax; wi.xrcap = xrcap;
+			wi.fill_form = fill_form; wi.d_res = d_res; wi.g = geom;
 			/* a batch of many buckets: the k_capture launches (one small, latency-bound grid per bucket) side by side -- a bucket keeps its
 			   side stream for both passes (the reverse pass reads what the locate pass wrote) */
 			int nwin = 0, wused[SSW_TSTREAMS];
@@ -2264,23 +2392,17 @@ plan_again:
 			for (int32_t q = 0; q < nq; ++q) { goffs[q] = at; if (hres[q].cigarLen > 0 && hres[q].status == 0) at += hres[q].cigarLen; }
 			int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)nq);
 			uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
-			if (!d_goff || !d_gpool) { free(goffs); goto done; }
-			if (pool_words + gwords > pool_cap) {
-				pool_cap = (pool_words + gwords) * 2 + 1024;
-				uint32_t* npool = (uint32_t*)realloc(pool, sizeof(uint32_t) * (size_t)pool_cap);
-				if (!npool) { fail(c, "out of host memory (%s)", "CIGAR pool"); free(goffs); goto done; }
-				pool = npool;
-			}
+			if (!d_goff || !d_gpool || stage_reserve(c, &pool, gwords)) { free(goffs); goto done; }
 			if (nq <= 4) {      /* a handful of alignments: every CIGAR straight from its slot (no offset upload, no gather launch) */
 				for (int32_t q = 0; q < nq; ++q)
 					if (hres[q].cigarLen > 0 && hres[q].status == 0 &&
-					    ssw_shim_d2h(pool + pool_words + goffs[q], d_cig + hres[q].cigar_off, sizeof(uint32_t) * (size_t)hres[q].cigarLen, c->stream)) {
+					    ssw_shim_d2h(pool.words + pool.n + goffs[q], d_cig + hres[q].cigar_off, sizeof(uint32_t) * (size_t)hres[q].cigarLen, c->stream)) {
 						fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); free(goffs); goto done;
 					}
 			} else {
 			ssw_gather_args ga; ga.src = d_cig; ga.res = d_res; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = nq;
 			if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)nq, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
-			    ssw_shim_d2h(pool + pool_words, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream)) {
+			    ssw_shim_d2h(pool.words + pool.n, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream)) {
 				fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); free(goffs); goto done;
 			}
 			}
@@ -2295,11 +2417,11 @@ plan_again:
 			o->ref_end2 = r->ref_end2; o->cigarLen = r->cigarLen; o->cigar_off = -1; o->flag = (uint16_t)r->flag; o->status = (uint16_t)r->status;
 			o->edit_distance = r->nm;
 			if (r->score1 <= 0 && r->status == 0) { o->ref_begin1 = -1; o->read_begin1 = -1; }
-			if (r->cigarLen > 0 && r->status == 0) o->cigar_off = pool_words + goffs[q];
+			if (r->cigarLen > 0 && r->status == 0) o->cigar_off = pool.n + goffs[q];
 			if (r->status == 0 && r->score1 > 0) { if (r->word) c->tm.n_word++; else c->tm.n_byte++; }
 			c->tm.cells += (Q->h_off[q + 1] - Q->h_off[q]) * (int64_t)refLen;
 		}
-		pool_words += gwords;
+		pool.n += gwords;
 		free(goffs);
 		ssw_shim_event_record(c->ev_d, c->stream);
 		CALL_TRACE("results + CIGARs on the host");
@@ -2307,10 +2429,6 @@ plan_again:
 		for (int e = ev_first; e + 1 < c->nev; e += 2) fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
 		locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
 		trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
-		{
-			double span = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_a);
-			(void)span;
-		}
 	}
 	{
 		double total = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_d);
@@ -2318,12 +2436,20 @@ plan_again:
 		reduce_ms = total - fill_ms - locate_ms - trace_ms; if (reduce_ms < 0) reduce_ms = 0;
 		c->tm.reduce_ms = reduce_ms;   /* reduction + transfers: everything that is not one of the three timed phases */
 	}
-	if (cigar_pool) { *cigar_pool = pool; pool = 0; }
-	if (cigar_words) *cigar_words = pool_words;
+	if (cigar_pool) { *cigar_pool = pool.words; pool.words = 0; }
+	if (cigar_words) *cigar_words = pool.n;
 	rc = 0;
 done:
-	free(pool); free(order); free(pairs); free(hres); free(hneed); free(bk); free(qdone); free(bplans); free(border); free(defer); free(rdefer); free(hhdr);
+	free(pool.words); free(order); free(pairs); free(hres); free(hneed); free(bk); free(qdone); free(bplans); free(border); free(defer); free(rdefer); free(hhdr);
 	return rc;
+}
+
+int ssw_gpu_align_batch(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
+                        const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_batch: NULL context%s", "");
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_batch_locked(c, Q, T, tfirst, tcount, prm, results, cigar_pool, cigar_words, 0));
 }
 
 int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm,
@@ -2333,7 +2459,7 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	if (!Q || !T || !prm || !fn || !prm->mat) return fail(c, "search_db: NULL argument%s", "");
 	if (Q->ctx != c || T->ctx != c) return fail(c, "search_db: sequences belong to another context%s", "");
 	if (prm->flag != 0) return fail(c, "search_db: scores and end positions only (flag must be 0)%s", "");
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) return SSW_GPU_BUSY;
+	if (ctx_enter(c, 0, 0)) return SSW_GPU_BUSY;      /* (no pool outputs) */
 	ssw_shim_set_device(c->device);
 	const int32_t nq = Q->count, nt_all = T->count;
 	int rc = 0;
@@ -2376,8 +2502,7 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (rc == 0 && ds.fn_rc) rc = ds.fn_rc;
 		ssw_shim_stream_sync(c->stream); ssw_shim_stream_sync(c->stream2);
 	}
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
-	return rc;
+	return ctx_leave(c, rc);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -2403,23 +2528,10 @@ static inline int32_t ps_tid(const pair_src* s, int64_t i) { return s->tbeg ? (i
 
 static double wall_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
-static void timing_add(ssw_gpu_timing* acc, const ssw_gpu_timing* t, int64_t* best_cells)
-{
-	acc->fill_ms += t->fill_ms; acc->fill_launches += t->fill_launches; acc->fill_cells += t->fill_cells; acc->cells += t->cells;
-	acc->reduce_ms += t->reduce_ms; acc->locate_ms += t->locate_ms; acc->trace_ms += t->trace_ms; acc->n_word += t->n_word; acc->n_byte += t->n_byte;
-	acc->db_repeats += t->db_repeats; acc->fill_pipelined += t->fill_pipelined; acc->win_copied += t->win_copied;
-	if (t->fill_cells > *best_cells) {
-		*best_cells = t->fill_cells;
-		memcpy(acc->fill_kernel, t->fill_kernel, sizeof acc->fill_kernel);
-		acc->fill_ops_per_row = t->fill_ops_per_row; acc->fill_rows_per_lane = t->fill_rows_per_lane; acc->fill_strips = t->fill_strips;
-	}
-}
-
 /* the pairs list[0 .. nl) outside the kernel's envelope: grouped by target (counting sort), their queries gathered on the device in
-   chunks of at most max(budget / 8, 1 MiB) residues, one align_batch per target; CIGARs appended to the staging pool *spool */
+   chunks of at most max(budget / 8, 1 MiB) residues, one align_batch per target; CIGARs appended to the staging pool */
 static int pairs_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
-                          const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
-                          uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+                          const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results, cigar_stage* st, call_acc* acc)
 {
 	const int32_t nt = T->count;
 	int64_t* tstart = (int64_t*)calloc((size_t)nt + 1, sizeof(int64_t));
@@ -2476,23 +2588,8 @@ static int pairs_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_s
 			V.total = V.h_off[m] - V.h_off[0];
 			uint32_t* pool = 0; int64_t words = 0;
 			if (align_batch_locked(c, &V, T, t, 1, prm, tmp, &pool, &words, 0)) { ssw_gpu_seqs_free(G); goto out; }      /* (the pool is always taken: offsets in pair order) */
-			timing_add(acc, &c->tm, best_cells);
-			if (words > 0) {
-				if (*swords + words > *scap) {
-					const int64_t ncap = (*swords + words) * 2 + 1024;
-					uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
-					if (!np2) { free(pool); ssw_gpu_seqs_free(G); fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
-					*spool = np2; *scap = ncap;
-				}
-				memcpy(*spool + *swords, pool, sizeof(uint32_t) * (size_t)words);
-			}
-			for (int64_t k = 0; k < m; ++k) {
-				ssw_gpu_result r = tmp[k];
-				if (r.cigarLen > 0 && r.cigar_off >= 0) r.cigar_off += *swords;
-				results[bytgt[tstart[t] + k]] = r;
-			}
-			*swords += words;
-			free(pool);
+			timing_add(acc, &c->tm);
+			if (stage_append_batch(c, st, pool, words, tmp, m, bytgt + tstart[t], sizeof(int64_t), results)) { ssw_gpu_seqs_free(G); goto out; }
 		}
 		ssw_gpu_seqs_free(G);
 		t0 = t1;
@@ -2504,30 +2601,21 @@ out:
 }
 
 /* Flagged pairs inside the fused kernel's envelope: k_fillpairs gave scores and end positions (status carries SSW_OUT_WORD); the pairs that
-   pass the reference's gate (src/ssw.c:900-903, 916) become a survivor list grouped by query geometry bucket, and the reverse pass
-   (window_pass) and the traceback (trace_phase, k_mark included) run over it as (query, target) jobs through an ssw_vmap -- the flagged
-   database search's phases (dbx_chunk) over a pair list.  rec[0 .. nrec) are the fill's records of the pairs pix[]; they are completed in
-   place, CIGARs appended to the staging pool (always, like align_batch does). */
+   pass the reference's gate (src/ssw.c:900-903, 916) become a survivor list grouped by query geometry bucket (a counting sort: survivors of
+   a bucket stay in record order), and the reverse pass and the traceback run over it as (query, target) jobs: survivor_phases.  rec[0 .. nrec)
+   are the fill's records of the pairs pix[]; they are completed in place, CIGARs appended to the staging pool (always, like align_batch does). */
 static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
                          const int64_t* pix, ssw_gpu_result* rec, int64_t nrec, const ssw_gpu_params* prm, const int8_t* d_mat,
-                         int32_t maxmat, int32_t minmat, uint32_t** spool, int64_t* swords, int64_t* scap,
-                         double* locate_ms, double* trace_ms)
+                         int32_t maxmat, int32_t minmat, cigar_stage* st)
 {
-	const int32_t n = prm->n;
-	/* geometry of the window kernels, as align_batch chooses it (queries here are <= 640 residues) */
-	int32_t xlanes = 64, xrmax = 4 * (24 / (n + 1) < 1 ? 1 : 24 / (n + 1) > 3 ? 3 : 24 / (n + 1)), xrcap = 12;
-	if (c->kn.xlanes16) xlanes = 16;
-	if (c->kn.xr) { xrmax = c->kn.xr; xrcap = xrmax; }
-	if (c->kn.xr_window) xrcap = c->kn.xr_window;
-	while (xlanes == 64 && xrmax > 4 && (int64_t)n * ((xrmax + 3) / 4) * 1024 > 65535) xrmax -= 4;
-	const int32_t rows = xlanes * (xlanes == 64 ? xrmax : SSW_RMAX);
-	/* bucket key per query length: R (short queries), SSW_RMAX + 1 + Rq (one strip), SSW_RMAX + 64 + P16 / 16 (several strips) */
-	const int NKEY = SSW_RMAX + 64 + 41;
-	int64_t kfirst[SSW_RMAX + 64 + 42]; int32_t kp16[SSW_RMAX + 64 + 41];
+	win_geom geom;
+	win_geom_fill(&geom, &c->kn, prm->n);      /* (queries here are <= 640 residues) */
+	enum { NKEY = SSW_RMAX + 64 + 41 };        /* bucket keys of queries up to 640 residues: win_bucket_key */
+	int64_t kfirst[NKEY + 1]; int32_t kp16[NKEY];
 	memset(kfirst, 0, sizeof kfirst); memset(kp16, 0, sizeof kp16);
 	int32_t* key = (int32_t*)malloc(sizeof(int32_t) * (size_t)(nrec > 0 ? nrec : 1));
 	int64_t* order = (int64_t*)malloc(sizeof(int64_t) * (size_t)(nrec > 0 ? nrec : 1));
-	ssw_dres* hs = 0; int32_t* hvq = 0; int32_t* hvt = 0; int32_t* ids = 0; int32_t* hneed = 0; int64_t* goffs = 0;
+	ssw_dres* hs = 0; int32_t* hvq = 0; int64_t* poff = 0; surv_range* rg = 0;
 	int rc = -1;
 	if (!key || !order) { fail(c, "out of host memory%s", ""); goto out; }
 	int64_t ns = 0; int32_t maxlen = 0; int64_t maxt = 0;
@@ -2538,11 +2626,10 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		key[k] = -1;
 		if (o->status != 0 || o->score1 == 0 || (prm->flag == 2 && (int)o->score1 < prm->filters)) continue;      /* ssw.c:900-903, 916 */
 		const int64_t i = pix[k];
-		const int32_t len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]), P16q = (len + 15) / 16 * 16;
+		const int32_t len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]);
 		const int64_t tl = ps_tlen(src, T, i);
-		int32_t kk;
-		if (len <= 16 * SSW_RMAX) kk = P16q / 16;
-		else { const int32_t st = (P16q + rows - 1) / rows, Rq = (P16q + xlanes * st - 1) / (xlanes * st); kk = st == 1 ? SSW_RMAX + 1 + Rq : SSW_RMAX + 64 + P16q / 16; }
+		int32_t P16q;
+		const int32_t kk = win_bucket_key(&geom, len, &P16q);
 		key[k] = kk | (word << 30);
 		kfirst[kk + 1]++;
 		if (P16q > kp16[kk]) kp16[kk] = P16q;
@@ -2554,11 +2641,11 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 	if (ns > 0x7fffff00) { fail(c, "%s: more than 2^31 flagged pairs in one call", src->who); goto out; }
 	for (int b = 0; b < NKEY; ++b) kfirst[b + 1] += kfirst[b];
 	{
-		int64_t pos[SSW_RMAX + 64 + 41];
+		int64_t pos[NKEY];
 		memcpy(pos, kfirst, sizeof pos);
 		for (int64_t k = 0; k < nrec; ++k) if (key[k] >= 0) order[pos[key[k] & 0xffff]++] = k;
 	}
-	hs = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)ns); hvq = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)ns); hvt = hvq + ns;
+	hs = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)ns); hvq = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)ns);
 	if (!hs || !hvq) { fail(c, "out of host memory%s", ""); goto out; }
 	for (int64_t v = 0; v < ns; ++v) {
 		const int64_t k = order[v], i = pix[k];
@@ -2567,105 +2654,46 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 		memset(r, 0, sizeof *r);
 		r->score1 = o->score1; r->score2 = o->score2; r->ref_begin1 = -1; r->ref_end1 = o->ref_end1; r->read_begin1 = -1; r->read_end1 = o->read_end1;
 		r->ref_end2 = o->ref_end2; r->word = (key[k] >> 30) & 1; r->want_begin = 1; r->loc_done = 1;      /* (as k_select writes them) */
-		hvq[v] = qidx[i]; hvt[v] = ps_tid(src, i); hvq[2 * ns + v] = (int32_t)v;
+		hvq[v] = qidx[i]; hvq[ns + v] = ps_tid(src, i); hvq[2 * ns + v] = (int32_t)v;      /* query, target, identity list */
 	}
-	{
-		ssw_dres* d_sres = (ssw_dres*)ensure(c, &c->sres, sizeof(ssw_dres) * (size_t)ns);
-		int32_t* d_maps = (int32_t*)ensure(c, &c->svq, sizeof(int32_t) * 4 * (size_t)ns);      /* vq, vt, identity list, traceback job lists */
-		if (!d_sres || !d_maps) goto out;
-		int32_t* d_vq = d_maps; int32_t* d_vt = d_maps + ns; int32_t* d_vl = d_maps + 2 * (size_t)ns; int32_t* d_tl = d_maps + 3 * (size_t)ns;
-		ssw_shim_event_record(c->ev_a, c->stream);
-		if (ssw_shim_h2d(d_sres, hs, sizeof(ssw_dres) * (size_t)ns, c->stream) || ssw_shim_h2d(d_maps, hvq, sizeof(int32_t) * 3 * (size_t)ns, c->stream)) {
-			fail(c, "upload failed: %s", ssw_shim_last_error()); goto out;
-		}
-		ssw_vmap vm; vm.vq = d_vq; vm.vt = d_vt; vm.tcodes = T->d_codes; vm.toff = T->d_off; vm.win = src->d_win;
-		win_in wi; memset(&wi, 0, sizeof wi);
-		wi.Q = Q; wi.prm = prm; wi.d_tgt = T->d_codes; wi.refLen = (int32_t)maxt; wi.d_mat = d_mat; wi.n = n; wi.maxmat = maxmat; wi.minmat = minmat;
-		wi.fill_form = c->kn.fill_plain ? 0 : -1; wi.xlanes = xlanes; wi.xrmax = xrmax; wi.xrcap = xrcap;
-		for (int kk = 0; kk < NKEY; ++kk) {
-			const int64_t f0 = kfirst[kk], cnt = kfirst[kk + 1] - kfirst[kk];
-			if (cnt <= 0) continue;
-			bucket B; memset(&B, 0, sizeof B);
-			if (kk <= SSW_RMAX) { B.R = kk; B.strips = 1; B.P16 = 16 * kk; B.lanes = 16; B.use_x = 0; }
-			else {      /* the strip geometry of align_batch's bucket (ssw_host.c align_batch_locked) */
-				B.P16 = kp16[kk]; B.lanes = xlanes; B.use_x = 1;
-				B.strips = (B.P16 + rows - 1) / rows;
-				B.R = (B.P16 + B.lanes * B.strips - 1) / (B.lanes * B.strips);
-				if (B.lanes == 64 && B.strips > 1 && xrmax > 4 && !c->kn.no_tail) {
-					const int32_t rem = B.P16 - (B.strips - 1) * 64 * xrmax, need = (rem + 63) / 64, tr = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 0;
-					if (rem > 0 && tr > 0 && xrmax * (B.strips - 1) + tr < B.R * B.strips) { B.R = xrmax; B.tailR = tr; }
-				}
-			}
-			wi.d_res = d_sres + f0; wi.vm = vm; wi.vm.vq = d_vq + f0; wi.vm.vt = d_vt + f0;
-			if (window_pass(c, &wi, &B, 1, d_vl, (int32_t)cnt, 0)) goto out;
-		}
-		ssw_shim_event_record(c->ev_b, c->stream);
-		/* traceback over slabs of survivors (a slab = the CIGAR slots that fit half the budget), as the flagged database search does it */
-		const int32_t halo_max = halo_for((maxlen + 15) / 16 * 16, maxmat, prm->gapE);
-		const int64_t ref_span = halo_max < maxt ? halo_max : maxt;
-		const int64_t slot_bytes = 8 * ((int64_t)maxlen + ref_span + 16) + 4 * (int64_t)maxlen + 256;
-		int64_t slab = (int64_t)(c->cm_budget / 2) / slot_bytes;
-		if (slab < 1024) slab = 1024;
-		if (c->kn.dbx_slab) slab = c->kn.dbx_slab;
-		const int64_t sl = ns < slab ? ns : slab;
-		ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)sl); goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)sl);
-		if (!ids || !hneed || !goffs) { fail(c, "out of host memory%s", ""); goto out; }
-		for (int64_t s0 = 0; s0 < ns; s0 += slab) {
-			const int32_t cnt = (int32_t)(ns - s0 < slab ? ns - s0 : slab);
-			trace_out tro; memset(&tro, 0, sizeof tro);
-			if ((prm->flag & 7) != 0) {
-				for (int32_t k = 0; k < cnt; ++k) ids[k] = k;
-				trace_in tri; memset(&tri, 0, sizeof tri);
-				tri.Q = Q; tri.prm = prm; tri.d_tgt = T->d_codes; tri.vm = vm; tri.vm.vq = d_vq + s0; tri.vm.vt = d_vt + s0; tri.d_mat = d_mat; tri.n = n;
-				tri.d_res = d_sres + s0; tri.nslots = cnt; tri.ids = ids; tri.nids = cnt; tri.d_list = d_tl; tri.hneed = hneed; tri.maxlen = maxlen; tri.ref_span = ref_span;
-				if (trace_phase(c, &tri, &tro)) goto out;
-			}
-			if (ssw_shim_d2h(hs + s0, d_sres + s0, sizeof(ssw_dres) * (size_t)cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto out; }
-			int64_t gwords = 0;
-			for (int32_t k = 0; k < cnt; ++k) {
-				const ssw_dres* r = &hs[s0 + k];
-				if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); goto out; }
-				goffs[k] = gwords;
-				if (r->cigarLen > 0 && r->status == 0) gwords += r->cigarLen;
-			}
-			if (gwords > 0) {
-				int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
-				uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
-				if (!d_goff || !d_gpool) goto out;
-				if (*swords + gwords > *scap) {
-					const int64_t ncap = (*swords + gwords) * 2 + 1024;
-					uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
-					if (!np2) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
-					*spool = np2; *scap = ncap;
-				}
-				ssw_gather_args ga; ga.src = tro.d_cig; ga.res = d_sres + s0; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
-				if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
-				    ssw_shim_d2h(*spool + *swords, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream) || ssw_shim_stream_sync(c->stream)) {
-					fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); goto out;
-				}
-			}
-			for (int32_t k = 0; k < cnt; ++k) {      /* what the reverse pass and the traceback added to the records */
-				const ssw_dres* r = &hs[s0 + k];
-				ssw_gpu_result* o = &rec[order[s0 + k]];
-				o->ref_begin1 = r->ref_begin1; o->read_begin1 = r->read_begin1; o->cigarLen = r->cigarLen; o->flag = (uint16_t)r->flag;
-				o->edit_distance = r->nm; o->cigar_off = r->cigarLen > 0 && r->status == 0 ? *swords + goffs[k] : -1;
-			}
-			*swords += gwords;
-		}
-		ssw_shim_event_record(c->ev_c, c->stream);
-		if (ssw_shim_stream_sync(c->stream) || chainq_check(c)) { if (!c->err[0]) fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto out; }
-		*locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
-		*trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
+	ssw_dres* d_sres = (ssw_dres*)ensure(c, &c->sres, sizeof(ssw_dres) * (size_t)ns);
+	int32_t* d_maps = (int32_t*)ensure(c, &c->svq, sizeof(int32_t) * 4 * (size_t)ns);      /* vq, vt, identity list, traceback job lists */
+	if (!d_sres || !d_maps) goto out;
+	ssw_shim_event_record(c->ev_a, c->stream);
+	if (ssw_shim_h2d(d_sres, hs, sizeof(ssw_dres) * (size_t)ns, c->stream) || ssw_shim_h2d(d_maps, hvq, sizeof(int32_t) * 3 * (size_t)ns, c->stream)) {
+		fail(c, "upload failed: %s", ssw_shim_last_error()); goto out;
+	}
+	poff = (int64_t*)malloc(sizeof(int64_t) * (size_t)ns); rg = (surv_range*)malloc(sizeof(surv_range) * NKEY);
+	if (!poff || !rg) { fail(c, "out of host memory%s", ""); goto out; }
+	int nrg = 0;
+	for (int kk = 0; kk < NKEY; ++kk) {
+		if (kfirst[kk + 1] == kfirst[kk]) continue;
+		memset(&rg[nrg], 0, sizeof rg[nrg]);
+		win_bucket_shape(&rg[nrg].b, &geom, kk, kp16[kk]);
+		rg[nrg].first = kfirst[kk]; rg[nrg].count = kfirst[kk + 1] - kfirst[kk];
+		++nrg;
+	}
+	surv_in si; memset(&si, 0, sizeof si);
+	si.Q = Q; si.T = T; si.prm = prm; si.d_mat = d_mat; si.maxmat = maxmat; si.minmat = minmat; si.g = &geom; si.fill_form = c->kn.fill_plain ? 0 : -1;
+	si.maxlen = maxlen; si.maxt = maxt; si.d_sres = d_sres; si.d_maps = d_maps; si.ns = ns; si.d_win = src->d_win; si.rg = rg; si.nrg = nrg;
+	si.check_queue = 1;
+	if (survivor_phases(c, &si, hs, st, poff, &c->tm.locate_ms, &c->tm.trace_ms)) goto out;
+	for (int64_t v = 0; v < ns; ++v) {      /* what the reverse pass and the traceback added to the records */
+		const ssw_dres* r = &hs[v];
+		ssw_gpu_result* o = &rec[order[v]];
+		o->ref_begin1 = r->ref_begin1; o->read_begin1 = r->read_begin1; o->cigarLen = r->cigarLen; o->flag = (uint16_t)r->flag;
+		o->edit_distance = r->nm; o->cigar_off = r->cigarLen > 0 && r->status == 0 ? poff[v] : -1;
 	}
 	rc = 0;
 out:
-	free(key); free(order); free(hs); free(hvq); free(ids); free(hneed); free(goffs);
+	free(key); free(order); free(hs); free(hvq); free(poff); free(rg);
 	return rc;
 }
 
+/* (the fallbacks go back into the pair path with the temporary sets they gathered: windows_fallback -> align_pairs_locked -> pairs_core ->
+   windows_fallback.  The nested call has whole targets and never gets here again.) */
 static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
-                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
-                            uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells);
+                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results, cigar_stage* st, call_acc* acc);
 
 /* select mode of the pair list (ssw_gpu_align_windows_best): the pairs are candidates in groups, `results` has one record per GROUP */
 typedef struct { const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel; } best_mode;
@@ -2673,8 +2701,7 @@ typedef struct { const int64_t* cand_off; int64_t ngroups; int32_t min_score; ss
 /* windows_fallback over the candidates list[0 .. nl) of a select-mode call, records to out[0 .. nl) in list order (the candidates' four
    arrays are compacted, so that the fallback's "pair index" is the position in the list) */
 static int best_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
-                         const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* out,
-                         uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+                         const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* out, cigar_stage* st, call_acc* acc)
 {
 	int64_t* b2 = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)nl);
 	int32_t* q2 = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)nl);
@@ -2684,7 +2711,7 @@ static int best_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 	for (int64_t k = 0; k < nl; ++k) { const int64_t i = list[k]; q2[k] = qidx[i]; t2[k] = src->tidx[i]; b2[k] = src->tbeg[i]; l2[k] = src->tlen[i]; id[k] = k; }
 	pair_src s2 = *src;
 	s2.tidx = t2; s2.tbeg = b2; s2.tlen = l2; s2.d_win = 0;
-	rc = windows_fallback(c, Q, T, q2, &s2, id, nl, prm, out, spool, swords, scap, acc, best_cells);
+	rc = windows_fallback(c, Q, T, q2, &s2, id, nl, prm, out, st, acc);
 out:
 	free(b2); free(q2);
 	return rc;
@@ -2709,9 +2736,8 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	ssw_shim_set_device(c->device);
 	knobs_load(&c->kn);
 
-	int32_t minmat = 0, maxmat = 0;
-	for (int64_t i = 0; i < (int64_t)prm->n * prm->n; ++i) { if (prm->mat[i] < minmat) minmat = prm->mat[i]; if (prm->mat[i] > maxmat) maxmat = prm->mat[i]; }
-	const int32_t bias = (prm->score_size == 0 || prm->score_size == 2) ? -minmat : 0;
+	int32_t minmat, maxmat, bias;
+	mat_range(prm, &minmat, &maxmat, &bias);
 	const int32_t n = prm->n;
 	/* (flagged pairs: the window kernels reach a job's target through a 64-bit base and keep their column indices relative to it, so the size
 	   of the resident set does not matter -- unlike the flagged database search's survivors) */
@@ -2727,9 +2753,8 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	ssw_gpu_result* fbrec = 0; int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0;      /* select mode */
 	unsigned char* d_brec = 0; int8_t* d_mat = 0; int64_t nj = 0;
 	const int64_t nout = bm ? bm->ngroups : np;
-	uint32_t* spool = 0; int64_t swords = 0, scap = 0;
-	ssw_gpu_timing acc; memset(&acc, 0, sizeof acc);
-	int64_t best_cells = 0;
+	cigar_stage st; memset(&st, 0, sizeof st);
+	call_acc acc; memset(&acc, 0, sizeof acc);
 	int rc = -1;
 	if (!kcount || !key || !perm) { fail(c, "out of host memory%s", ""); goto done; }
 	for (int64_t i = 0; i < np; ++i) {
@@ -2751,7 +2776,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		ssw_gpu_params p0 = *prm; p0.flag = 0;
 		fbrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nfb);
 		if (!fbrec) { fail(c, "out of host memory%s", ""); goto done; }
-		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, &st, &acc)) goto done;
 		memset(&c->tm, 0, sizeof c->tm);
 	}
 	if (nk > 0) {
@@ -2862,10 +2887,9 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			int64_t nrec = 0;
 			for (int64_t j = 0; j < nj; ++j)
 				for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
-			if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
-			                                    &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
+			if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &st)) goto done;
 			for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
-			timing_add(&acc, &c->tm, &best_cells);
+			timing_add(&acc, &c->tm);
 		}
 	}
 	if (bm) {
@@ -2907,27 +2931,26 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 				if (key[i] == 0xffffffffu) { ++nfw; wlist[ng - nfw] = i; wg[ng - nfw] = g; }
 				else { wlist[nin] = i; wg[nin] = g; wrec[nin] = results[g]; ++nin; }
 			}
-			if (nin > 0 && pairs_flagged(c, Q, T, qidx, src, wlist, wrec, nin, prm, d_mat, maxmat, minmat, &spool, &swords, &scap,
-			                             &c->tm.locate_ms, &c->tm.trace_ms)) goto done;
+			if (nin > 0 && pairs_flagged(c, Q, T, qidx, src, wlist, wrec, nin, prm, d_mat, maxmat, minmat, &st)) goto done;
 			for (int64_t k = 0; k < nin; ++k) results[wg[k]] = wrec[k];
 		}
-		timing_add(&acc, &c->tm, &best_cells);
+		timing_add(&acc, &c->tm);
 		if (nfw > 0) {
-			if (best_fallback(c, Q, T, qidx, src, wlist + (ng - nfw), nfw, prm, wrec, &spool, &swords, &scap, &acc, &best_cells)) goto done;
+			if (best_fallback(c, Q, T, qidx, src, wlist + (ng - nfw), nfw, prm, wrec, &st, &acc)) goto done;
 			for (int64_t k = 0; k < nfw; ++k) results[wg[ng - nfw + k]] = wrec[k];
 		}
-		acc.best_flagged = nin + nfw;
+		acc.t.best_flagged = nin + nfw;
 	}
-	if (!bm && nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells)
-	                          : pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &spool, &swords, &scap, &acc, &best_cells))) goto done;
-	if (swords > 0) {      /* the pool in pair order (offsets as the caller's pool would have them, also when it asked for none) */
-		uint32_t* pool = cigar_pool ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)swords) : 0;
+	if (!bm && nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &st, &acc)
+	                          : pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &st, &acc))) goto done;
+	if (st.n > 0) {      /* the pool in pair order (offsets as the caller's pool would have them, also when it asked for none) */
+		uint32_t* pool = cigar_pool ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)st.n) : 0;
 		if (cigar_pool && !pool) { fail(c, "out of host memory (%s)", "CIGAR pool"); goto done; }
 		int64_t w = 0;
 		for (int64_t i = 0; i < nout; ++i) {
 			ssw_gpu_result* r = &results[i];
 			if (r->cigarLen > 0 && r->cigar_off >= 0) {
-				if (pool) memcpy(pool + w, spool + r->cigar_off, sizeof(uint32_t) * (size_t)r->cigarLen);
+				if (pool) memcpy(pool + w, st.words + r->cigar_off, sizeof(uint32_t) * (size_t)r->cigarLen);
 				r->cigar_off = w; w += r->cigarLen;
 			}
 		}
@@ -2935,12 +2958,12 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (cigar_words) *cigar_words = w;
 	}
 	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
-		const int64_t i = perm[k]; acc.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
-	acc.total_ms = wall_ms() - t_start;
-	c->tm = acc;
+		const int64_t i = perm[k]; acc.t.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
+	acc.t.total_ms = wall_ms() - t_start;
+	c->tm = acc.t;
 	rc = 0;
 done:
-	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(spool);
+	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(st.words);
 	free(fbrec); free(slot); free(wlist); free(wrec);
 	return rc;
 }
@@ -2948,10 +2971,8 @@ done:
 static int align_pairs_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const int32_t* tidx,
                               int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !results))) return fail(c, "align_pairs: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "align_pairs: sequences belong to another context%s", "");
-	if (prm->n < 1) return fail(c, "align_pairs: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_pairs: score_size must be 0, 1 or 2%s", "");
+	if (np < 0 || (np > 0 && (!qidx || !tidx || !results))) return fail(c, "align_pairs: NULL argument%s", "");
+	if (check_common(c, "align_pairs", Q, T, prm)) return -1;
 	for (int64_t i = 0; i < np; ++i)
 		if (qidx[i] < 0 || qidx[i] >= Q->count || tidx[i] < 0 || tidx[i] >= T->count) {
 			char msg[160];
@@ -2967,14 +2988,8 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seq
                         const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
 	if (!c) return fail(0, "align_pairs: NULL context%s", "");
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
-		if (cigar_pool) *cigar_pool = 0;
-		if (cigar_words) *cigar_words = 0;
-		return SSW_GPU_BUSY;
-	}
-	const int rc = align_pairs_locked(c, Q, T, qidx, tidx, npairs, prm, results, cigar_pool, cigar_words);
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
-	return rc;
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_pairs_locked(c, Q, T, qidx, tidx, npairs, prm, results, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -2995,8 +3010,7 @@ static int wkey_cmp(const void* pa, const void* pb)
 }
 
 static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
-                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results,
-                            uint32_t** spool, int64_t* swords, int64_t* scap, ssw_gpu_timing* acc, int64_t* best_cells)
+                            const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results, cigar_stage* st, call_acc* acc)
 {
 	wkey* wk = (wkey*)malloc(sizeof(wkey) * (size_t)nl);
 	int32_t* q2 = 0; int32_t* t2 = 0; int32_t* gidx = 0; int64_t* gbeg = 0; int64_t* goff = 0; ssw_gpu_result* tmp = 0;
@@ -3043,24 +3057,9 @@ static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu
 		uint32_t* pool = 0; int64_t words = 0;
 		if (align_pairs_locked(c, Q, G, q2, t2, m, prm, tmp, &pool, &words)) { ssw_gpu_seqs_free(G); goto out; }
 		ssw_gpu_seqs_free(G);
-		timing_add(acc, &c->tm, best_cells);
-		acc->win_copied += sum;
-		if (words > 0) {
-			if (*swords + words > *scap) {
-				const int64_t ncap = (*swords + words) * 2 + 1024;
-				uint32_t* np2 = (uint32_t*)realloc(*spool, sizeof(uint32_t) * (size_t)ncap);
-				if (!np2) { free(pool); fail(c, "out of host memory (%s)", "CIGAR pool"); goto out; }
-				*spool = np2; *scap = ncap;
-			}
-			memcpy(*spool + *swords, pool, sizeof(uint32_t) * (size_t)words);
-		}
-		free(pool);
-		for (int64_t k = 0; k < m; ++k) {
-			ssw_gpu_result r = tmp[k];
-			if (r.cigarLen > 0 && r.cigar_off >= 0) r.cigar_off += *swords;
-			results[wk[k0 + k].i] = r;
-		}
-		*swords += words;
+		timing_add(acc, &c->tm);
+		acc->t.win_copied += sum;
+		if (stage_append_batch(c, st, pool, words, tmp, m, &wk[k0].i, sizeof(wkey), results)) goto out;
 		k0 = k1;
 	}
 	rc = 0;
@@ -3093,10 +3092,8 @@ static int align_windows_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
                                 const int64_t* tbeg, const int32_t* tlen, int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results,
                                 uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	if (!Q || !T || !prm || !prm->mat || np < 0 || (np > 0 && (!qidx || !tidx || !tbeg || !tlen || !results))) return fail(c, "align_windows: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "align_windows: sequences belong to another context%s", "");
-	if (prm->n < 1) return fail(c, "align_windows: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_windows: score_size must be 0, 1 or 2%s", "");
+	if (np < 0 || (np > 0 && (!qidx || !tidx || !tbeg || !tlen || !results))) return fail(c, "align_windows: NULL argument%s", "");
+	if (check_common(c, "align_windows", Q, T, prm)) return -1;
 	if (np > 0x7fffff00) return fail(c, "align_windows: %s", "more than 2^31 pairs in one call");      /* (a pair's window is named by a 32-bit index) */
 	if (windows_check(c, "align_windows", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
 	pair_src src; memset(&src, 0, sizeof src);
@@ -3109,30 +3106,22 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_s
                           uint32_t** cigar_pool, int64_t* cigar_words)
 {
 	if (!c) return fail(0, "align_windows: NULL context%s", "");
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
-		if (cigar_pool) *cigar_pool = 0;
-		if (cigar_words) *cigar_words = 0;
-		return SSW_GPU_BUSY;
-	}
-	const int rc = align_windows_locked(c, Q, T, qidx, tidx, tbeg, tlen, npairs, prm, results, cigar_pool, cigar_words);
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
-	return rc;
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_locked(c, Q, T, qidx, tidx, tbeg, tlen, npairs, prm, results, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------
  * Best candidate window per read (ssw_gpu_align_windows_best): ssw_gpu_align_windows' pair list in groups, pairs_core in select mode.
  * ------------------------------------------------------------------------------------------------ */
-static void topk_pad(ssw_gpu_result* o);
-
 static int align_windows_best_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t ng,
                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, const ssw_gpu_params* prm,
                                      int32_t min_score, ssw_gpu_best* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
 	char msg[200];
-	if (!Q || !T || !prm || !prm->mat || ng < 0 || (ng > 0 && (!cand_off || !sel || !results))) return fail(c, "align_windows_best: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "align_windows_best: sequences belong to another context%s", "");
-	if (prm->n < 1) return fail(c, "align_windows_best: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "align_windows_best: score_size must be 0, 1 or 2%s", "");
+	if (cigar_pool) *cigar_pool = 0;      /* (this entry point alone empties its pool outputs before the argument checks) */
+	if (cigar_words) *cigar_words = 0;
+	if (ng < 0 || (ng > 0 && (!cand_off || !sel || !results))) return fail(c, "align_windows_best: NULL argument%s", "");
+	if (check_common(c, "align_windows_best", Q, T, prm)) return -1;
 	if (ng == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }
 	if (cand_off[0] != 0) {
 		snprintf(msg, sizeof msg, "group 0 starts at candidate %lld", (long long)cand_off[0]);
@@ -3164,16 +3153,8 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
                                uint32_t** cigar_pool, int64_t* cigar_words)
 {
 	if (!c) return fail(0, "align_windows_best: NULL context%s", "");
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
-		if (cigar_pool) *cigar_pool = 0;
-		if (cigar_words) *cigar_words = 0;
-		return SSW_GPU_BUSY;
-	}
-	if (cigar_pool) *cigar_pool = 0;
-	if (cigar_words) *cigar_words = 0;
-	const int rc = align_windows_best_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, min_score, sel, results, cigar_pool, cigar_words);
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
-	return rc;
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_best_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, min_score, sel, results, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -3184,7 +3165,6 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
  *   flag != 0: the selected (query, target) pairs, in (q, r) order, through align_pairs_locked with the caller's parameters.
  * Queries go in blocks whose lists take at most half the budget; the two chunk buffers at most a quarter each.
  * ------------------------------------------------------------------------------------------------ */
-static void topk_pad(ssw_gpu_result* o) { memset(o, 0, sizeof *o); o->ref_begin1 = -1; o->read_begin1 = -1; o->cigar_off = -1; }
 static uint64_t topk_hkey(uint32_t score1, int32_t t) { return ((uint64_t)score1 << 32) | (uint32_t)~(uint32_t)t; }
 
 typedef struct { uint64_t key; int32_t t; ssw_gpu_result r; } topk_cand;
@@ -3196,7 +3176,7 @@ static int topk_cand_cmp(const void* a, const void* b)
 
 /* generic path of one query block: lists in lt[q * k ..] / lr[q * k ..], counts in cnt[] */
 static int topk_generic(ssw_gpu_ctx* c, const ssw_gpu_seqs* V, const ssw_gpu_seqs* T, const ssw_gpu_params* p0, int32_t k, int32_t lo,
-                        int64_t chunk, int32_t* lt, ssw_gpu_result* lr, ssw_gpu_timing* acc, int64_t* best_cells)
+                        int64_t chunk, int32_t* lt, ssw_gpu_result* lr, call_acc* acc)
 {
 	const int32_t nq = V->count, nt_all = T->count;
 	ssw_gpu_result* full = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nq * (size_t)chunk);
@@ -3207,7 +3187,7 @@ static int topk_generic(ssw_gpu_ctx* c, const ssw_gpu_seqs* V, const ssw_gpu_seq
 	for (int32_t t0 = 0; t0 < nt_all; t0 += (int32_t)chunk) {
 		const int32_t nt = nt_all - t0 < chunk ? nt_all - t0 : (int32_t)chunk;
 		if (align_batch_locked(c, V, T, t0, nt, p0, full, 0, 0, 0)) goto out;
-		timing_add(acc, &c->tm, best_cells);
+		timing_add(acc, &c->tm);
 		for (int32_t q = 0; q < nq; ++q) {
 			int32_t* qt = lt + (int64_t)q * k; ssw_gpu_result* qr = lr + (int64_t)q * k;
 			const int32_t m0 = cnt[q];
@@ -3266,8 +3246,7 @@ static int search_topk_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	const int64_t nch = (nt_all + chunk - 1) / chunk;
 
 	topk_sel sel; memset(&sel, 0, sizeof sel);
-	ssw_gpu_timing acc; memset(&acc, 0, sizeof acc);
-	int64_t best_cells = 0;
+	call_acc acc; memset(&acc, 0, sizeof acc);
 	int32_t* hlt = 0; struct ssw_hit_rec* hlh = 0; int32_t* hst = 0;
 	int32_t *pq = 0, *pt = 0; int64_t* ppos = 0; ssw_gpu_result* pres = 0;
 	int rc = -1;
@@ -3300,14 +3279,14 @@ static int search_topk_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		const int brc = align_batch_locked(c, &V, T, 0, nt_all, &p0, 0, 0, 0, &ds);
 		if (brc == SSW_NOT_STREAMABLE) {
 			ssw_shim_stream_sync(c->stream); ssw_shim_stream_sync(c->stream2);
-			if (topk_generic(c, &V, T, &p0, k, lo, chunk, lt, lr, &acc, &best_cells)) goto done;
+			if (topk_generic(c, &V, T, &p0, k, lo, chunk, lt, lr, &acc)) goto done;
 			continue;
 		}
 		if (brc) { ssw_shim_stream_sync(c->stream); ssw_shim_stream_sync(c->stream2); goto done; }
 		double sel_ms = 0;
 		for (int64_t i = 0; i < nch; ++i) sel_ms += ssw_shim_event_elapsed_ms(sel.ev[2 * i], sel.ev[2 * i + 1]);
 		c->tm.reduce_ms = sel_ms;      /* (include/ssw_gpu.h: the selection's device time) */
-		timing_add(&acc, &c->tm, &best_cells);
+		timing_add(&acc, &c->tm);
 		/* the lists, once */
 		if (ssw_shim_d2h(hst, d_state, sizeof(int32_t) * 2 * (size_t)nb, c->stream) ||
 		    ssw_shim_d2h(hlt, d_lt, sizeof(int32_t) * (size_t)nb * (size_t)k, c->stream) ||
@@ -3334,11 +3313,11 @@ static int search_topk_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		int64_t p = 0;
 		for (int64_t i = 0; i < (int64_t)nq * k; ++i) if (tidx[i] >= 0) { pq[p] = (int32_t)(i / k); pt[p] = tidx[i]; ppos[p] = i; ++p; }
 		if (align_pairs_locked(c, Q, T, pq, pt, np, prm, pres, cigar_pool, cigar_words)) goto done;
-		timing_add(&acc, &c->tm, &best_cells);
+		timing_add(&acc, &c->tm);
 		for (int64_t i = 0; i < np; ++i) results[ppos[i]] = pres[i];
 	}
-	acc.total_ms = wall_ms() - t_start;
-	c->tm = acc;
+	acc.t.total_ms = wall_ms() - t_start;
+	c->tm = acc.t;
 	rc = 0;
 done:
 	for (int i = 0; i < sel.nev; ++i) ssw_shim_event_destroy(sel.ev[i]);
@@ -3351,18 +3330,10 @@ int ssw_gpu_search_topk(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seq
 {
 	if (!c) return fail(0, "search_topk: NULL context%s", "");
 	if (k < 1 || k > SSW_GPU_TOPK_MAX) return fail(c, "search_topk: k must be 1 .. SSW_GPU_TOPK_MAX%s", "");
-	if (!Q || !T || !prm || !prm->mat || !tidx || !results) return fail(c, "search_topk: NULL argument%s", "");
-	if (Q->ctx != c || T->ctx != c) return fail(c, "search_topk: sequences belong to another context%s", "");
-	if (prm->n < 1) return fail(c, "search_topk: alphabet size must be >= 1%s", "");
-	if (prm->score_size < 0 || prm->score_size > 2) return fail(c, "search_topk: score_size must be 0, 1 or 2%s", "");
-	if (__atomic_exchange_n(&c->busy, 1, __ATOMIC_ACQUIRE)) {
-		if (cigar_pool) *cigar_pool = 0;
-		if (cigar_words) *cigar_words = 0;
-		return SSW_GPU_BUSY;
-	}
-	const int rc = search_topk_locked(c, Q, T, prm, k, min_score, targets_per_chunk, tidx, results, cigar_pool, cigar_words);
-	__atomic_store_n(&c->busy, 0, __ATOMIC_RELEASE);
-	return rc;
+	if (!tidx || !results) return fail(c, "search_topk: NULL argument%s", "");
+	if (check_common(c, "search_topk", Q, T, prm)) return -1;      /* (this entry point checks its arguments before it takes the context) */
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, search_topk_locked(c, Q, T, prm, k, min_score, targets_per_chunk, tidx, results, cigar_pool, cigar_words));
 }
 
 void* ssw_gpu_host_alloc(ssw_gpu_ctx* c, size_t bytes)

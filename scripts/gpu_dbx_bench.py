@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box: begin positions / CIGARs against a whole database in ONE batch call (ssw_host.c dbx_chunk) next to the score-only search and to
+"""GPU box: begin positions / CIGARs against a whole database in ONE batch call (ssw_host.c dbx_chunk + survivor_phases) next to the score-only search and to
 the per-target loop it replaces -- config-5-shaped proteins, BLOSUM50, gaps 3/1, flag 2 with a score filter; every record and every CIGAR
 checked against the reference's own loop (oracle/_ref: refwrap_bench_dbx = ssw_init per query + ssw_align per entry with the same flag /
 filter, src/main.c:493-506).  One JSON line.   usage: gpu_dbx_bench.py [nq] [nt] [keep_percent]"""

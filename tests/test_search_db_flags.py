@@ -1,6 +1,6 @@
 """Begin positions / CIGARs against MANY targets in one batch call (the reference's loop: ssw_align with flag 2 and a score filter for
 every (read, target) pair, src/main.c:493-506; gating src/ssw.c:916, 938).  The flagged database path (ssw_host.c dbx_chunk: fused
-search -> k_select -> one batched reverse pass + traceback over the survivors as (query, target) jobs) must return, for every pair,
+search -> k_select; survivor_phases: one batched reverse pass + traceback over the survivors as (query, target) jobs) must return, for every pair,
 exactly what the reference returns -- all s_align fields and every CIGAR word -- for every flag / filter combination, in chunks of
 targets too, and the same records as the per-target loop it replaces (SSW_GPU_NO_DBX=1)."""
 import os
