@@ -242,4 +242,25 @@ SSW_DEV int fr_phi(int step, int lane, int GL, int base, int kmask, int gapE) { 
 SSW_DEV u32 pk_dup(int v) { return ((u32)v & 0xffffu) * 0x10001u; }
 SSW_DEV u32 pk_make(int lo, int hi) { return ((u32)lo & 0xffffu) | ((u32)hi << 16); }
 
+/* ---- half-row chains (k_fill8): TWO chains per DPP row on interleaved lanes -- chain = lane & 1, position = lane >> 1 -- so every hand-off is
+   row_shr:2 and BOTH heads (lanes 0 and 1 of the row) get the head treatment from the DPP control itself: the zero that bound_ctrl fills in /
+   a disabled lane without it.  Same fusing and the same s_nop padding as the row_shr:1 forms above. */
+#ifdef SSW_SIMT_EMU
+SSW_DEV u32 xl_row_shr2_zero(u32 v) { return xl_row_shr_keep<2>(0u, v); }
+SSW_DEV u32 xl_row_shr2_umax(u32 v, u32 b) { return umax32(xl_row_shr_keep<2>(0u, v), b); }
+SSW_DEV void xl_row_shr2_sub_keep(u32& dst, u32 v, u32 b) { dst = xl_row_shr_keep<2>(dst + b, v) - b; }
+#else
+SSW_DEV u32 xl_row_shr2_zero(u32 v) { return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x112, 0xf, 0xf, true); }
+SSW_DEV u32 xl_row_shr2_umax(u32 v, u32 b)
+{
+	u32 r;
+	asm("s_nop 4\n\tv_max_u32_dpp %0, %1, %2 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(v), "v"(b));
+	return r;
+}
+SSW_DEV void xl_row_shr2_sub_keep(u32& dst, u32 v, u32 b)
+{
+	asm("s_nop 4\n\tv_sub_u32_dpp %0, %1, %2 row_shr:2 row_mask:0xf bank_mask:0xf" : "+v"(dst) : "v"(v), "v"(b));
+}
+#endif
+
 #endif /* SSW_LANES_H */

@@ -14,6 +14,7 @@ extern "C" {
 #endif
 
 #define SSW_RMAX 24            /* rows per lane supported by the 16-lane chains: queries up to 16*24 = 384 residues */
+#define SSW_R8MAX 23           /* rows per position of the half-row chains (k_fill8): reads up to 184 residues with len mod 16 in 1..8 */
 #define SSW_MAX_N 32           /* alphabet size limit of the profile kernels (profile residues held in LDS) */
 #define SSW_MAX_N_WIDE 128     /* wider alphabets (33 .. 128 letters: every int8 code) take the lane-model kernel with the matrix in LDS and the thread traceback */
 #define SSW_LDS_LIMIT (160 * 1024)   /* LDS per workgroup on gfx950 */
@@ -472,6 +473,7 @@ int   ssw_shim_stream_wait_event(void* stream, void* ev);   /* later work on `st
 float ssw_shim_event_elapsed_ms(void* start, void* stop);   /* both must have completed */
 
 int ssw_shim_launch_fill(int R, const ssw_fill_args* a, void* stream);
+int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* stream);   /* half-row chains (k_fill8): odd R8 up to SSW_R8MAX, form 3 only; -2: no instance */
 int ssw_shim_fill_class(int R);    /* register class of k_fill<R>: sub-launches of one k_fillm grid share it */
 int ssw_shim_launch_fillm(const ssw_fillm_args* a, const int32_t* host_R, int n, int form, int64_t total_wgs, void* stream);
 int ssw_shim_launch_filldb(int R, const ssw_filldb_args* a, void* stream);

@@ -67,6 +67,7 @@ typedef struct {
 	int pipe_any_count;     /* SSW_GPU_PIPE_EVEN=0: a pipelined series may have a number of launches that the streams do not share evenly (the form before this was measured) */
 	int pipe_low_prio;      /* SSW_GPU_PIPE_PRIO=low: the extra streams of a pipelined series at the LOWEST dispatch priority (the first form of round 6; measured slower) */
 	int pipe_parts;         /* SSW_GPU_PIPE_PARTS=2..8: the number of scratch parts / streams of a pipelined series (default 2; more were measured slower) */
+	int no_fill_half;       /* SSW_GPU_FILL_HALF=0: the 16-lane kernel also where the half-row chains (k_fill8) apply */
 	int no_pipe;            /* SSW_GPU_PIPE=0: the launches of a chunked short-query bucket one after the other on the main stream (the form before round 6) */
 	int no_lit_spec;        /* SSW_GPU_LIT_SPEC=0: the lane-model kernel runs its 16-bit rules after the 8-bit ones (never both side by side: the form before round 6) */
 	int trace_no_cls80;     /* SSW_GPU_TRACE_CLS80=0: no 80-KiB LDS class for the traceback teams (the classes before round 6) */
@@ -170,6 +171,7 @@ static void knobs_load(ssw_knobs* k)
 	k->trace_no_cls80 = env_is("SSW_GPU_TRACE_CLS80", '0');
 	k->no_lit_spec = env_is("SSW_GPU_LIT_SPEC", '0');
 	k->no_pipe = env_is("SSW_GPU_PIPE", '0');
+	k->no_fill_half = env_is("SSW_GPU_FILL_HALF", '0');
 	k->pipe_low_prio = env_is("SSW_GPU_PIPE_PRIO", 'l');
 	k->pipe_any_count = env_is("SSW_GPU_PIPE_EVEN", '0');
 	{ const int v = env_int("SSW_GPU_TRACE_W1MAX", 0); if (v >= 2 && v <= 254) k->trace_w1max = v; }
@@ -625,7 +627,8 @@ static void timing_add(call_acc* acc, const ssw_gpu_timing* t)
 /* queries that share a chain geometry: short queries (<= 384 residues) by R = ceil(len/16) rows per lane, one strip;
    longer ones by their padded length P16, cut into `strips` row strips of lanes*R rows (k_chainx; lanes = 64: the
    wavefront is one chain, 16: four chains per wavefront) */
-typedef struct { int32_t R, strips, P16, lanes, use_x; int32_t first_pair, npairs; int32_t first_q, nq; int32_t tailR; /* k_chainq: rows per lane of the last strip (0: R) */ } bucket;
+typedef struct { int32_t R, strips, P16, lanes, use_x; int32_t first_pair, npairs; int32_t first_q, nq; int32_t tailR; /* k_chainq: rows per lane of the last strip (0: R) */
+                 int32_t half; /* rows per position R8 = 2R - 1 when every read of the bucket pads to P16 - 8 under 16-bit rules (k_fill8), else 0 */ } bucket;
 
 /* Geometry of the strip kernel and its window passes for an alphabet of n letters.  The forward pass of a batch and the reverse pass over
    flagged survivors (of a database search or of a pair list) must bucket a query length the same way: both take it from here. */
@@ -675,7 +678,7 @@ static int32_t win_bucket_key(const win_geom* g, int32_t len, int32_t* P16q)
 /* the strip shape of the bucket `key` whose longest query has the padded length P16 */
 static void win_bucket_shape(bucket* b, const win_geom* g, int32_t key, int32_t P16)
 {
-	b->tailR = 0;
+	b->tailR = 0; b->half = 0;
 	if (key <= SSW_RMAX) { b->R = key; b->strips = 1; b->P16 = 16 * key; b->lanes = 16; b->use_x = 0; return; }
 	b->P16 = P16; b->lanes = g->xlanes; b->use_x = 1;
 	b->strips = (P16 + g->rows - 1) / g->rows;
@@ -1781,16 +1784,50 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 	/* bucket keys (the strip geometry decides them: win_bucket_key) */
 	win_geom geom;
 	win_geom_fill(&geom, &c->kn, n);
-	for (int32_t k = 0; k < nqa; ++k) keys[k].key = win_bucket_key(&geom, keys[k].key, &keys[k].sub);
+	/* Half-row chains (k_fill8): reads with len mod 16 in 1..8 pad to P16 - 8 under 16-bit rules, and eight positions x R8 = 2R - 1 rows are
+	   exactly those rows.  A padded-length class takes them (sub 0; short queries of one class otherwise all carry the same sub) only where
+	   the kernel can actually run: the batch cannot go to the database-search paths or the lane model, and the frame form fits the class.
+	   A class of nothing but such reads is marked as it is.  A class that mixes both kinds of length is SPLIT only when its launches cannot
+	   join a side-by-side grid of 16-lane chains anyway -- its column maxima alone are beyond what that needs of the budget, or the hooks
+	   build runs the buckets one after the other; a small mixed batch keeps the buckets it always had. */
+	int64_t half_maxt = 0;
+	for (int32_t ti = 0; ti < tcount; ++ti) { const int64_t L = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti]; if (L > half_maxt) half_maxt = L; }
+	const int may_db = !c->kn.no_db && (tcount >= 4 || ds) && half_maxt <= 65000 && maxmat <= 49 &&
+	                   (prm->flag == 0 || (!ds && !c->kn.no_dbx && T->total < 0x7fff0000));
+	const int half_ok = !c->kn.no_fill_half && !c->kn.fill_plain && !literal && !may_db;
+	int32_t n_el[SSW_RMAX + 1], n_all[SSW_RMAX + 1];
+	memset(n_el, 0, sizeof n_el); memset(n_all, 0, sizeof n_all);
+	for (int32_t k = 0; k < nqa; ++k) {
+		const int32_t len = keys[k].key;
+		keys[k].key = win_bucket_key(&geom, len, &keys[k].sub);
+		if (half_ok && keys[k].key <= SSW_RMAX) {
+			keys[k].sub = (len - 1) % 16 < 8 && 2 * keys[k].key - 1 <= SSW_R8MAX ? 0 : 1;
+			n_all[keys[k].key]++; n_el[keys[k].key] += keys[k].sub == 0;
+		}
+	}
+	if (half_ok) {
+		int half_class[SSW_RMAX + 1];
+		for (int32_t R = 1; R <= SSW_RMAX; ++R) {
+			int32_t hb, hk;
+			half_class[R] = n_el[R] > 0 && ssw_frame_params(&c->kn, (int64_t)16 * R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 8, &hb, &hk);
+			if (half_class[R] && n_el[R] < n_all[R]) {
+				const int64_t cm_bytes = 8 * ((half_maxt + 15) / 16 * 16 + 16) * (((int64_t)n_all[R] + 1) / 2);      /* both column-maximum streams of the class */
+				half_class[R] = c->kn.serial_buckets || 2 * cm_bytes > (int64_t)c->cm_budget;
+			}
+		}
+		for (int32_t k = 0; k < nqa; ++k) if (keys[k].key <= SSW_RMAX && !half_class[keys[k].key]) keys[k].sub = 1;
+	}
+	const int split_half = half_ok;
 	qsort(keys, (size_t)nqa, sizeof(keyed), keyed_cmp);
 	for (int32_t i = 0; i < nqa; ) {
 		int32_t j = i;
-		while (j < nqa && keys[j].key == keys[i].key) ++j;
+		while (j < nqa && keys[j].key == keys[i].key && (keys[i].key > SSW_RMAX || keys[j].sub == keys[i].sub)) ++j;
 		bucket* nbk = (bucket*)realloc(bk, sizeof(bucket) * (size_t)(nb + 1));
 		if (!nbk) { free(bk); free(order); free(pairs); free(keys); free(qdone); return fail(c, "out of host memory%s", ""); }
 		bk = nbk;
 		bucket b;
 		win_bucket_shape(&b, &geom, keys[i].key, keys[j - 1].sub);       /* (sorted by padded length: the last is the longest of the bucket) */
+		if (split_half && keys[i].key <= SSW_RMAX && keys[i].sub == 0) b.half = 2 * b.R - 1;
 		b.first_q = i; b.nq = j - i; b.first_pair = npairs_total;
 		for (int32_t k = i; k < j; ++k) order[k] = keys[k].q;
 		for (int32_t k = i; k < j; k += 2) {
@@ -2050,10 +2087,11 @@ plan_again:
 					if (pipe && parts > 1 && !c->kn.pipe_any_count && nl % parts) nl += parts - nl % parts;
 					int64_t even = (B->npairs + nl - 1) / nl;                      /* pairs per launch if all launches are alike */
 					const int64_t ncu = c->dev_cus;
-					const int64_t unit = ncu / (bpp > ncu ? ncu : bpp) > 0 ? ncu / (bpp > ncu ? ncu : bpp) : 1;      /* pairs that make one workgroup per compute unit */
+					const int64_t unit = (ncu / (bpp > ncu ? ncu : bpp) > 0 ? ncu / (bpp > ncu ? ncu : bpp) : 1) * (B->half ? 2 : 1);      /* pairs that make one workgroup per compute unit (k_fill8: two pairs per workgroup) */
 					even = (even + unit - 1) / unit * unit;
 					if (even <= chunk) chunk = even;
 					else if (chunk >= unit) chunk = chunk / unit * unit;
+					if (B->half && (chunk & 1) && chunk > 1) --chunk;      /* whole workgroups of two pairs (a chunk of one pair stays: the second chain is dead) */
 				}
 				P->tile = tile; P->halo = halo; P->ntiles = ntiles; P->maxcols = maxcols; P->chunk = chunk; P->dbl = dbl; P->pipe = pipe && chunk < B->npairs ? parts : 0;
 				P->seg = !dbl && !c->kn.no_seg_reduce ;      /* the fill kernels also leave the maxima of 16-column groups, which is all the reduction reads */
@@ -2186,6 +2224,12 @@ plan_again:
 					   the bucket scores more than its padded length x max(mat)); else plain int16 */
 					fa.form = 0; fa.fr_base = 0; fa.fr_kmask = 0;
 					if (fill_form != 0 && ssw_frame_params(&c->kn, (int64_t)16 * B->R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 16, &fa.fr_base, &fa.fr_kmask)) fa.form = 3;
+					/* half-row chains: single-bucket launches of the frame form only (the frame of a chain of 8 positions) */
+					int use_half = 0;
+					if (B->half && !use_x && !conc && fa.form == 3) {
+						int32_t hb = 0, hk = 0;
+						if (ssw_frame_params(&c->kn, (int64_t)16 * B->R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 8, &hb, &hk)) { use_half = 1; fa.fr_base = hb; fa.fr_kmask = hk; }
+					}
 					int xform = 0;
 					int32_t xfr_base = 0, xfr_kmask = 0;
 					if (fill_form != 0 && B->lanes == 64 &&
@@ -2214,6 +2258,9 @@ plan_again:
 					if (conc) {      /* short-query buckets side by side: their workgroups join the grid of their register class (k_fillm, below) */
 						defer[ndefer].fa = fa; defer[ndefer].R = B->R; defer[ndefer].wgs = (int64_t)np * fa.bpp; defer[ndefer].group = ssw_shim_fill_class(B->R) * 2 + (fa.form == 3);
 					} else
+					if (use_half) {
+						if (ssw_shim_launch_fill8(B->half, &fa, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
+					} else
 					if (ssw_shim_launch_fill(B->R, &fa, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
 					if (!conc && !pipe) ssw_shim_event_record(e1, st);      /* (pipe: one event pair around the whole series, below -- the launches overlap) */
 					if (!conc) { c->tm.fill_launches++; if (pipe) c->tm.fill_pipelined++; }
@@ -2224,14 +2271,15 @@ plan_again:
 							int64_t cf = lo - halo > 0 ? lo - halo : 0;
 							cols += hi - cf;
 						}
-						const int64_t lc = cols * (int64_t)(B->lanes * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips)) * 2 * np;
+						const int64_t lc = cols * (int64_t)(use_half ? 8 * B->half : B->lanes * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips)) * 2 * np;
 						c->tm.fill_cells += lc;
 						char nm[48];
-						if (!use_x) snprintf(nm, sizeof nm, "k_fill<%d,%s>", B->R, fa.form == 3 ? "frame" : "int16");
+						if (use_half) snprintf(nm, sizeof nm, "k_fill8<%d,frame>", B->half);
+						else if (!use_x) snprintf(nm, sizeof nm, "k_fill<%d,%s>", B->R, fa.form == 3 ? "frame" : "int16");
 						else if (B->lanes == 64 && B->tailR) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR);
 						else if (B->lanes == 64) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
 						else snprintf(nm, sizeof nm, "k_chainx<%d,16 lanes> x %d strips", B->R, B->strips);
-						note_fill_kernel(c, lc, &best_fill_cells, nm, !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), B->R, B->strips);
+						note_fill_kernel(c, lc, &best_fill_cells, nm, !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
 					}
 					ssw_reduce_args ra;
 					ra.cm16 = d_cm16; ra.cm8 = d_cm8; ra.cm_stride = stride; ra.refLen = refLen; ra.pairs = fa.pairs; ra.npairs = np;

@@ -338,6 +338,240 @@ __global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(R <= 10 ? 7 : 1, 8) k_fi
 	fill_body<R, FORM>(a, (int)blockIdx.x, lds);
 }
 
+/* ================================================================================================
+ * k_fill8: the same fill on HALF-ROW chains (DESIGN.md "Half-row chains").  A chain of 16 lanes x R rows pads a read to a multiple of 16
+ * rows; the reference's 16-bit kernel pads to a multiple of 8, and for reads with len mod 16 in 1..8 the last 8 of the 16R rows are
+ * rows that only the 8-bit rule's column maxima see.  Here a chain is 8 positions x R8 rows = exactly P8 = 8 * ceil(len / 8) rows and a
+ * DPP row of 16 lanes carries TWO chains on interleaved lanes (chain = lane & 1, position = lane >> 1: every hand-off is row_shr:2 and
+ * both heads get lane 0's treatment from the DPP control).  The two chains of a row take the SAME tile of the target for two DIFFERENT
+ * pairs: they share the target ring and its staging, each has its own profile.  grid = ceil(npairs / 2) * bpp workgroups of 256 threads.
+ *
+ * What position 7 hands out IS the 16-bit rule's maximum (rows < P8).  The 8-bit rule's eight further zero-score rows are not computed:
+ * their column maximum has a closed form in what enters them from above,
+ *     v(c) = max(0, Htop(c-1), Ftop(c))       Htop: H of row P8-1, Ftop: the F that enters row P8
+ *     T(j) = max(T(j-1) - gapE, v(j-8) - gapO)
+ *     M(j) = max(v(j) .. v(j-7), T(j))        maximum of column j over rows < P16  =  max(maximum over rows < P8, M(j))
+ * (a value that enters a region of zero scores travels down-right for free for 7 more columns and can only go on through one horizontal
+ * gap; vertical and second gaps never beat that when gapO > gapE -- the only regime of the frame form).  Position 7 parks v (true value)
+ * beside the chain's maximum; the flush takes the 8-column window from the ring and scans T over the 16 columns of a group, carried
+ * from group to group in LDS, from the chain's first traversal column on (inside the halo).
+ *
+ * LDS map: the profile of k_fill with lane index chain * 8 + position (so the 16 lanes of a row read 16 different bank groups), then per
+ * row of 16 lanes the target ring (160 B), per chain 64 x u32 finished maxima and 64 + 8 x u32 parked v (the first 8 mirrored behind the
+ * ring), and one carry word per chain.
+ * ================================================================================================ */
+#define VRING8_BYTES 288      /* 64 + 8 mirrored entries: the flush reads 9 consecutive columns with immediates */
+#define CHAIN8_BYTES (RING_BYTES + 2 * 256 + 2 * VRING8_BYTES + 16)
+
+/* profile of two pairs: word ((b*C + c)*16 + chain*8 + p)*4 + k = scores of residue b against rows p*R + 4c + k of pair `chain`.  All 8R rows
+   are live (zero score below the read); a pair that does not exist gets dead rows: its chain stays at the floor */
+template <int R>
+SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const int8_t* mat, int n,
+                            const int8_t* const (&q)[4], const int (&len)[4], bool live1, int gapE)
+{
+	constexpr int C = ChainGeom<R>::C;
+	const int total = (n + 1) * C * 64;
+	for (int w = first; w < total; w += nthreads) {
+		const int b = w / (C * 64), rem = w - b * (C * 64);
+		const int c = rem >> 6, l = (rem & 63) >> 2, k = rem & 3;
+		const int ch = l >> 3, r = c * 4 + k, row = (l & 7) * R + r;
+		u32 v;
+		if (b == n || (ch && !live1)) v = fr_pack(FR_DEAD, FR_DEAD);
+		else if (r >= R) v = 0;
+		else {
+			int lo = 0, hi = 0;
+			if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
+			if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
+			v = fr_pack(lo + gapE, hi + gapE);
+		}
+		lds_st32(lds, (u32)w * 4u, v);
+	}
+}
+
+/* the 16 lanes of a row finish traversal columns [base, base + 16) of ONE of their two chains: the chain's own maximum (16-bit rule), the
+   closed form of the eight rows below it (8-bit rule), and the maxima over the group.  Every group is scanned, stored or not: T runs from the
+   chain's first column */
+SSW_DEV void fill_flush8(unsigned char* lds, u32 outc, u32 outv, u32 carry, int base, int l16, int store_from, int ncols, bool live,
+                         uint32_t* o16, uint32_t* o8, uint32_t* g16, uint32_t* g8, int fr_base, int fr_kmask, int gapE, int gapO)
+{
+	const int tc = base + l16;
+	const bool in = live && tc >= store_from && tc < ncols;
+	/* column tc was finished by position 7 at step tc + 7; v is parked as a true value, the maximum in the frame of that step */
+	const u32 i8 = lds_ld32(lds, outc + 4u * ((u32)(tc + 7) & 63u)) - pk_dup(fr_phi(tc + 7, 7, 8, fr_base, fr_kmask, gapE));
+	/* v of columns tc - 8 .. tc: slots (tc - 1) & 63 and the eight behind it (mirrored past the end of the ring).  Columns before the chain's
+	   first one: position 7 spends steps 0..6 on the null columns the target ring starts with, where every row is dead -- H stays at the floor and
+	   F below it, so what it parks is v = 0; the slot of column -8 keeps the zero it was initialised with */
+	u32 v[9];
+	const u32 va = outv + 4u * ((u32)(tc - 1) & 63u);
+#pragma unroll
+	for (int k = 0; k < 9; ++k) v[k] = lds_ld32(lds, va + 4u * k);
+	u32 w = pk_max3_nonneg(v[1], v[2], v[3]);
+	w = pk_max3_nonneg(w, v[4], v[5]);
+	w = pk_max3_nonneg(w, v[6], v[7]);
+	w = pk_max(w, v[8]);
+	/* T in the group's own frame, T(base + l) + l * gapE, is a running maximum: a prefix scan over the row, lane 0 taking the previous
+	   group's last value (lane 15 presents it to row_ror:1) */
+	const int lg = l16 * gapE;
+	u32 x = pk_adds(v[0], pk_dup(lg - gapO));
+	const u32 y = l16 == 15 ? lds_ld32(lds, carry) : x;
+	x = pk_max(x, xl_row_ror<1>(y));
+	x = pk_max(x, xl_row_shr_keep<2>(x, x));
+	x = pk_max(x, xl_row_shr_keep<4>(x, x));
+	x = pk_max(x, xl_row_shr_keep<8>(x, x));
+	if (l16 == 15) lds_st32(lds, carry, pk_adds(x, pk_dup(-16 * gapE)));
+	const u32 i16 = pk_max(pk_max(w, i8), pk_adds(x, pk_dup(-lg)));
+	if (in) { o16[tc] = i16; o8[tc] = i8; }
+	if (g16) {
+		u32 m16 = in ? i16 : 0u, m8 = in ? i8 : 0u;
+		m16 = pk_max(m16, xl_row_ror<1>(m16)); m8 = pk_max(m8, xl_row_ror<1>(m8));
+		m16 = pk_max(m16, xl_row_ror<2>(m16)); m8 = pk_max(m8, xl_row_ror<2>(m8));
+		m16 = pk_max(m16, xl_row_ror<4>(m16)); m8 = pk_max(m8, xl_row_ror<4>(m8));
+		m16 = pk_max(m16, xl_row_ror<8>(m16)); m8 = pk_max(m8, xl_row_ror<8>(m8));
+		if (live && l16 == 0 && base >= store_from && base < ncols) { g16[base >> 4] = m16; g8[base >> 4] = m8; }
+	}
+}
+
+template <int R>
+SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* lds)
+{
+	typedef ChainGeom<R> G;
+	constexpr int C = G::C;
+	const int tid = (int)threadIdx.x, l16 = tid & 15, grp = tid >> 4, ch = l16 & 1, pos = l16 >> 1;
+	const int pg = bid / a.bpp, tchunk = bid - pg * a.bpp;      /* pairs 2 pg and 2 pg + 1 */
+	const bool live1 = 2 * pg + 1 < a.npairs;
+	const int gapEi = (int)(a.gapE2 & 0xffffu), gapOi = (int)(a.gapO2 & 0xffffu);
+	const u32 prof_bytes = (u32)(a.n + 1) * G::PSTRIDE;
+	const u32 ring = prof_bytes + (u32)grp * CHAIN8_BYTES, outc = ring + RING_BYTES, outv = outc + 512, carry = outv + 2 * VRING8_BYTES;      /* (chain 1: + 256 / + VRING8_BYTES / + 4) */
+	const u32 nulloff = (u32)a.n * G::PSTRIDE;
+
+	{   /* score profiles of the two pairs, shared by the 16 rows of the workgroup */
+		const int8_t* q[4]; int len[4];
+#pragma unroll
+		for (int k = 0; k < 2; ++k) {
+			const ssw_pair pr = a.pairs[k && !live1 ? 2 * pg : 2 * pg + k];
+			q[2 * k] = a.qcodes + a.qoff[pr.qa];
+			len[2 * k] = (int)(a.qoff[pr.qa + 1] - a.qoff[pr.qa]);
+			q[2 * k + 1] = pr.qb >= 0 ? a.qcodes + a.qoff[pr.qb] : (const int8_t*)0;
+			len[2 * k + 1] = pr.qb >= 0 ? (int)(a.qoff[pr.qb + 1] - a.qoff[pr.qb]) : 0;
+		}
+		build_profile8<R>(lds, tid, 256, a.mat, a.n, q, len, live1, gapEi);
+	}
+
+	/* this row's tile (both chains) */
+	const int t = tchunk * 16 + grp;
+	const bool active = t < a.ntiles;
+	const int tile_lo = active ? t * a.tile : 0;
+	const int tile_hi = active ? (tile_lo + a.tile < a.refLen ? tile_lo + a.tile : a.refLen) : 0;
+	const int c_first = tile_lo - a.halo > 0 ? tile_lo - a.halo : 0;
+	const int ncols = tile_hi - c_first;
+	int maxcols = a.tile + a.halo; if (maxcols > a.refLen) maxcols = a.refLen;
+	const int nsteps = (maxcols + 8 + 15) & ~15;
+	const int8_t* tg = a.tgt + c_first;
+	uint32_t* o16 = a.cm16 + (int64_t)(2 * pg) * a.cm_stride + c_first;      /* (pair 2 pg + 1: + cm_stride / + seg_stride) */
+	uint32_t* o8 = a.cm8 + (int64_t)(2 * pg) * a.cm_stride + c_first;
+	const int store_from = tile_lo - c_first;
+	uint32_t* g16 = a.sg16 ? a.sg16 + (int64_t)(2 * pg) * a.seg_stride + (c_first >> 4) : (uint32_t*)0;
+	uint32_t* g8 = a.sg16 ? a.sg8 + (int64_t)(2 * pg) * a.seg_stride + (c_first >> 4) : (uint32_t*)0;
+
+	/* target ring as in k_fill; the parked v of the columns before the first are zero, T starts below every score */
+	lds_st16(lds, ring + 2u * (48 + l16), nulloff);
+	{
+		int code = l16 < ncols ? tg[l16] : a.n;
+		if (code < 0 || code > a.n) code = a.n;
+		const u32 off = (u32)code * G::PSTRIDE;
+		lds_st16(lds, ring + 2u * l16, off);
+		lds_st16(lds, ring + 2u * (64 + l16), off);
+	}
+#pragma unroll
+	for (int k = 0; k < 9; ++k) lds_st32(lds, outv + 4u * (u32)(l16 + 16 * k), 0u);      /* (both chains' rings: 144 words) */
+	if (l16 < 2) lds_st32(lds, carry + 4u * l16, pk_dup(-gapOi));
+	u32 nxt;
+	{
+		const int tc = 16 + l16;
+		int code = tc < ncols ? tg[tc] : a.n;
+		if (code < 0 || code > a.n) code = a.n;
+		nxt = (u32)code * G::PSTRIDE;
+	}
+	__syncthreads();
+
+	const u32 zero0 = pk_dup(fr_phi(0, pos, 8, a.fr_base, a.fr_kmask, gapEi) - gapEi);
+	u32 fl = zero0 + a.gapE2;
+	u32 H[R], E[R];
+#pragma unroll
+	for (int r = 0; r < R; ++r) { H[r] = zero0; E[r] = fl; }
+	u32 Hlast = zero0, Fout = zero0 + a.gapE2, cmout = zero0, hsave = zero0;
+	const u32 lane_prof = (u32)(ch * 8 + pos) * 16u;
+	const u32 gO = a.gapO2 - a.gapE2, gE = a.gapE2, gE2 = 2u * a.gapE2;
+	const u32 gEv = opaque(gE);
+	u32 fin = 0;
+	const u32 park = outc + (u32)ch * 256u, parkv = outv + (u32)ch * VRING8_BYTES;      /* position 7 of each chain parks what it finishes */
+
+	for (int s0 = 0; s0 < nsteps; s0 += 16) {
+		if (s0 > 0 && (s0 & a.fr_kmask) == 0) {
+			const u32 k = (u32)(a.fr_kmask + 1) * a.gapE2;
+#pragma unroll
+			for (int r = 0; r < R; ++r) { H[r] -= k; E[r] -= k; }
+			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl -= k;
+		}
+		{   /* stage target columns [s0+16, s0+32), prefetch [s0+32, s0+48) */
+			const int p = (s0 + 16 + l16) & 63;
+			lds_st16(lds, ring + 2u * p, nxt);
+			if (p < 16) lds_st16(lds, ring + 2u * (64 + p), nxt);
+			const int tc = s0 + 32 + l16;
+			int code = tc < ncols ? tg[tc] : a.n;
+			if (code < 0 || code > a.n) code = a.n;
+			nxt = (u32)code * G::PSTRIDE;
+		}
+		wave_lds_fence();
+		if (s0 >= 32) {   /* columns [s0-32, s0-16) are complete in the rings, and so are the eight before them */
+			fill_flush8(lds, outc, outv, carry, s0 - 32, l16, store_from, ncols, true, o16, o8, g16, g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
+			fill_flush8(lds, outc + 256, outv + VRING8_BYTES, carry + 4, s0 - 32, l16, store_from, ncols, live1, o16 + a.cm_stride, o8 + a.cm_stride,
+			            g16 ? g16 + a.seg_stride : g16, g16 ? g8 + a.seg_stride : g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
+		}
+		wave_lds_fence();
+		const u32 rp = ring + 2u * (u32)((s0 - pos) & 63);
+		const u32 ob = park + 4u * (u32)(s0 & 63), obv = parkv + 4u * (u32)(s0 & 63);
+		const bool lap = (s0 & 63) == 0;
+#pragma unroll
+		for (int j = 0; j < 16; ++j) {
+			const u32 paddr = lds_ld16(lds, rp + 2u * j) + lane_prof;
+			u32x4 sc[C];
+#pragma unroll
+			for (int c = 0; c < C; ++c) sc[c] = lds_ld128(lds, paddr + 256u * c);
+			const u32 hp = Hlast + gE2;                           /* H of the chain's last row one column back, two columns' frames ahead */
+			const u32 hin = xl_row_shr2_umax(Hlast, fl); fl += gE;
+			xl_row_shr2_sub_keep(fin, Fout, gEv);
+			u32 f = fin, d = hsave;
+			u32 cm = xl_row_shr2_zero(cmout);
+			chain_rows_fr<R, 0, R, true>(sc, H, E, d, f, cm, gO, gE, fl);
+			hsave = hin; Hlast = H[R - 1]; Fout = f; cmout = cm;
+			/* what enters the row below the chain, as a true value: max(0, Htop(c-1), Ftop(c)) -- all three one gapE above the column's frame (f is OPEN) */
+			const u32 vv = pk_max3_fr(f, hp, fl) - fl;
+			if (pos == 7) {
+				lds_st32(lds, ob + 4u * j, cm); lds_st32(lds, obv + 4u * j, vv);
+				if (j < 8 && lap) lds_st32(lds, obv + 256u + 4u * j, vv);      /* slots 0..7 once more behind the ring */
+			}
+		}
+	}
+	wave_lds_fence();
+	for (int base = nsteps - 32; base < nsteps; base += 16)
+		if (base >= 0) {
+			fill_flush8(lds, outc, outv, carry, base, l16, store_from, ncols, true, o16, o8, g16, g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
+			fill_flush8(lds, outc + 256, outv + VRING8_BYTES, carry + 4, base, l16, store_from, ncols, live1, o16 + a.cm_stride, o8 + a.cm_stride,
+			            g16 ? g16 + a.seg_stride : g16, g16 ? g8 + a.seg_stride : g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
+			wave_lds_fence();
+		}
+}
+
+/* register budget per class as for k_fill: up to 9 rows per position 72 registers, up to 15 96, beyond that 128.  (R8 = 19 held to 96
+   registers -- five wavefronts per SIMD, with spills -- measured 2.9 % slower than at 118 registers and four: docs/NOTEBOOK.md) */
+template <int R>
+__global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(R <= 9 ? 7 : R <= 15 ? 5 : 4, 8) k_fill8(ssw_fill_args a)
+{
+	SSW_DYN_LDS(lds);
+	fill_body8<R>(a, (int)blockIdx.x, lds);
+}
+
 /* k_fillm: SEVERAL geometry buckets in one launch (round 4).  A batch of mixed read lengths -- the reference's own benchmark: 1000 reads of
    25-540 bp -- is ~25 buckets with a few pairs each; as 25 launches they queue up behind each other on the four hardware queues and the
    device ends with a long thin tail of small kernels (profiles/round4_config6_timeline.txt).  Here the workgroups of all buckets of one
@@ -3967,6 +4201,23 @@ extern "C" int ssw_shim_launch_fill(int R, const ssw_fill_args* a, void* stream)
 		if (args.form == 3) SSW_LAUNCH((k_fill<r, 3>), ssw_fill_args, args, grid, 256, ldsb, stream); \
 		else SSW_LAUNCH((k_fill<r, 0>), ssw_fill_args, args, grid, 256, ldsb, stream); } break;
 		FOR_EACH_R(X)
+#undef X
+		default: return -2;
+	}
+	return SSW_LAUNCH_OK();
+}
+
+/* half-row chains: R8 = ceil(len / 8) rows per position, odd values up to 23; frame form only */
+extern "C" int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* stream)
+{
+	ssw_fill_args args = *a;
+	const int64_t grid = (int64_t)((args.npairs + 1) / 2) * args.bpp;
+	if (grid <= 0) return 0;
+	if (args.form != 3) return -2;
+	switch (R8) {
+#define X(r) case r: { const size_t ldsb = (size_t)(args.n + 1) * ChainGeom<r>::PSTRIDE + 16 * CHAIN8_BYTES; \
+		SSW_LAUNCH((k_fill8<r>), ssw_fill_args, args, grid, 256, ldsb, stream); } break;
+		X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23)
 #undef X
 		default: return -2;
 	}
