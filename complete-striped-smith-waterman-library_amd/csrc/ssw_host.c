@@ -84,13 +84,14 @@ typedef struct {
 } ssw_knobs;
 
 #define SSW_TSTREAMS 6
+#define SSW_PSTREAMS 7     /* extra streams of a pipelined series: up to 8 parts (SSW_GPU_PIPE_PARTS) */
 #define DB_STREAMS 4                   /* side streams the size classes of a database-search chunk are spread over */
 
 struct ssw_gpu_ctx {
 	int device;
 	void* stream;
 	void* stream2;                      /* reductions of chunk i overlap the fill of chunk i+1 */
-	void* pstream[7]; void* ev_pipe[7]; /* launches 1, 2, .. (mod the number of parts) of a pipelined series of fills (align_batch "pipe"), created with the first series that needs them */
+	void* pstream[SSW_PSTREAMS]; void* ev_pipe[SSW_PSTREAMS]; /* launches 1, 2, .. (mod the number of parts) of a pipelined series of fills (align_batch "pipe"), created with the first series that needs them */
 	void* ustream;                      /* sequence uploads / translation (ssw_gpu_seqs_*): beside a running batch call, see upload_stream() */
 	void* tstream[SSW_TSTREAMS]; void* tev[SSW_TSTREAMS];   /* traceback classes of one negotiation round run side by side */
 	void *ev_fill[2], *ev_red[2];
@@ -106,7 +107,7 @@ struct ssw_gpu_ctx {
 	size_t cm_budget;                   /* bytes allowed for the two column-max buffers */
 	int busy;                           /* a batch call is running on this context (one call at a time per context) */
 	int side_ready;                     /* the side streams exist (ctx_side_streams) */
-	int budget_shrunk;                  /* an allocation failed once: the device is shared, the budget was cut (SSW_ALLOC_RETRY) */
+	int budget_shrunk;                  /* an allocation failed once: the device is shared, the budget was cut (plan_retreat) */
 	ssw_knobs kn;                       /* environment hooks of the running call (knobs_load) */
 	int dev_cus, dev_wave_slots;        /* compute units and resident wavefront slots of the device (hipGetDeviceProperties) */
 	int device_share;                   /* > 1: that many single-pair calls of this process are in flight right now (ssw_align): a small call sizes its tiles for its share of the device */
@@ -281,6 +282,18 @@ static int ctx_side_streams(ssw_gpu_ctx* c)
 	return ok ? 0 : fail(c, "stream/event creation failed: %s", ssw_shim_last_error());
 }
 
+/* Waits for everything a FAILED call may have left queued, on the main stream and on every side stream it can have launched to: its caller
+   frees or reuses the buffers those launches read and write.  (Results ignored: the call reports its own error.) */
+static void ctx_drain(ssw_gpu_ctx* c)
+{
+	ssw_shim_stream_sync(c->stream);
+	if (__atomic_load_n(&c->side_ready, __ATOMIC_ACQUIRE)) {
+		ssw_shim_stream_sync(c->stream2);
+		for (int k = 0; k < SSW_TSTREAMS; ++k) ssw_shim_stream_sync(c->tstream[k]);
+	}
+	for (int k = 0; k < SSW_PSTREAMS; ++k) if (c->pstream[k]) ssw_shim_stream_sync(c->pstream[k]);
+}
+
 const char* ssw_gpu_strerror(int rc)
 {
 	switch (rc) {
@@ -337,7 +350,7 @@ void ssw_gpu_close(ssw_gpu_ctx* c)
 	ssw_shim_event_destroy(c->ev_t0); ssw_shim_event_destroy(c->ev_a); ssw_shim_event_destroy(c->ev_b);
 	ssw_shim_event_destroy(c->ev_c); ssw_shim_event_destroy(c->ev_d); ssw_shim_event_destroy(c->ev_db);
 	for (int i = 0; i < 2; ++i) { ssw_shim_event_destroy(c->ev_fill[i]); ssw_shim_event_destroy(c->ev_red[i]); }
-	ssw_shim_stream_destroy(c->stream2); ssw_shim_stream_destroy(c->ustream); for (int i = 0; i < 7; ++i) { ssw_shim_stream_destroy(c->pstream[i]); ssw_shim_event_destroy(c->ev_pipe[i]); }
+	ssw_shim_stream_destroy(c->stream2); ssw_shim_stream_destroy(c->ustream); for (int i = 0; i < SSW_PSTREAMS; ++i) { ssw_shim_stream_destroy(c->pstream[i]); ssw_shim_event_destroy(c->ev_pipe[i]); }
 	for (int i = 0; i < SSW_TSTREAMS; ++i) { ssw_shim_stream_destroy(c->tstream[i]); ssw_shim_event_destroy(c->tev[i]); }
 	ssw_shim_stream_destroy(c->stream);
 	pthread_mutex_destroy(&c->mu);
@@ -606,6 +619,33 @@ static int stage_append_batch(ssw_gpu_ctx* c, cigar_stage* st, uint32_t* pool, i
 		results[*(const int64_t*)((const char*)idx + idx_stride * (size_t)k)] = r;
 	}
 	st->n += words;
+	return 0;
+}
+/* CIGARs of cnt downloaded records (hres; d_res on the device, their slots in d_cig) on their way into the stage.  goffs[k]: where record
+   k's CIGAR starts, in words from st->n -- the caller advances st->n by *gwords once its records name them.  The used slots are packed into
+   one device pool (k_gather) and come down in one copy, enqueued on the main stream and not waited for.  direct: every CIGAR straight from
+   its slot instead (a handful of alignments: no offset upload, no gather launch). */
+static int cigars_to_stage(ssw_gpu_ctx* c, const ssw_dres* hres, int32_t cnt, const ssw_dres* d_res, const uint32_t* d_cig, cigar_stage* st,
+                           int64_t* goffs, int direct, int64_t* gwords)
+{
+	int64_t at = 0;
+	for (int32_t k = 0; k < cnt; ++k) { goffs[k] = at; if (hres[k].cigarLen > 0 && hres[k].status == 0) at += hres[k].cigarLen; }
+	*gwords = at;
+	if (at == 0) return 0;
+	int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
+	uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)at);
+	if (!d_goff || !d_gpool || stage_reserve(c, st, at)) return -1;
+	if (direct) {
+		for (int32_t k = 0; k < cnt; ++k)
+			if (hres[k].cigarLen > 0 && hres[k].status == 0 &&
+			    ssw_shim_d2h(st->words + st->n + goffs[k], d_cig + hres[k].cigar_off, sizeof(uint32_t) * (size_t)hres[k].cigarLen, c->stream))
+				return fail(c, "CIGAR download failed: %s", ssw_shim_last_error());
+		return 0;
+	}
+	ssw_gather_args ga; ga.src = d_cig; ga.res = d_res; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
+	if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
+	    ssw_shim_d2h(st->words + st->n, d_gpool, sizeof(uint32_t) * (size_t)at, c->stream))
+		return fail(c, "CIGAR download failed: %s", ssw_shim_last_error());
 	return 0;
 }
 
@@ -1621,23 +1661,12 @@ static int survivor_phases(ssw_gpu_ctx* c, const surv_in* si, ssw_dres* hs, ciga
 		}
 		if (ssw_shim_d2h(hs + s0, si->d_sres + s0, sizeof(ssw_dres) * (size_t)cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto out; }
 		int64_t gwords = 0;
-		for (int32_t k = 0; k < cnt; ++k) {
-			const ssw_dres* r = &hs[s0 + k];
-			if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); goto out; }
-			goffs[k] = gwords; pool_off[s0 + k] = st->n + gwords;
-			if (r->cigarLen > 0 && r->status == 0) gwords += r->cigarLen;
-		}
-		if (gwords > 0) {
-			int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)cnt);
-			uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
-			if (!d_goff || !d_gpool || stage_reserve(c, st, gwords)) goto out;
-			ssw_gather_args ga; ga.src = tro.d_cig; ga.res = si->d_sres + s0; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = cnt;
-			if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)cnt, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
-			    ssw_shim_d2h(st->words + st->n, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream) || ssw_shim_stream_sync(c->stream)) {
-				fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); goto out;
-			}
-			st->n += gwords;
-		}
+		for (int32_t k = 0; k < cnt; ++k)
+			if (hs[s0 + k].status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); goto out; }
+		if (cigars_to_stage(c, hs + s0, cnt, si->d_sres + s0, tro.d_cig, st, goffs, 0, &gwords)) goto out;
+		if (gwords > 0 && ssw_shim_stream_sync(c->stream)) { fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); goto out; }
+		for (int32_t k = 0; k < cnt; ++k) pool_off[s0 + k] = st->n + goffs[k];
+		st->n += gwords;
 	}
 	ssw_shim_event_record(c->ev_c, c->stream);
 	if (ssw_shim_stream_sync(c->stream)) { fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto out; }
@@ -1726,80 +1755,109 @@ out:
 }
 
 #define SSW_NOT_STREAMABLE (-3)     /* the fused database-search kernel does not cover this batch: ssw_gpu_search_db takes the generic path */
+#define ALIGN16(x) (((size_t)(x) + 15) / 16 * 16)
 
-static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
-                              const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds)
-{
-	if (!results && !ds) return fail(c, "align_batch: NULL argument%s", "");
-	if (check_seqs(c, "align_batch", Q, T, prm)) return -1;
-	if (tfirst < 0 || tcount < 0 || tfirst + tcount > T->count) return fail(c, "align_batch: target range out of bounds%s", "");
-	if (check_scoring(c, "align_batch", prm)) return -1;
-	/* Alphabets.  The reference takes any int32 n (src/ssw.h:86, ssw.c:826-847).  Up to 32 letters the per-residue score profile of a query
-	   lives in LDS (the profile kernels); 33 .. 128 letters -- every value an int8 code can take -- run on the lane-model kernel, which looks
-	   its scores up in the MATRIX (n x n bytes of LDS) and is exact in every gap regime, and on the thread traceback, which reads the matrix
-	   through the cache: slow (a CPU-class path, like gapO <= gapE), but the reference's answer instead of a refusal.  n > 128: codes are int8,
-	   so only the leading 128 x 128 block of the matrix can ever be addressed -- the kernels get that block; the 8-bit bias is still the minimum
-	   over the WHOLE matrix, as ssw_init computes it (ssw.c:834-836). */
-	const int wide = prm->n > SSW_MAX_N;
-	const int literal = prm->gapO <= prm->gapE || wide;   /* layout-dependent regime of the reference / wide alphabet: lane-model kernel (k_literal) */
-	ssw_shim_set_device(c->device);
-	knobs_load(&c->kn);
-	if ((Q->count > 1 || tcount > 1 || ds) && ctx_side_streams(c)) return -1;      /* (one pair never leaves the main stream) */
-	if (cigar_pool) *cigar_pool = 0;
-	if (cigar_words) *cigar_words = 0;
-	const int32_t nq = Q->count, n = prm->n > SSW_MAX_N_WIDE ? SSW_MAX_N_WIDE : prm->n;
-	if (nq == 0 || tcount == 0) return 0;
-
+/* ------------------------------------------------------------------------------------------------
+ * ssw_gpu_align_batch: every query against every target of a range.  align_batch_locked (below) is the sequence of phases; what they
+ * share lives in two structs.  batch_call: what is fixed for the whole call.  target_plan: what is decided per target.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct { ssw_fill_args fa; int R, group; int64_t wgs; } fill_defer;      /* a short-query bucket that joins a multi-bucket grid */
+typedef struct {
+	const ssw_gpu_seqs* Q; const ssw_gpu_seqs* T; const ssw_gpu_params* prm;
+	int32_t tfirst, tcount, nq;
+	int32_t n;                             /* letters the kernels address (prm->n, at most SSW_MAX_N_WIDE) */
 	int32_t minmat, maxmat, bias;
-	mat_range(prm, &minmat, &maxmat, &bias);
+	int literal;                           /* layout-dependent regime of the reference / wide alphabet: lane-model kernel (k_literal) */
+	int32_t maxlen; int64_t maxt;          /* longest query, longest target of the range */
+	int may_db, use_dbx;                   /* db_gate: the fused database search may answer the call; ... its flagged form */
+	int32_t* order; int32_t nqa;           /* non-empty queries in bucket order */
+	ssw_pair* pairs; int32_t npairs_total;
+	bucket* bk; int nb;
+	uint8_t* qdone;                        /* queries whose records came out of the fused database-search path */
+	win_geom geom;
+	int8_t* d_mat; ssw_pair* d_pairs; int32_t* d_qlist;      /* the call's small inputs on the device (one upload: batch_header) */
+	ssw_dres* d_res;
+	uint32_t gapO2, gapE2;
+	int fill_form;                         /* tests: SSW_GPU_FILL_FORM=0 (or the older SSW_GPU_FILL_F16=0) keeps the plain int16 form everywhere */
+	ssw_dres* hres; int32_t* hneed; int64_t* goffs; cigar_stage pool;      /* host staging: records, traceback needs, CIGAR offsets, CIGARs */
+	/* scratch of the phases, sized by the buckets (batch_buckets) */
+	keyed* keys; unsigned char* hhdr; bplan* bplans;
+	int* border; fill_defer* defer; ssw_reduce_args* rdefer;      /* side-by-side group: buckets by size, deferred fills and reductions */
+	/* running sums of the call */
+	double fill_ms, locate_ms, trace_ms; int64_t best_fill_cells;
+} batch_call;
+/* every heap block of the call */
+static void batch_call_free(batch_call* bc)
+{
+	free(bc->order); free(bc->pairs); free(bc->bk); free(bc->qdone); free(bc->hres); free(bc->hneed); free(bc->goffs); free(bc->pool.words);
+	free(bc->keys); free(bc->hhdr); free(bc->bplans); free(bc->border); free(bc->defer); free(bc->rdefer);
+}
 
-	/* bucket the queries by chain geometry, pair neighbours inside a bucket.  Empty queries take no part: the reference gives
-	   them the empty record (score 0, begins -1; src/ssw.c:900-903), which is what an untouched result record reads as. */
-	int32_t* order = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
-	uint8_t* qdone = (uint8_t*)calloc((size_t)nq, 1);   /* queries whose records came out of the fused database-search path */
-	ssw_pair* pairs = (ssw_pair*)malloc(sizeof(ssw_pair) * ((size_t)nq + 1));
-	keyed* keys = (keyed*)malloc(sizeof(keyed) * (size_t)nq);
-	bucket* bk = 0; int nb = 0;
-	int32_t maxlen = 0, npairs_total = 0, nqa = 0;    /* nqa: non-empty queries = entries of `order` */
-	if (!order || !qdone || !pairs || !keys) { free(order); free(pairs); free(keys); free(qdone); return fail(c, "out of host memory%s", ""); }
+typedef struct {
+	int32_t refLen; const int8_t* d_tgt;
+	int64_t stride;                        /* columns of a column-maximum row */
+	int64_t seg_stride;                    /* rows of the group arrays: 16-byte aligned, padded by >= 4 words (k_reduce_seg loads four groups at a time) */
+	bplan* bp;                             /* [nb] (the call's block) */
+	int nact, max_chunk, any_dbl, any_chunked;
+	int conc;                              /* the buckets run side by side (plan_target) */
+	size_t tot_cm, tot_sg, tot_bnd, tot_cand, tot_q, tot_cs;      /* all buckets side by side */
+	size_t max_cm, max_sg, max_bnd, max_cand;                      /* one bucket at a time */
+	unsigned char *base_cm16, *base_cm8, *base_cmB16, *base_cmB8, *base_sg16, *base_sg8, *base_bnd, *base_cand;      /* plan_alloc */
+	int32_t *base_q, *base_cs;
+} target_plan;
+
+/* The fused database search (k_filldb) may answer the call: several short targets, scores only -- or flagged (begin positions / CIGARs;
+   *use_dbx) with the batched reverse pass and traceback over the pairs that pass the score filter (dbx_chunk, survivor_phases).  The bound on
+   the target set dates from the window kernels' 32-bit column indices into the concatenated targets; they take a 64-bit base per job now
+   (the pair lists run above 2^31 residues), but this path has not been run there, so the bound stays.  k_filldb takes the column maximum
+   of two rows with a 16-bit float max3, valid below 31744: 640 rows x max(mat) <= 49.  Both the half-row class rule (batch_buckets) and
+   the database attempt (batch_try_db) ask here. */
+static int db_gate(const ssw_gpu_ctx* c, const batch_call* bc, const db_stream* ds, int* use_dbx)
+{
+	*use_dbx = bc->prm->flag != 0 && !ds && !c->kn.no_dbx && bc->tcount >= 4 && bc->T->total < 0x7fff0000;
+	return !c->kn.no_db && (bc->tcount >= 4 || ds) && bc->maxt <= 65000 && bc->maxmat <= 49 && (bc->prm->flag == 0 || *use_dbx);
+}
+
+/* bucket the queries by chain geometry, pair neighbours inside a bucket.  Empty queries take no part: the reference gives
+   them the empty record (score 0, begins -1; src/ssw.c:900-903), which is what an untouched result record reads as.
+   Returns with bc->nqa == 0 (and no buckets) when there is nothing but empty queries. */
+static int batch_buckets(ssw_gpu_ctx* c, batch_call* bc, const db_stream* ds)
+{
+	const ssw_gpu_seqs* Q = bc->Q; const ssw_gpu_seqs* T = bc->T; const ssw_gpu_params* prm = bc->prm;
+	const int32_t nq = bc->nq;
+	bc->order = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
+	bc->qdone = (uint8_t*)calloc((size_t)nq, 1);
+	bc->pairs = (ssw_pair*)malloc(sizeof(ssw_pair) * ((size_t)nq + 1));
+	keyed* const keys = bc->keys = (keyed*)malloc(sizeof(keyed) * (size_t)nq);
+	if (!bc->order || !bc->qdone || !bc->pairs || !keys) return fail(c, "out of host memory%s", "");
+	int32_t nqa = 0;
 	for (int32_t q = 0; q < nq; ++q) {
 		int64_t len = Q->h_off[q + 1] - Q->h_off[q];
-		if (len > 0x3fffff00) {
-			free(order); free(pairs); free(keys); free(qdone);
-			return fail(c, "align_batch: query longer than 2^30 residues%s", "");
-		}
+		if (len > 0x3fffff00) return fail(c, "align_batch: query longer than 2^30 residues%s", "");
 		if (len == 0) continue;
-		if (len > maxlen) maxlen = (int32_t)len;
+		if (len > bc->maxlen) bc->maxlen = (int32_t)len;
 		keys[nqa].q = q;
 		keys[nqa].key = (int32_t)len; keys[nqa].sub = 0;      /* (the bucket keys follow below, once the strip geometry is known) */
 		++nqa;
 	}
-	if (nqa == 0 && ds) { free(order); free(pairs); free(keys); free(qdone); return SSW_NOT_STREAMABLE; }
-	if (nqa == 0) {     /* nothing but empty queries */
-		for (int64_t k = 0; k < (int64_t)nq * tcount; ++k) topk_pad(&results[k]);
-		memset(&c->tm, 0, sizeof c->tm);
-		free(order); free(pairs); free(keys); free(qdone);
-		return 0;
-	}
+	bc->nqa = nqa;
+	if (nqa == 0) return 0;
+	for (int32_t ti = 0; ti < bc->tcount; ++ti) { const int64_t L = T->h_off[bc->tfirst + ti + 1] - T->h_off[bc->tfirst + ti]; if (L > bc->maxt) bc->maxt = L; }
+	bc->may_db = db_gate(c, bc, ds, &bc->use_dbx);
 	/* bucket keys (the strip geometry decides them: win_bucket_key) */
-	win_geom geom;
-	win_geom_fill(&geom, &c->kn, n);
+	win_geom_fill(&bc->geom, &c->kn, bc->n);
 	/* Half-row chains (k_fill8): reads with len mod 16 in 1..8 pad to P16 - 8 under 16-bit rules, and eight positions x R8 = 2R - 1 rows are
 	   exactly those rows.  A padded-length class takes them (sub 0; short queries of one class otherwise all carry the same sub) only where
 	   the kernel can actually run: the batch cannot go to the database-search paths or the lane model, and the frame form fits the class.
 	   A class of nothing but such reads is marked as it is.  A class that mixes both kinds of length is SPLIT only when its launches cannot
 	   join a side-by-side grid of 16-lane chains anyway -- its column maxima alone are beyond what that needs of the budget, or the hooks
 	   build runs the buckets one after the other; a small mixed batch keeps the buckets it always had. */
-	int64_t half_maxt = 0;
-	for (int32_t ti = 0; ti < tcount; ++ti) { const int64_t L = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti]; if (L > half_maxt) half_maxt = L; }
-	const int may_db = !c->kn.no_db && (tcount >= 4 || ds) && half_maxt <= 65000 && maxmat <= 49 &&
-	                   (prm->flag == 0 || (!ds && !c->kn.no_dbx && T->total < 0x7fff0000));
-	const int half_ok = !c->kn.no_fill_half && !c->kn.fill_plain && !literal && !may_db;
+	const int half_ok = !c->kn.no_fill_half && !c->kn.fill_plain && !bc->literal && !bc->may_db;
 	int32_t n_el[SSW_RMAX + 1], n_all[SSW_RMAX + 1];
 	memset(n_el, 0, sizeof n_el); memset(n_all, 0, sizeof n_all);
 	for (int32_t k = 0; k < nqa; ++k) {
 		const int32_t len = keys[k].key;
-		keys[k].key = win_bucket_key(&geom, len, &keys[k].sub);
+		keys[k].key = win_bucket_key(&bc->geom, len, &keys[k].sub);
 		if (half_ok && keys[k].key <= SSW_RMAX) {
 			keys[k].sub = (len - 1) % 16 < 8 && 2 * keys[k].key - 1 <= SSW_R8MAX ? 0 : 1;
 			n_all[keys[k].key]++; n_el[keys[k].key] += keys[k].sub == 0;
@@ -1809,686 +1867,825 @@ static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_g
 		int half_class[SSW_RMAX + 1];
 		for (int32_t R = 1; R <= SSW_RMAX; ++R) {
 			int32_t hb, hk;
-			half_class[R] = n_el[R] > 0 && ssw_frame_params(&c->kn, (int64_t)16 * R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 8, &hb, &hk);
+			half_class[R] = n_el[R] > 0 && ssw_frame_params(&c->kn, (int64_t)16 * R * (bc->maxmat > 0 ? bc->maxmat : 0), prm->gapO, prm->gapE, bc->minmat, 8, &hb, &hk);
 			if (half_class[R] && n_el[R] < n_all[R]) {
-				const int64_t cm_bytes = 8 * ((half_maxt + 15) / 16 * 16 + 16) * (((int64_t)n_all[R] + 1) / 2);      /* both column-maximum streams of the class */
+				const int64_t cm_bytes = 8 * ((bc->maxt + 15) / 16 * 16 + 16) * (((int64_t)n_all[R] + 1) / 2);      /* both column-maximum streams of the class */
 				half_class[R] = c->kn.serial_buckets || 2 * cm_bytes > (int64_t)c->cm_budget;
 			}
 		}
 		for (int32_t k = 0; k < nqa; ++k) if (keys[k].key <= SSW_RMAX && !half_class[keys[k].key]) keys[k].sub = 1;
 	}
-	const int split_half = half_ok;
 	qsort(keys, (size_t)nqa, sizeof(keyed), keyed_cmp);
 	for (int32_t i = 0; i < nqa; ) {
 		int32_t j = i;
 		while (j < nqa && keys[j].key == keys[i].key && (keys[i].key > SSW_RMAX || keys[j].sub == keys[i].sub)) ++j;
-		bucket* nbk = (bucket*)realloc(bk, sizeof(bucket) * (size_t)(nb + 1));
-		if (!nbk) { free(bk); free(order); free(pairs); free(keys); free(qdone); return fail(c, "out of host memory%s", ""); }
-		bk = nbk;
+		bucket* nbk = (bucket*)realloc(bc->bk, sizeof(bucket) * (size_t)(bc->nb + 1));
+		if (!nbk) return fail(c, "out of host memory%s", "");
+		bc->bk = nbk;
 		bucket b;
-		win_bucket_shape(&b, &geom, keys[i].key, keys[j - 1].sub);       /* (sorted by padded length: the last is the longest of the bucket) */
-		if (split_half && keys[i].key <= SSW_RMAX && keys[i].sub == 0) b.half = 2 * b.R - 1;
-		b.first_q = i; b.nq = j - i; b.first_pair = npairs_total;
-		for (int32_t k = i; k < j; ++k) order[k] = keys[k].q;
+		win_bucket_shape(&b, &bc->geom, keys[i].key, keys[j - 1].sub);       /* (sorted by padded length: the last is the longest of the bucket) */
+		if (half_ok && keys[i].key <= SSW_RMAX && keys[i].sub == 0) b.half = 2 * b.R - 1;
+		b.first_q = i; b.nq = j - i; b.first_pair = bc->npairs_total;
+		for (int32_t k = i; k < j; ++k) bc->order[k] = keys[k].q;
 		for (int32_t k = i; k < j; k += 2) {
-			pairs[npairs_total].qa = order[k];
-			pairs[npairs_total].qb = k + 1 < j ? order[k + 1] : -1;
-			++npairs_total;
+			bc->pairs[bc->npairs_total].qa = bc->order[k];
+			bc->pairs[bc->npairs_total].qb = k + 1 < j ? bc->order[k + 1] : -1;
+			++bc->npairs_total;
 		}
-		b.npairs = npairs_total - b.first_pair;
-		bk[nb++] = b;
+		b.npairs = bc->npairs_total - b.first_pair;
+		bc->bk[bc->nb++] = b;
 		i = j;
 	}
-	free(keys);
+	return 0;
+}
 
-	int rc = -1;
-	bplan* bplans = 0;
-	unsigned char* hhdr = 0;      /* host copy of the packed small inputs */
-	struct fill_defer { ssw_fill_args fa; int R, group; int64_t wgs; } *defer = 0;      /* short-query buckets that join a multi-bucket grid */
-	ssw_reduce_args* rdefer = 0;                                                          /* ... and the reductions of all buckets of a side-by-side group */
-	int* border = (int*)malloc(sizeof(int) * (size_t)(nb > 0 ? nb : 1));      /* buckets by size (side-by-side launches go largest first) */
-	cigar_stage pool; memset(&pool, 0, sizeof pool);
-	ssw_dres* hres = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)nq);
-	int32_t* hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
-	memset(&c->tm, 0, sizeof c->tm);
-	c->nev = 0;
-	if (!hres || !hneed || !border) { fail(c, "out of host memory%s", ""); goto done; }
-
-	/* the call's small inputs -- scoring matrix, query pairs, bucket-ordered query list -- travel in ONE upload (a single-pair ssw_align call is
-	   bound by the number of dependent operations on its stream, not by their size: profiles/round4_latency.txt) */
-	const size_t hdr_mat = ((size_t)n * n + 15) / 16 * 16, hdr_pairs = (sizeof(ssw_pair) * (size_t)npairs_total + 15) / 16 * 16;
-	const size_t hdr_bytes = hdr_mat + hdr_pairs + sizeof(int32_t) * (size_t)nq;
+/* the call's small inputs -- scoring matrix, query pairs, bucket-ordered query list -- travel in ONE upload (a single-pair ssw_align call is
+   bound by the number of dependent operations on its stream, not by their size: profiles/round4_latency.txt) */
+static int batch_header(ssw_gpu_ctx* c, batch_call* bc)
+{
+	const ssw_gpu_params* prm = bc->prm;
+	const int32_t n = bc->n;
+	const size_t hdr_mat = ((size_t)n * n + 15) / 16 * 16, hdr_pairs = (sizeof(ssw_pair) * (size_t)bc->npairs_total + 15) / 16 * 16;
+	const size_t hdr_bytes = hdr_mat + hdr_pairs + sizeof(int32_t) * (size_t)bc->nq;
 	unsigned char* d_hdr = (unsigned char*)ensure(c, &c->mat, hdr_bytes);
-	ssw_dres* d_res = (ssw_dres*)ensure(c, &c->res, sizeof(ssw_dres) * (size_t)nq);
-	hhdr = (unsigned char*)malloc(hdr_bytes);
-	if (!d_hdr || !d_res) goto done;
-	if (!hhdr) { fail(c, "out of host memory%s", ""); goto done; }
-	int8_t* d_mat = (int8_t*)d_hdr;
-	ssw_pair* d_pairs = (ssw_pair*)(d_hdr + hdr_mat);
-	int32_t* d_qlist = (int32_t*)(d_hdr + hdr_mat + hdr_pairs);
+	bc->d_res = (ssw_dres*)ensure(c, &c->res, sizeof(ssw_dres) * (size_t)bc->nq);
+	unsigned char* const hhdr = bc->hhdr = (unsigned char*)malloc(hdr_bytes);      /* host copy of the packed small inputs */
+	if (!d_hdr || !bc->d_res) return -1;
+	if (!hhdr) return fail(c, "out of host memory%s", "");
+	bc->d_mat = (int8_t*)d_hdr;
+	bc->d_pairs = (ssw_pair*)(d_hdr + hdr_mat);
+	bc->d_qlist = (int32_t*)(d_hdr + hdr_mat + hdr_pairs);
 	if (n == prm->n) memcpy(hhdr, prm->mat, (size_t)n * n);
 	else for (int32_t r = 0; r < n; ++r) memcpy(hhdr + (size_t)r * n, prm->mat + (size_t)r * prm->n, (size_t)n);      /* the addressable block of a matrix wider than int8 codes */
-	memcpy(hhdr + hdr_mat, pairs, sizeof(ssw_pair) * (size_t)npairs_total);
-	memcpy(hhdr + hdr_mat + hdr_pairs, order, sizeof(int32_t) * (size_t)nqa);
+	memcpy(hhdr + hdr_mat, bc->pairs, sizeof(ssw_pair) * (size_t)bc->npairs_total);
+	memcpy(hhdr + hdr_mat + hdr_pairs, bc->order, sizeof(int32_t) * (size_t)bc->nqa);
 	ssw_shim_event_record(c->ev_t0, c->stream);
 	CALL_TRACE("entry: bucketed, buffers ready");
-	if (ssw_shim_h2d(d_hdr, hhdr, hdr_mat + hdr_pairs + sizeof(int32_t) * (size_t)nqa, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+	if (ssw_shim_h2d(d_hdr, hhdr, hdr_mat + hdr_pairs + sizeof(int32_t) * (size_t)bc->nqa, c->stream)) return fail(c, "upload failed: %s", ssw_shim_last_error());
+	return 0;
+}
 
-	const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
-	double fill_ms = 0, reduce_ms = 0, locate_ms = 0, trace_ms = 0;
-	const int fill_form = c->kn.fill_plain ? 0 : -1;      /* tests: SSW_GPU_FILL_FORM=0 (or the older SSW_GPU_FILL_F16=0) keeps the plain int16 form everywhere */
+/* the call's timing record and its CIGAR pool, handed to the caller */
+static void batch_totals(ssw_gpu_ctx* c, batch_call* bc, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	c->tm.total_ms = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_d); c->tm.fill_ms = bc->fill_ms; c->tm.locate_ms = bc->locate_ms; c->tm.trace_ms = bc->trace_ms;
+	c->tm.reduce_ms = c->tm.total_ms - bc->fill_ms - bc->locate_ms - bc->trace_ms;   /* reduction + transfers: everything that is not one of the three timed phases */
+	if (c->tm.reduce_ms < 0) c->tm.reduce_ms = 0;
+	if (cigar_pool) { *cigar_pool = bc->pool.words; bc->pool.words = 0; }
+	if (cigar_words) *cigar_words = bc->pool.n;
+}
 
-	{   /* database search: scores only, several short targets -> fused kernel for the short-query buckets */
-		int any_short = 0, any_long = 0; int64_t maxt = 0;
-		for (int b = 0; b < nb; ++b) { if (bk[b].use_x && (bk[b].P16 > 640 || (int64_t)n * 10 * 256 > 65535)) any_long = 1; else any_short = 1; }
-		for (int32_t ti = 0; ti < tcount; ++ti) { int64_t L = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti]; if (L > maxt) maxt = L; }
-		/* (k_filldb takes the column maximum of two rows with a 16-bit float max3, valid below 31744: 640 rows x max(mat) <= 49) */
-		/* flagged batches (begin positions / CIGARs) against several targets: the same fused search + one batched reverse pass and traceback
-		   over the pairs that pass the score filter (dbx_chunk, survivor_phases).  The bound on the target set dates from the window kernels' 32-bit column
-		   indices into the concatenated targets; they take a 64-bit base per job now (the pair lists run above 2^31 residues), but this path has
-		   not been run there, so the bound stays */
-		const int use_dbx = prm->flag != 0 && !ds && !c->kn.no_dbx && tcount >= 4 && T->total < 0x7fff0000;
-		const int db_ok = !literal && (prm->flag == 0 || use_dbx) && any_short && maxt <= 65000 && maxmat <= 49 && !c->kn.no_db;
-		dbx_state dxs; memset(&dxs, 0, sizeof dxs);
-		if (use_dbx) {
-			dxs.order = order; dxs.nqa = nqa; dxs.d_order = d_qlist; dxs.maxmat = maxmat; dxs.minmat = minmat; dxs.maxt = (int32_t)(maxt > 0x7fffffff ? 0x7fffffff : maxt);
-			dxs.g = geom; dxs.fill_form = fill_form; dxs.stage = &pool;
+/* database search: several short targets -> fused kernel for the short-query buckets (scores only, or flagged: db_gate).
+   Returns 0: go on with the generic path (for the queries not marked in qdone), 1: the call is answered, SSW_NOT_STREAMABLE, -1: error. */
+static int batch_try_db(ssw_gpu_ctx* c, batch_call* bc, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds)
+{
+	const ssw_gpu_seqs* Q = bc->Q;
+	const int32_t n = bc->n;
+	const int mid_ok = (int64_t)n * 10 * 256 <= 65535;     /* 40 rows per lane: 10 chunks of 256 bytes per residue; n x that must stay a 16-bit offset */
+	int any_short = 0, any_long = 0;
+	for (int b = 0; b < bc->nb; ++b) { if (bc->bk[b].use_x && (bc->bk[b].P16 > 640 || !mid_ok)) any_long = 1; else any_short = 1; }
+	const int db_ok = !bc->literal && any_short && bc->may_db;
+	if (ds && (!db_ok || any_long)) return SSW_NOT_STREAMABLE;
+	if (!db_ok) return 0;
+	dbx_state dxs; memset(&dxs, 0, sizeof dxs);
+	if (bc->use_dbx) {
+		dxs.order = bc->order; dxs.nqa = bc->nqa; dxs.d_order = bc->d_qlist; dxs.maxmat = bc->maxmat; dxs.minmat = bc->minmat; dxs.maxt = (int32_t)bc->maxt;
+		dxs.g = bc->geom; dxs.fill_form = bc->fill_form; dxs.stage = &bc->pool;
+	}
+	for (int b = 0; b < bc->nb; ++b) if (!bc->bk[b].use_x || (bc->bk[b].P16 <= 640 && mid_ok)) for (int32_t k = 0; k < bc->bk[b].nq; ++k) {
+		const int32_t qq = bc->order[bc->bk[b].first_q + k];
+		bc->qdone[qq] = 1;
+		if (Q->h_off[qq + 1] - Q->h_off[qq] > dxs.maxlen) dxs.maxlen = (int32_t)(Q->h_off[qq + 1] - Q->h_off[qq]);
+	}
+	for (int32_t q = 0; q < bc->nq; ++q) if (Q->h_off[q + 1] == Q->h_off[q]) bc->qdone[q] = 1;     /* empty queries: empty records, written there */
+	const int db_rc = align_db(c, Q, bc->T, bc->tfirst, bc->tcount, bc->prm, results, bc->bk, bc->nb, bc->d_pairs, bc->d_mat, bc->bias, (int32_t)bc->maxt, bc->qdone, ds,
+	                           bc->use_dbx ? &dxs : 0);
+	free(dxs.hs); free(dxs.hvq); free(dxs.hvt); free(dxs.hpo);      /* (the survivors' host copies were patched into the records inside) */
+	if (db_rc) return -1;
+	bc->d_res = (ssw_dres*)ensure(c, &c->res, sizeof(ssw_dres) * (size_t)bc->nq);   /* align_db may have regrown the record buffer */
+	if (!bc->d_res) return -1;
+	bc->locate_ms += dxs.locate_ms; bc->trace_ms += dxs.trace_ms;
+	if (any_long) return 0;
+	/* nothing left for the generic path */
+	ssw_shim_event_record(c->ev_d, c->stream);
+	if (ssw_shim_stream_sync(c->stream)) return fail(c, "stream sync failed: %s", ssw_shim_last_error());
+	for (int e = 0; e + 1 < c->nev; e += 2) bc->fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
+	batch_totals(c, bc, cigar_pool, cigar_words);
+	return 1;
+}
+
+/* gapO <= gapE and wide alphabets: the lane-model kernel, both passes */
+static int literal_fill(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp)
+{
+	const ssw_gpu_seqs* Q = bc->Q; const ssw_gpu_params* prm = bc->prm;
+	const int32_t nq = bc->nq, nqa = bc->nqa, refLen = tp->refLen;
+	/* scratch per alignment: 4 x [segments][16] int16 + codes + maxColumn (sized for the 16-bit kernel: 8 lanes) */
+	const int64_t seg8 = ((int64_t)bc->maxlen + 7) / 8;
+	const int64_t lstate = (seg8 * 16 * 2 * 4 + seg8 * 16 + 64 + 15) / 16 * 16;
+	const int64_t sstr = (lstate + (int64_t)refLen * 2 + 64 + 15) / 16 * 16;
+	int64_t per = (int64_t)(c->cm_budget / (size_t)sstr); if (per < 1) per = 1;
+	/* A forward pass that leaves most of the device idle (round 6; the device holds ~50 alignments of this kernel per compute unit) runs BOTH
+	   rule sets of every query side by side instead of the 16-bit kernel after the 8-bit one saturated: 2 000 reads x 1 Mb took two kernel
+	   lengths on a sixth of the device (45 GCUPS against the reference's 63 on the box's 16 cores, round-5 verdict weak #8). */
+	const int spec = prm->score_size == 2 && !c->kn.no_lit_spec && 2 * (int64_t)nqa + 4 <= (int64_t)c->dev_cus * 48 && per >= 2 * (int64_t)nqa + 4;
+	int32_t* d_spec = 0;
+	if (spec) {
+		d_spec = (int32_t*)ensure(c, &c->cand, sizeof(int32_t) * 17 * (size_t)nq);      /* [nq counters][nq x 2 x 8 outcomes] */
+		if (!d_spec) return -1;
+		if (ssw_shim_memset(d_spec, 0, sizeof(int32_t) * (size_t)nq, c->stream)) return fail(c, "memset failed: %s", ssw_shim_last_error());
+	}
+	void* e0 = next_event(c); void* e1 = next_event(c);
+	ssw_shim_event_record(e0, c->stream);
+	for (int pass = 0; pass < (prm->flag != 0 ? 2 : 1); ++pass)
+		for (int32_t q0 = 0; q0 < nqa; q0 += (int32_t)per) {      /* (d_qlist holds the nqa NON-EMPTY queries; empty ones keep the zeroed record) */
+			const int32_t cnt_q = nqa - q0 < per ? nqa - q0 : (int32_t)per;
+			const int64_t regions = spec && pass == 0 ? (((int64_t)cnt_q + 3) & ~(int64_t)3) + cnt_q : cnt_q;      /* (spec: one launch takes all of them, per >= 2 nqa + 4) */
+			uint8_t* d_scr = (uint8_t*)ensure(c, &c->scratch, (size_t)(sstr * regions));
+			if (!d_scr) return -1;
+			ssw_literal_args la;
+			la.spec_cnt = spec && pass == 0 ? d_spec : 0; la.spec_out = spec && pass == 0 ? d_spec + nq : 0;
+			la.tgt = tp->d_tgt; la.refLen = refLen; la.qcodes = Q->d_codes; la.qoff = Q->d_off; la.qlist = bc->d_qlist + q0; la.nq = cnt_q;
+			la.mat = bc->d_mat; la.n = bc->n; la.gapO = prm->gapO; la.gapE = prm->gapE; la.pass = pass; la.maskLen = prm->maskLen; la.bias = bc->bias;
+			la.score_size = prm->score_size; la.flag = prm->flag; la.filters = prm->filters; la.filterd = prm->filterd; la.res = bc->d_res;
+			la.scratch = d_scr; la.scratch_stride = sstr; la.mc_off = lstate; la.state_bytes = lstate; la.lds_stride = 0;
+			if (ssw_shim_launch_literal(&la, c->stream)) return fail(c, "literal launch failed: %s", ssw_shim_last_error());
 		}
-		if (ds && (!db_ok || any_long)) { rc = SSW_NOT_STREAMABLE; goto done; }
-		if (db_ok && (tcount >= 4 || ds)) {
-			const int mid_ok = (int64_t)n * 10 * 256 <= 65535;     /* 40 rows per lane: 10 chunks of 256 bytes per residue; n x that must stay a 16-bit offset */
-			for (int b = 0; b < nb; ++b) if (!bk[b].use_x || (bk[b].P16 <= 640 && mid_ok)) for (int32_t k = 0; k < bk[b].nq; ++k) {
-				const int32_t qq = order[bk[b].first_q + k];
-				qdone[qq] = 1;
-				if (Q->h_off[qq + 1] - Q->h_off[qq] > dxs.maxlen) dxs.maxlen = (int32_t)(Q->h_off[qq + 1] - Q->h_off[qq]);
-			}
-			for (int32_t q = 0; q < nq; ++q) if (Q->h_off[q + 1] == Q->h_off[q]) qdone[q] = 1;     /* empty queries: empty records, written there */
-			{
-				const int db_rc = align_db(c, Q, T, tfirst, tcount, prm, results, bk, nb, d_pairs, d_mat, bias, (int32_t)maxt, qdone, ds, use_dbx ? &dxs : 0);
-				free(dxs.hs); free(dxs.hvq); free(dxs.hvt); free(dxs.hpo); dxs.hs = 0; dxs.hvq = 0; dxs.hvt = 0; dxs.hpo = 0;      /* (the survivors' host copies were patched into the records inside) */
-				if (db_rc) goto done;
-			}
-			d_res = (ssw_dres*)ensure(c, &c->res, sizeof(ssw_dres) * (size_t)nq);   /* align_db may have regrown the record buffer */
-			if (!d_res) goto done;
-			locate_ms += dxs.locate_ms; trace_ms += dxs.trace_ms;
+	ssw_shim_event_record(e1, c->stream);
+	c->tm.fill_launches++;
+	for (int32_t q = 0; q < nq; ++q) c->tm.fill_cells += (Q->h_off[q + 1] - Q->h_off[q]) * (int64_t)refLen;
+	note_fill_kernel(c, c->tm.fill_cells, &bc->best_fill_cells, "k_literal (lane model of the SSE2 kernels)", 0.0, 0, 1);
+	return 0;
+}
 
-			if (!any_long) {
-				ssw_shim_event_record(c->ev_d, c->stream);
-				if (ssw_shim_stream_sync(c->stream)) { fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto done; }
-				for (int e = 0; e + 1 < c->nev; e += 2) fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
-				c->tm.total_ms = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_d); c->tm.fill_ms = fill_ms;
-				c->tm.locate_ms = dxs.locate_ms; c->tm.trace_ms = dxs.trace_ms;
-				c->tm.reduce_ms = c->tm.total_ms - fill_ms - dxs.locate_ms - dxs.trace_ms; if (c->tm.reduce_ms < 0) c->tm.reduce_ms = 0;
-				if (cigar_pool) { *cigar_pool = pool.words; pool.words = 0; }
-				if (cigar_words) *cigar_words = pool.n;
-				rc = 0;
-				goto done;
-			}
+/* Tile geometry, launch size and scratch of one bucket against one target, into *P (its slice offsets are plan_target's).  Pure: reads the
+   context's knobs, budget and device sizes; allocates nothing, launches nothing, writes nothing but *P. */
+static void plan_bucket(const ssw_gpu_ctx* c, const batch_call* bc, const target_plan* tp, const bucket* B, bplan* P)
+{
+	const int32_t refLen = tp->refLen;
+	const int64_t stride = tp->stride;
+	const int32_t Pq = B->P16, halo_full = halo_for(Pq, bc->maxmat, bc->prm->gapE);
+	const int use_x = B->use_x;     /* long queries: strip kernel, one job per chain */
+	const int gran = use_x ? 1 : 16;     /* k_fill: one workgroup = 16 tiles of one pair */
+	int32_t tile, halo, ntiles;
+	int64_t want = 1;
+	int small_call = 0;
+	if ((int64_t)halo_full * 8 * gran < refLen) {
+		/* enough chains PER LAUNCH to fill the device several times over, halo overhead <= 1/8.  A launch covers the pairs
+		   whose column-maximum arrays fit the budget (8 bytes per column and pair): a 5 Mb target leaves 1600 pairs per
+		   launch, which with 16 tiles (one workgroup) per pair would fill little more than half of the device */
+		int64_t launch_pairs = use_x ? B->npairs : (int64_t)(c->cm_budget / (size_t)(8 * stride));
+		if (launch_pairs < 1) launch_pairs = 1;
+		if (launch_pairs > B->npairs) launch_pairs = B->npairs;
+		want = (4 * 32768 + B->npairs - 1) / B->npairs;
+		if (!use_x && launch_pairs * ((want + 15) / 16) < 6000) want = 16 * ((6000 + launch_pairs - 1) / launch_pairs);   /* >= ~2 rounds of workgroups per launch */
+		int64_t maxt = refLen / ((int64_t)halo_full * 8);
+		if (want > maxt) want = maxt;
+		want = (want + gran - 1) / gran * gran; if (want < gran) want = gran;      /* whole workgroups of 16 chains */
+	}
+	{
+		/* A call that cannot fill the device anyway -- one ssw_align pair, a handful of reads -- is bound by the LATENCY of a chain, tile +
+		   halo columns in sequence: then the tiles go down to half the halo (at least 64 columns) as long as all chains of the
+		   call still fit the device at once (since round 5: down to an eighth of the halo); the recomputed halos run on compute units that would idle.  One 150-bp read against a
+		   10-kb target: 736 steps instead of 10 000 (2.3 -> 0.x ms per ssw_align call, profiles/round4_latency.txt). */
+		/* chains a latency-bound call spreads over: for the 16-lane chains TWO workgroups (32 chains, two wavefronts per SIMD) per compute
+		   unit -- a step of a lone wavefront is bound by the latency of its dependent instructions (~800 cycles for ~75), a second one hides
+		   in it, a third and fourth only share the issue port (measured: 977 workgroups on 256 CUs 0.61 ms per call, 260: 0.57) */
+		int64_t slots = use_x ? (int64_t)c->dev_wave_slots : (int64_t)c->dev_cus * (c->device_share > 1 ? 96 : 32);      /* (several caller threads: what the device holds, shared below) */
+		if (c->device_share > 1) { slots /= c->device_share; if (slots < 256) slots = 256; }      /* other caller threads' pairs are on the device too */
+		const int64_t all_pairs = bc->npairs_total > 0 ? bc->npairs_total : 1;
+		if (all_pairs * want < slots && halo_full < refLen) {
+			/* (round 5: an eighth of the halo, not half -- a chain's latency is tile + halo steps and the halo is fixed; one 150-bp read against
+			   1 Mb: k_fill 240 -> ~185 us of the call's 0.53 ms, profiles/round5_latency_single_pair.json) */
+			/* ... for the 16-lane chains of a call that is alone on the device; the strip kernel (two wavefronts per SIMD by its LDS) and
+			   calls that share the device with other caller threads keep half a halo: their extra chains would only queue up */
+			const int div = !use_x && c->device_share <= 1 ? 8 : 2;
+			const int64_t mint = halo_full / div > 64 ? halo_full / div : 64;
+			int64_t small = slots / all_pairs;
+			if (small > refLen / mint) small = refLen / mint;
+			if (small > want) { want = small; small_call = 1; }
 		}
 	}
-	int64_t best_fill_cells = 0;
+	if (want <= 1) { ntiles = 1; tile = (refLen + 15) / 16 * 16; halo = 0; }
+	else {
+		if (!small_call || want >= gran) want = (want + gran - 1) / gran * gran;      /* (a small call may have fewer tiles than a workgroup has chains: the others stay idle) */
+		tile = (int32_t)(((refLen + want - 1) / want + 15) / 16 * 16);
+		ntiles = (refLen + tile - 1) / tile; halo = (halo_full + 15) / 16 * 16;     /* (more halo is always exact; multiples of 16 keep the 16-column groups inside one tile) */
+		if (ntiles <= 1) { ntiles = 1; tile = (refLen + 15) / 16 * 16; halo = 0; }
+	}
+	const int64_t maxcols = (((int64_t)tile + halo < refLen ? (int64_t)tile + halo : refLen) + 31) / 16 * 16;
+	int64_t per_pair = 8 * stride + (use_x ? 16 * maxcols * ntiles : 0);
+	int64_t chunk = (int64_t)(c->cm_budget / (size_t)per_pair);
+	/* optional: two column-maximum buffer sets so that k_reduce of chunk i runs on a second stream beside k_fill of chunk i+1 */
+	/* measured on MI355X (config 2): overlapping costs more than it saves -- the fill runs at ~100 % VALU issue, so the
+	   reduction's waves only take slots from it (2347 ms/step with, 2160 ms without); kept as an opt-in experiment */
+	const int dbl = !use_x && chunk < B->npairs && c->kn.overlap;
+	/* Pipelined launches (round 6).  A bucket that needs several launches -- its column maxima do not fit the budget at once -- used to
+	   run them one after the other on one stream, and every launch ended with a last, partly filled round of workgroups: all
+	   workgroups of a launch take the same ~50 ms (config 2), so the device drains for most of a workgroup's duration at two or three
+	   workgroups per compute unit instead of seven -- three times per 100 000 reads at a whole-HBM budget, 25 times at 16 GiB (-4 %).
+	   Now the launches alternate between the main stream and a second stream, each with its own half of the scratch: the two
+	   launches in flight share the compute units, each one's drain and reduction is covered by the other, and launch i + 2 follows
+	   the reduction of launch i on its stream.  Same work, same records; only the order in which workgroups reach the compute
+	   units changes.  The second stream has the main stream's priority: at the LOWEST priority (the first form; SSW_GPU_PIPE_PRIO=low
+	   in the hooks build) its launches only got the slots the main stream's left over, fell behind and ran out the series alone --
+	   config 2 on one box, two / four / eight parts at the lowest priority against two at equal priority: 10 073 / 10 211 / 10 282 /
+	   10 353 GCUPS under 16 GiB, 10 377 / 10 446 / 10 423 / 10 480 under 64 GiB, 10 398-10 437 / 10 413 / 10 443 / 10 469-10 514 with
+	   the whole HBM; more than two parts at equal priority lose again (10 127 under 64 GiB: the streams share hardware queues).
+	   profiles/round6_pipeline_parts.txt. */
+	const int pipe = !use_x && !dbl && chunk < B->npairs && !c->kn.no_pipe;
+	int parts = dbl || pipe ? 2 : 1;
+	if (pipe && c->kn.pipe_parts) parts = c->kn.pipe_parts;
+	if (parts > 1) chunk = (int64_t)((c->cm_budget / (size_t)parts) / (size_t)per_pair);
+	if (chunk < 1) chunk = 1;
+	if (chunk > B->npairs) chunk = B->npairs;
+	if (!use_x && chunk < B->npairs) {
+		/* All workgroups of a launch do the same amount of work, so a launch is as slow as the CU that got one workgroup more
+		   than the others: the launches of a bucket get the same number of pairs (not full chunks and a remainder), and that
+		   number makes the workgroup count a multiple of the CU count (256 on an unpartitioned MI355X; read from the device).
+		   16 tiles per pair left 1600 workgroups per launch on a 5 Mb target: 6 or 7 per CU, 12 % lost. */
+		const int64_t bpp = (ntiles + 15) / 16;
+		int64_t nl = (B->npairs + chunk - 1) / chunk;
+		/* a pipelined series: as many launches on one stream as on the other, so that both reach the end together (5 launches were 3 + 2: the
+		   last one ran alone, its drain exposed) */
+		if (pipe && parts > 1 && !c->kn.pipe_any_count && nl % parts) nl += parts - nl % parts;
+		int64_t even = (B->npairs + nl - 1) / nl;                      /* pairs per launch if all launches are alike */
+		const int64_t ncu = c->dev_cus;
+		const int64_t unit = (ncu / (bpp > ncu ? ncu : bpp) > 0 ? ncu / (bpp > ncu ? ncu : bpp) : 1) * (B->half ? 2 : 1);      /* pairs that make one workgroup per compute unit (k_fill8: two pairs per workgroup) */
+		even = (even + unit - 1) / unit * unit;
+		if (even <= chunk) chunk = even;
+		else if (chunk >= unit) chunk = chunk / unit * unit;
+		if (B->half && (chunk & 1) && chunk > 1) --chunk;      /* whole workgroups of two pairs (a chunk of one pair stays: the second chain is dead) */
+	}
+	memset(P, 0, sizeof *P);
+	P->active = 1;
+	P->tile = tile; P->halo = halo; P->ntiles = ntiles; P->maxcols = maxcols; P->chunk = chunk; P->dbl = dbl; P->pipe = pipe && chunk < B->npairs ? parts : 0;
+	P->seg = !dbl && !c->kn.no_seg_reduce ;      /* the fill kernels also leave the maxima of 16-column groups, which is all the reduction reads */
+	P->cm_bytes = ALIGN16(4 * stride * chunk) * (P->pipe ? P->pipe : 1);      /* (pipe: one set per stream) */
+	P->sg_bytes = P->seg ? ALIGN16(4 * tp->seg_stride * chunk) * (P->pipe ? P->pipe : 1) : 0;
+	P->bnd_bytes = use_x ? ALIGN16(16 * maxcols * ntiles * chunk) : 0;
+	P->cand_bytes = use_x ? ALIGN16(32 * ntiles * chunk) : 0;   /* 2 halves x 4 ints per job */
+	if (use_x && B->lanes == 64) { P->q_ints = chainq_queue_ints(chunk * ntiles * B->strips); P->cs_ints = chainq_cands_ints(chunk * ntiles * B->strips); }
+}
 
+/* ---- plan: tile geometry and scratch of every geometry bucket against the target (tp->refLen, stride, seg_stride are set), the sums
+   over the buckets, and whether the buckets run side by side (allow_conc: the caller has not had that refused yet) */
+static void plan_target(const ssw_gpu_ctx* c, const batch_call* bc, target_plan* tp, int allow_conc)
+{
+	tp->max_chunk = 1; tp->nact = 0;
+	tp->tot_cm = tp->tot_sg = tp->tot_bnd = tp->tot_cand = tp->tot_q = tp->tot_cs = 0;
+	tp->max_cm = tp->max_sg = tp->max_bnd = tp->max_cand = 0;
+	tp->any_dbl = tp->any_chunked = 0;
+	for (int b = 0; b < bc->nb; ++b) {
+		const bucket* B = &bc->bk[b];
+		bplan* P = &tp->bp[b];
+		if (bc->qdone[bc->order[B->first_q]]) { memset(P, 0, sizeof *P); continue; }     /* bucket already answered by the database-search path */
+		plan_bucket(c, bc, tp, B, P);
+		++tp->nact;
+		P->cm_off = tp->tot_cm; P->sg_off = tp->tot_sg; P->bnd_off = tp->tot_bnd; P->cand_off = tp->tot_cand; P->q_off = tp->tot_q; P->cs_off = tp->tot_cs;
+		tp->tot_cm += P->cm_bytes; tp->tot_sg += P->sg_bytes; tp->tot_bnd += P->bnd_bytes; tp->tot_cand += P->cand_bytes; tp->tot_q += P->q_ints; tp->tot_cs += P->cs_ints;
+		if (P->cm_bytes > tp->max_cm) tp->max_cm = P->cm_bytes;
+		if (P->sg_bytes > tp->max_sg) tp->max_sg = P->sg_bytes;
+		if (P->bnd_bytes > tp->max_bnd) tp->max_bnd = P->bnd_bytes;
+		if (P->cand_bytes > tp->max_cand) tp->max_cand = P->cand_bytes;
+		if (P->chunk > tp->max_chunk) tp->max_chunk = (int)(P->chunk > 0x7fffffff ? 0x7fffffff : P->chunk);
+		tp->any_dbl |= P->dbl; tp->any_chunked |= P->chunk < B->npairs;
+	}
+	/* Geometry buckets side by side (round 4).  A batch of mixed read lengths -- the reference's own benchmark: 1000 reads of 25-540 bp
+	   -- is ~30 buckets with a few pairs each; one after the other on one stream every bucket pays its own partly filled last round
+	   of workgroups and the strip kernel's few long jobs leave most of the device idle.  When every bucket is ONE launch and all of
+	   them fit the budget together, each gets its own slice of the scratch buffers and its fill + reduction go to one of the side
+	   streams; the main stream continues after all of them.  SSW_GPU_SERIAL_BUCKETS=1 keeps the old order (tests compare). */
+	tp->conc = tp->nact > 1 && allow_conc && !c->kn.serial_buckets && !c->kn.no_seg_reduce &&     /* (k_reducem reads group maxima only) */
+	           !tp->any_dbl && !tp->any_chunked && 2 * tp->tot_cm + 2 * tp->tot_sg + tp->tot_bnd + tp->tot_cand <= c->cm_budget;
+	if (!tp->conc) for (int b = 0; b < bc->nb; ++b) { bplan* P = &tp->bp[b]; P->cm_off = P->sg_off = P->bnd_off = P->cand_off = 0; P->q_off = P->cs_off = 0; }
+}
+
+/* the scratch of a plan.  Returns 0, or -1: an allocation was refused (c->err says which; plan_retreat) */
+static int plan_alloc(ssw_gpu_ctx* c, target_plan* tp)
+{
+	const int conc = tp->conc;
+	tp->base_cm16 = tp->base_cm8 = tp->base_cmB16 = tp->base_cmB8 = tp->base_sg16 = tp->base_sg8 = tp->base_bnd = tp->base_cand = 0;
+	tp->base_q = tp->base_cs = 0;
+	if (tp->nact == 0) return 0;
+	/* (side by side the buffers are the SUM over the buckets: before the budget is cut, the buckets go one after the other -- the maximum) */
+	tp->base_cm16 = (unsigned char*)ensure(c, &c->cm16, conc ? tp->tot_cm : tp->max_cm);
+	tp->base_cm8 = (unsigned char*)ensure(c, &c->cm8, conc ? tp->tot_cm : tp->max_cm);
+	if (!tp->base_cm16 || !tp->base_cm8) return -1;
+	tp->base_cmB16 = tp->base_cm16; tp->base_cmB8 = tp->base_cm8;
+	if (tp->any_dbl) {
+		tp->base_cmB16 = (unsigned char*)ensure(c, &c->cm16b, tp->max_cm); tp->base_cmB8 = (unsigned char*)ensure(c, &c->cm8b, tp->max_cm);
+		if (!tp->base_cmB16 || !tp->base_cmB8) return -1;
+	}
+	if (tp->max_sg) {
+		tp->base_sg16 = (unsigned char*)ensure(c, &c->sg16, conc ? tp->tot_sg : tp->max_sg); tp->base_sg8 = (unsigned char*)ensure(c, &c->sg8, conc ? tp->tot_sg : tp->max_sg);
+		if (!tp->base_sg16 || !tp->base_sg8) return -1;
+	}
+	if (tp->max_bnd) {
+		tp->base_bnd = (unsigned char*)ensure(c, &c->bnd, conc ? tp->tot_bnd : tp->max_bnd); tp->base_cand = (unsigned char*)ensure(c, &c->cand, conc ? tp->tot_cand : tp->max_cand);
+		if (!tp->base_bnd || !tp->base_cand) return -1;
+	}
+	if (conc && tp->tot_q) {
+		tp->base_q = (int32_t*)ensure(c, &c->queue, sizeof(int32_t) * tp->tot_q); tp->base_cs = (int32_t*)ensure(c, &c->cands, sizeof(int32_t) * tp->tot_cs);
+		if (!tp->base_q || !tp->base_cs) return -1;
+	}
+	return 0;
+}
+
+/* An allocation that fails although it is within the budget (contexts of ONE process sharing a device; across processes HIP
+   over-subscribes silently): what the next plan gives up.  First the side-by-side launches (their buffers are the sum over the buckets),
+   then the budget -- to a quarter the first time, a budget that only just fits leaves nothing for the rest of the call, then by halves;
+   not when every launch is down to one pair already (a smaller budget cannot shrink them further).  The shim clears HIP's sticky error
+   after the failed allocation, so the launches that follow a successful retry do not report it again; ssw_gpu_set_budget starts the
+   ladder afresh.  tests/test_emu_pipeline.py runs it.  (ssw_kernels.hip still calls this ladder by its former name, SSW_ALLOC_RETRY.)
+   Returns 0 when there is nothing left to give up: c->err keeps the refusal. */
+static int plan_retreat(ssw_gpu_ctx* c, int* allow_conc, const target_plan* tp)
+{
+	if (tp->conc) *allow_conc = 0;
+	else if (c->cm_budget > ((size_t)2 << 20) && tp->max_chunk > 1) { c->cm_budget /= c->budget_shrunk ? 2 : 4; c->budget_shrunk = 1; }
+	else return 0;
+	c->err[0] = 0;
+	return 1;
+}
+
+/* the scratch of one launch: column maxima under 16-bit and 8-bit rules, and the maxima of their 16-column groups (0: not kept) */
+typedef struct { uint32_t *cm16, *cm8, *sg16, *sg8; } fill_bufs;
+/* ... of a bucket's plan: its slice when the buckets run side by side, else the whole buffers */
+static fill_bufs bucket_bufs(const target_plan* tp, const bplan* P)
+{
+	fill_bufs fb;
+	fb.cm16 = (uint32_t*)(tp->base_cm16 + P->cm_off); fb.cm8 = (uint32_t*)(tp->base_cm8 + P->cm_off);
+	fb.sg16 = P->seg ? (uint32_t*)(tp->base_sg16 + P->sg_off) : 0; fb.sg8 = P->seg ? (uint32_t*)(tp->base_sg8 + P->sg_off) : 0;
+	return fb;
+}
+
+static int32_t* bucket_cand(const ssw_gpu_ctx* c, const target_plan* tp, const bucket* B, const bplan* P)
+{
+	return B->use_x && !c->kn.no_track ? (int32_t*)(tp->base_cand + P->cand_off) : 0;      /* (no_track, diagnostic: always run the locate pass) */
+}
+
+/* arguments of k_fill / k_fill8 / k_fillm for the pairs [p0, p0 + np) of a bucket; `half`: the frame of a chain of 8 positions if it exists.
+   Returns whether the half-row chains run. */
+static int fill_args_for(const ssw_gpu_ctx* c, const batch_call* bc, const target_plan* tp, const bucket* B, const bplan* P, int32_t p0, int32_t np,
+                         const fill_bufs* fb, int half, ssw_fill_args* fa)
+{
+	const ssw_gpu_params* prm = bc->prm;
+	const int64_t top = (int64_t)16 * B->R * (bc->maxmat > 0 ? bc->maxmat : 0);
+	fa->tgt = tp->d_tgt; fa->refLen = tp->refLen; fa->qcodes = bc->Q->d_codes; fa->qoff = bc->Q->d_off;
+	fa->pairs = bc->d_pairs + B->first_pair + p0; fa->npairs = np; fa->mat = bc->d_mat; fa->n = bc->n;
+	fa->gapO2 = bc->gapO2; fa->gapE2 = bc->gapE2; fa->tile = P->tile; fa->halo = P->halo; fa->ntiles = P->ntiles;
+	fa->bpp = (P->ntiles + 15) / 16; fa->cm16 = fb->cm16; fa->cm8 = fb->cm8; fa->cm_stride = tp->stride;
+	fa->sg16 = fb->sg16; fa->sg8 = fb->sg8; fa->seg_stride = tp->seg_stride;
+	/* column-frame form of the recurrence whenever the bucket's scores leave room for the frame offsets below 31744 (no cell of
+	   the bucket scores more than its padded length x max(mat)); else plain int16 */
+	fa->form = 0; fa->fr_base = 0; fa->fr_kmask = 0;
+	if (bc->fill_form != 0 && ssw_frame_params(&c->kn, top, prm->gapO, prm->gapE, bc->minmat, 16, &fa->fr_base, &fa->fr_kmask)) fa->form = 3;
+	/* half-row chains: single-bucket launches of the frame form only (the frame of a chain of 8 positions) */
+	int32_t hb = 0, hk = 0;
+	if (!half || B->use_x || fa->form != 3 || !ssw_frame_params(&c->kn, top, prm->gapO, prm->gapE, bc->minmat, 8, &hb, &hk)) return 0;
+	fa->fr_base = hb; fa->fr_kmask = hk;
+	return 1;
+}
+
+static void reduce_args_for(const ssw_gpu_ctx* c, const batch_call* bc, const target_plan* tp, const bucket* B, const bplan* P, int32_t p0, int32_t np,
+                            const fill_bufs* fb, ssw_reduce_args* ra)
+{
+	const ssw_gpu_params* prm = bc->prm;
+	ra->cm16 = fb->cm16; ra->cm8 = fb->cm8; ra->cm_stride = tp->stride; ra->refLen = tp->refLen; ra->pairs = bc->d_pairs + B->first_pair + p0; ra->npairs = np;
+	ra->qoff = bc->Q->d_off; ra->maskLen = prm->maskLen; ra->bias = bc->bias; ra->score_size = prm->score_size;
+	ra->flag = prm->flag; ra->filters = prm->filters; ra->res = bc->d_res; ra->cand = bucket_cand(c, tp, B, P); ra->tile = P->tile; ra->ntiles = P->ntiles;
+	ra->sg16 = fb->sg16; ra->sg8 = fb->sg8; ra->seg_stride = tp->seg_stride;
+}
+
+/* The fill of the pairs [p0, p0 + np) of bucket b on stream st: the choice between k_fill, k_fill8, k_chainx and k_chainq, and what the
+   call's timing record says about it.  ndefer (side by side): a short-query bucket is not launched, its arguments join the group's
+   deferred grids (fill_side_by_side) as bc->defer[(*ndefer)++], and the strip kernel's work queue is the bucket's slice of the group's. */
+static int fill_launch(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, int b, int32_t p0, int32_t np, const fill_bufs* fb, void* st, int* ndefer)
+{
+	const bucket* B = &bc->bk[b]; const bplan* P = &tp->bp[b];
+	const ssw_gpu_params* prm = bc->prm;
+	const int use_x = B->use_x, conc = ndefer != 0;
+	const int32_t n = bc->n, refLen = tp->refLen, tile = P->tile, halo = P->halo, ntiles = P->ntiles;
+	ssw_fill_args fa;
+	const int use_half = fill_args_for(c, bc, tp, B, P, p0, np, fb, B->half && !conc, &fa);
+	int xform = 0;
+	if (use_x) {
+		int32_t xfr_base = 0, xfr_kmask = 0;
+		if (bc->fill_form != 0 && B->lanes == 64 &&
+		    ssw_frame_params(&c->kn, (int64_t)B->P16 * (bc->maxmat > 0 ? bc->maxmat : 0), prm->gapO, prm->gapE, bc->minmat, 64, &xfr_base, &xfr_kmask)) xform = 3;
+		ssw_chainx_args xa; memset(&xa, 0, sizeof xa);
+		xa.tgt = tp->d_tgt; xa.refLen = refLen; xa.qcodes = bc->Q->d_codes; xa.qoff = bc->Q->d_off; xa.mat = bc->d_mat; xa.n = n;
+		xa.gapO2 = bc->gapO2; xa.gapE2 = bc->gapE2; xa.gapE = prm->gapE; xa.maxmat = bc->maxmat; xa.njobs = np * ntiles;
+		xa.pairs = fa.pairs; xa.tile = tile; xa.halo = halo; xa.ntiles = ntiles; xa.cm16 = fb->cm16; xa.cm8 = fb->cm8;
+		xa.cm_stride = tp->stride; xa.bnd = (uint32_t*)(tp->base_bnd + P->bnd_off); xa.bnd_stride = P->maxcols; xa.cand = bucket_cand(c, tp, B, P); xa.lanes = B->lanes;
+		xa.sg16 = fb->sg16; xa.sg8 = fb->sg8; xa.seg_stride = tp->seg_stride;
+		if (B->lanes == 64) {     /* strips of all jobs behind one work queue (k_chainq) */
+			const int qgrid = chainq_grid(c, B->R, 0, n);
+			if (conc ? chainq_setup(c, &xa, B->strips, (int64_t)np * ntiles, qgrid, tp->base_q + P->q_off, tp->base_cs + P->cs_off, st)
+			         : chainq_prepare(c, &xa, B->strips, (int64_t)np * ntiles, qgrid)) return -1;
+			xa.form = xform; xa.fr_base = xfr_base; xa.fr_kmask = xfr_kmask; xa.tail_R = B->tailR;
+			if (c->kn.debug) fprintf(stderr, "[ssw_gpu] chainq fill: R %d (last strip %d), %d jobs x %d strips, %d wavefronts, %s tickets, form %d\n",
+			                                     B->R, B->tailR ? B->tailR : B->R, np * ntiles, B->strips, qgrid, xa.whole_jobs ? "job" : "strip", xa.form);
+			if (ssw_shim_launch_chainq(B->R, 0, &xa, qgrid, st)) return fail(c, "fill launch failed: %s", ssw_shim_last_error());
+			if (c->kn.debug) { const int src = ssw_shim_stream_sync(st); fprintf(stderr, "[ssw_gpu] chainq fill done (sync rc %d: %s)\n", src, src ? ssw_shim_last_error() : "ok"); }
+		} else
+		if (ssw_shim_launch_chainx(B->R, 0, &xa, st)) return fail(c, "fill launch failed: %s", ssw_shim_last_error());
+	} else
+	if (conc) {      /* short-query buckets side by side: their workgroups join the grid of their register class (k_fillm) */
+		fill_defer* d = &bc->defer[(*ndefer)++];
+		d->fa = fa; d->R = B->R; d->wgs = (int64_t)np * fa.bpp; d->group = ssw_shim_fill_class(B->R) * 2 + (fa.form == 3);
+	} else
+	if (use_half ? ssw_shim_launch_fill8(B->half, &fa, st) : ssw_shim_launch_fill(B->R, &fa, st)) return fail(c, "fill launch failed: %s", ssw_shim_last_error());
+
+	int64_t cols = 0;
+	for (int32_t k = 0; k < ntiles; ++k) {
+		int64_t lo = (int64_t)k * tile, hi = lo + tile < refLen ? lo + tile : refLen;
+		int64_t cf = lo - halo > 0 ? lo - halo : 0;
+		cols += hi - cf;
+	}
+	const int64_t lc = cols * (int64_t)(use_half ? 8 * B->half : B->lanes * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips)) * 2 * np;
+	c->tm.fill_cells += lc;
+	char nm[48];
+	if (use_half) snprintf(nm, sizeof nm, "k_fill8<%d,frame>", B->half);
+	else if (!use_x) snprintf(nm, sizeof nm, "k_fill<%d,%s>", B->R, fa.form == 3 ? "frame" : "int16");
+	else if (B->lanes == 64 && B->tailR) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR);
+	else if (B->lanes == 64) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
+	else snprintf(nm, sizeof nm, "k_chainx<%d,16 lanes> x %d strips", B->R, B->strips);
+	note_fill_kernel(c, lc, &bc->best_fill_cells, nm, !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
+	return 0;
+}
+
+/* One bucket on its own: as many launches of P->chunk pairs as it takes, each followed by its reduction.  Plain: all on the main stream, an
+   event pair around every fill.  dbl (opt-in): two buffer sets, the reductions on the second stream beside the next fill.  pipe: the
+   launches go round the main stream and the extra one(s), each with its own part of the scratch; one event pair around the series. */
+static int fill_bucket_series(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, int b)
+{
+	const bucket* B = &bc->bk[b]; const bplan* P = &tp->bp[b];
+	const int dbl = P->dbl;
+	const int pipe = P->pipe;      /* the number of parts: 0 (not pipelined), 2 (a hook: up to 8) */
+	const fill_bufs A = bucket_bufs(tp, P);
+	fill_bufs B2 = A;      /* dbl: the second buffer set */
+	if (dbl) { B2.cm16 = (uint32_t*)tp->base_cmB16; B2.cm8 = (uint32_t*)tp->base_cmB8; }
+	void *pe0 = 0, *pe1 = 0;
+	if (pipe) {
+		pe0 = next_event(c); pe1 = next_event(c);
+		if (ssw_shim_event_record(pe0, c->stream)) return fail(c, "stream wait failed: %s", ssw_shim_last_error());
+		for (int k = 0; k < pipe - 1; ++k) {
+			if (!c->pstream[k]) { c->pstream[k] = c->kn.pipe_low_prio ? ssw_shim_stream_create_low() : ssw_shim_stream_create(); c->ev_pipe[k] = ssw_shim_event_create(); }
+			if (!c->pstream[k] || !c->ev_pipe[k]) return fail(c, "stream creation failed: %s", ssw_shim_last_error());
+			/* (the extra streams start after everything the main stream has queued so far: the call's uploads, the record memset) */
+			if (ssw_shim_stream_wait_event(c->pstream[k], pe0)) return fail(c, "stream wait failed: %s", ssw_shim_last_error());
+		}
+	}
+	int launch_i = 0;
+	for (int32_t p0 = 0; p0 < B->npairs; p0 += (int32_t)P->chunk, ++launch_i) {
+		const int32_t np = B->npairs - p0 < P->chunk ? B->npairs - p0 : (int32_t)P->chunk;
+		const int bi = pipe ? launch_i % pipe : dbl ? (launch_i & 1) : 0;
+		void* st = c->stream;
+		fill_bufs fb = bi ? B2 : A;
+		if (pipe) {      /* launch i: part i mod parts of the scratch; parts 1.. on the extra streams (in order on each: launch i + parts follows the reduction of launch i) */
+			if (bi) st = c->pstream[bi - 1];
+			fb.cm16 = (uint32_t*)((unsigned char*)A.cm16 + (size_t)bi * (P->cm_bytes / (size_t)pipe)); fb.cm8 = (uint32_t*)((unsigned char*)A.cm8 + (size_t)bi * (P->cm_bytes / (size_t)pipe));
+			fb.sg16 = P->seg ? (uint32_t*)((unsigned char*)A.sg16 + (size_t)bi * (P->sg_bytes / (size_t)pipe)) : 0;
+			fb.sg8 = P->seg ? (uint32_t*)((unsigned char*)A.sg8 + (size_t)bi * (P->sg_bytes / (size_t)pipe)) : 0;
+		}
+		if (dbl && launch_i >= 2) ssw_shim_stream_wait_event(c->stream, c->ev_red[bi]);    /* the buffer set is free again */
+		void *e0 = 0, *e1 = 0;
+		if (!pipe) { e0 = next_event(c); e1 = next_event(c); ssw_shim_event_record(e0, st); }
+		if (fill_launch(c, bc, tp, b, p0, np, &fb, st, 0)) return -1;
+		if (!pipe) ssw_shim_event_record(e1, st);      /* (pipe: one event pair around the whole series, below -- the launches overlap) */
+		c->tm.fill_launches++; if (pipe) c->tm.fill_pipelined++;
+		ssw_reduce_args ra;
+		reduce_args_for(c, bc, tp, B, P, p0, np, &fb, &ra);
+		if (dbl) {
+			ssw_shim_event_record(c->ev_fill[bi], c->stream);
+			ssw_shim_stream_wait_event(c->stream2, c->ev_fill[bi]);
+			if (ssw_shim_launch_reduce(&ra, c->stream2)) return fail(c, "reduce launch failed: %s", ssw_shim_last_error());
+			ssw_shim_event_record(c->ev_red[bi], c->stream2);
+		} else
+		if (ssw_shim_launch_reduce(&ra, st)) return fail(c, "reduce launch failed: %s", ssw_shim_last_error());
+	}
+	if (dbl) {   /* everything later on the main stream sees all records of this bucket */
+		ssw_shim_stream_wait_event(c->stream, c->ev_red[0]);
+		if (launch_i > 1) ssw_shim_stream_wait_event(c->stream, c->ev_red[1]);
+	}
+	if (pipe) {   /* the main stream continues after the extra streams' last reductions; the series is timed as one (its reductions included: ~0.1 ms each) */
+		for (int k = 0; k < pipe - 1; ++k)
+			if (ssw_shim_event_record(c->ev_pipe[k], c->pstream[k]) || ssw_shim_stream_wait_event(c->stream, c->ev_pipe[k])) return fail(c, "stream join failed: %s", ssw_shim_last_error());
+		if (ssw_shim_event_record(pe1, c->stream)) return fail(c, "stream join failed: %s", ssw_shim_last_error());
+	}
+	return 0;
+}
+
+/* a side stream's first use in a side-by-side group: it starts after everything the main stream had queued (c->ev_db) */
+static int side_stream_join_in(ssw_gpu_ctx* c, int sx, int* side_used)
+{
+	if (side_used[sx]) return 0;
+	side_used[sx] = 1;
+	return ssw_shim_stream_wait_event(c->tstream[sx], c->ev_db) ? fail(c, "stream wait failed: %s", ssw_shim_last_error()) : 0;
+}
+/* ... and the main stream continues after every side stream that was used */
+static int side_streams_join_out(ssw_gpu_ctx* c, const int* side_used)
+{
+	for (int sx = 0; sx < SSW_TSTREAMS; ++sx)
+		if (side_used[sx] && (ssw_shim_event_record(c->tev[sx], c->tstream[sx]) || ssw_shim_stream_wait_event(c->stream, c->tev[sx])))
+			return fail(c, "stream join failed: %s", ssw_shim_last_error());
+	return 0;
+}
+
+/* one k_fillm grid per (register class, form) of the ndefer deferred short-query buckets, largest group first, longest chains first */
+static int fill_deferred_grids(ssw_gpu_ctx* c, batch_call* bc, int ndefer, int* side_used)
+{
+	const fill_defer* defer = bc->defer;
+	const size_t rec = sizeof(ssw_fill_args);
+	unsigned char* htab = (unsigned char*)calloc((rec + 16) * (size_t)ndefer + 64 * 6, 1);
+	unsigned char* dtab = (unsigned char*)ensure(c, &c->fmtab, (rec + 16) * (size_t)ndefer + 64 * 6);
+	if (!htab) return fail(c, "out of host memory%s", "");
+	if (!dtab) { free(htab); return -1; }
+	int64_t gw[6] = { 0, 0, 0, 0, 0, 0 };      /* groups by size, largest first */
+	for (int i = 0; i < ndefer; ++i) gw[defer[i].group] += defer[i].wgs * defer[i].R;
+	int gord[6] = { 0, 1, 2, 3, 4, 5 };
+	for (int i = 1; i < 6; ++i) { const int v = gord[i]; int j = i; while (j > 0 && gw[gord[j - 1]] < gw[v]) { gord[j] = gord[j - 1]; --j; } gord[j] = v; }
+	size_t at = 0;
+	int nside = 0, rc = -1;
+	for (int gi_ = 0; gi_ < 6; ++gi_) {
+		const int g = gord[gi_];
+		int idx[SSW_RMAX + 1], ng = 0;
+		for (int i = 0; i < ndefer; ++i) if (defer[i].group == g) idx[ng++] = i;
+		if (ng == 0) continue;
+		for (int i = 1; i < ng; ++i) { const int v = idx[i]; int j = i; while (j > 0 && defer[idx[j - 1]].R < defer[v].R) { idx[j] = idx[j - 1]; --j; } idx[j] = v; }
+		const size_t a0 = at, a1 = a0 + ALIGN16(rec * (size_t)ng), a2 = a1 + ALIGN16(4 * ((size_t)ng + 1));
+		int32_t* hfirst = (int32_t*)(htab + a1); int32_t* hR = (int32_t*)(htab + a2);
+		int64_t total = 0;
+		for (int i = 0; i < ng; ++i) { memcpy(htab + a0 + rec * (size_t)i, &defer[idx[i]].fa, sizeof(ssw_fill_args)); hfirst[i] = (int32_t)total; hR[i] = defer[idx[i]].R; total += defer[idx[i]].wgs; }
+		hfirst[ng] = (int32_t)total;
+		at = a2 + ALIGN16(4 * (size_t)ng);
+		if (total > 0x7fffffff) { fail(c, "internal error: %s", "more than 2^31 workgroups in one multi-bucket fill launch"); goto out; }
+		static const int grid_streams[3] = { 0, 1, 4 };      /* three different hardware queues (see fill_side_by_side) */
+		const int sx = grid_streams[nside++ % 3];
+		void* st = c->tstream[sx];
+		if (side_stream_join_in(c, sx, side_used)) goto out;
+		ssw_fillm_args ma; ma.sub = (const ssw_fill_args*)(dtab + a0); ma.first_wg = (const int32_t*)(dtab + a1); ma.subR = (const int32_t*)(dtab + a2); ma.nsub = ng;
+		if (ssw_shim_h2d(dtab + a0, htab + a0, at - a0, st) || ssw_shim_launch_fillm(&ma, hR, bc->n, g & 1 ? 3 : 0, total, st)) {
+			fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto out;
+		}
+	}
+	rc = 0;
+out:
+	free(htab);
+	return rc;
+}
+
+/* every bucket's reduction in one grid (k_reducem): one workgroup per pair */
+static int reduce_deferred_grid(ssw_gpu_ctx* c, const ssw_reduce_args* rdefer, int nrdefer)
+{
+	const size_t rec = sizeof(ssw_reduce_args), a1 = ALIGN16(rec * (size_t)nrdefer);
+	unsigned char* htab = (unsigned char*)calloc(a1 + 4 * ((size_t)nrdefer + 1) + 16, 1);
+	unsigned char* dtab = (unsigned char*)ensure(c, &c->fmtab, a1 + 4 * ((size_t)nrdefer + 1) + 16);
+	if (!htab) return fail(c, "out of host memory%s", "");
+	if (!dtab) { free(htab); return -1; }
+	int32_t* hfirst = (int32_t*)(htab + a1);
+	int64_t total = 0;
+	for (int i = 0; i < nrdefer; ++i) { memcpy(htab + rec * (size_t)i, &rdefer[i], rec); hfirst[i] = (int32_t)total; total += rdefer[i].npairs; }
+	hfirst[nrdefer] = (int32_t)total;
+	ssw_reducem_args rm; rm.sub = (const ssw_reduce_args*)dtab; rm.first_wg = (const int32_t*)(dtab + a1); rm.nsub = nrdefer;
+	const int bad = ssw_shim_h2d(dtab, htab, a1 + 4 * ((size_t)nrdefer + 1), c->stream) || ssw_shim_launch_reducem(&rm, total, c->stream);
+	free(htab);
+	return bad ? fail(c, "reduce launch failed: %s", ssw_shim_last_error()) : 0;
+}
+
+/* All buckets of a plan side by side (tp->conc): every bucket is one launch in its own slice of the scratch.  The short-query buckets
+   first (their grids are the bulk of the work and go to the hardware queues at once), then the strip kernel's launches; the main stream
+   continues after all of them with ONE grid of reductions.  The group counts as one launch (its event pair brackets the side streams' work). */
+static int fill_side_by_side(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp)
+{
+	const bucket* bk = bc->bk; const int nb = bc->nb;
+	int* const border = bc->border;
+	int side_used[SSW_TSTREAMS]; int ndefer = 0, nrdefer = 0;
+	for (int sx = 0; sx < SSW_TSTREAMS; ++sx) side_used[sx] = 0;
+	void* ge0 = next_event(c); void* ge1 = next_event(c);
+	if (ssw_shim_event_record(ge0, c->stream) || ssw_shim_event_record(c->ev_db, c->stream)) return fail(c, "event record failed: %s", ssw_shim_last_error());
+	/* largest bucket first: the side streams are served round-robin, and the device drains the big launches while the small ones fill its gaps */
+	for (int i = 0; i < nb; ++i) border[i] = i;
+	for (int i = 1; i < nb; ++i) {
+		const int v = border[i]; int j = i;
+		while (j > 0 && (int64_t)bk[border[j - 1]].npairs * bk[border[j - 1]].P16 < (int64_t)bk[v].npairs * bk[v].P16) { border[j] = border[j - 1]; --j; }
+		border[j] = v;
+	}
+	/* The runtime maps streams onto FOUR hardware queues (seen on ROCm 7.2: the context's eight streams land on queues
+	   1 2 3 4 4 3 2 1), and launches that share a queue run one after the other: the strip kernel's few, latency-bound
+	   launches all go to ONE side stream, in sequence (together they are shorter than the short-query grids beside them);
+	   the multi-bucket grids take three others.  profiles/round4_config6_timeline.txt */
+	const int strip_sx = 5;
+	if (side_stream_join_in(c, strip_sx, side_used)) return -1;
+	for (int pass_x = 0; pass_x < 2; ++pass_x) {
+		for (int bi_ = 0; bi_ < nb; ++bi_) {
+			const int b = border[bi_];
+			const bucket* B = &bk[b]; const bplan* P = &tp->bp[b];
+			if (!P->active || (B->use_x != 0) != pass_x) continue;
+			const fill_bufs fb = bucket_bufs(tp, P);
+			if (fill_launch(c, bc, tp, b, 0, B->npairs, &fb, c->tstream[strip_sx], &ndefer)) return -1;
+			reduce_args_for(c, bc, tp, B, P, 0, B->npairs, &fb, &bc->rdefer[nrdefer++]);      /* all reductions of the group as one grid, after the join */
+		}
+		if (pass_x == 0 && ndefer > 0 && fill_deferred_grids(c, bc, ndefer, side_used)) return -1;
+	}
+	if (side_streams_join_out(c, side_used)) return -1;
+	if (nrdefer > 0 && reduce_deferred_grid(c, bc->rdefer, nrdefer)) return -1;
+	ssw_shim_event_record(ge1, c->stream);
+	c->tm.fill_launches++;
+	return 0;
+}
+
+/* window passes of every bucket the generic path answers: read_end1 always (ssw.c:342-351); begin position only when asked for (ssw.c:916) */
+static int window_phase(ssw_gpu_ctx* c, const batch_call* bc, const target_plan* tp)
+{
+	const bucket* bk = bc->bk; const int nb = bc->nb; const int32_t n = bc->n;
+	win_in wi; memset(&wi, 0, sizeof wi);
+	wi.Q = bc->Q; wi.prm = bc->prm; wi.d_tgt = tp->d_tgt; wi.refLen = tp->refLen; wi.d_mat = bc->d_mat; wi.n = n; wi.maxmat = bc->maxmat; wi.minmat = bc->minmat;
+	wi.fill_form = bc->fill_form; wi.d_res = bc->d_res; wi.g = bc->geom;
+	/* a batch of many buckets: the k_capture launches (one small, latency-bound grid per bucket) side by side -- a bucket keeps its
+	   side stream for both passes (the reverse pass reads what the locate pass wrote) */
+	int nwin = 0, wused[SSW_TSTREAMS];
+	for (int b = 0; b < nb; ++b) if (!bc->qdone[bc->order[bk[b].first_q]] && !window_on_strips(&bk[b], n)) ++nwin;
+	const int fan = nwin > 2 && !c->kn.serial_buckets;
+	for (int sx = 0; sx < SSW_TSTREAMS; ++sx) wused[sx] = 0;
+	if (fan && ssw_shim_event_record(c->ev_db, c->stream)) return fail(c, "event record failed: %s", ssw_shim_last_error());
+	for (int pass = 0; pass < (bc->prm->flag != 0 ? 2 : 1); ++pass)
+		for (int b = 0; b < nb; ++b) {
+			const bucket* B = &bk[b];
+			if (bc->qdone[bc->order[B->first_q]]) continue;
+			void* st = 0;
+			if (fan && !window_on_strips(B, n)) {
+				const int sx = b % SSW_TSTREAMS;
+				st = c->tstream[sx];
+				if (side_stream_join_in(c, sx, wused)) return -1;
+			}
+			if (window_pass(c, &wi, B, pass, bc->d_qlist + B->first_q, B->nq, st)) return -1;
+		}
+	return side_streams_join_out(c, wused);
+}
+
+/* traceback (+ SAM-style rewrite) of the alignments whose record asks for a CIGAR; `last`: no further target follows */
+static int batch_trace(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, int last, trace_out* tro)
+{
+	const int32_t nq = bc->nq, refLen = tp->refLen;
+	const int32_t halo_max = halo_for((bc->maxlen + 15) / 16 * 16, bc->maxmat, bc->prm->gapE);
+	trace_in tri; memset(&tri, 0, sizeof tri);
+	tri.Q = bc->Q; tri.prm = bc->prm; tri.d_tgt = tp->d_tgt; tri.d_mat = bc->d_mat; tri.n = bc->n; tri.d_res = bc->d_res; tri.nslots = nq;
+	tri.ids = bc->order; tri.nids = bc->nqa; tri.d_list = bc->d_qlist; tri.hneed = bc->hneed; tri.maxlen = bc->maxlen; tri.ref_span = halo_max < refLen ? halo_max : refLen;
+	tri.list_on_device = 1;
+	if (bc->literal) {
+		/* gapO <= gapE: the halo argument (every gap base costs at least gapE) does not bound an alignment's reference span -- a gap base can
+		   cost gapO, and with gapO = 0 nothing at all: 33 read bases against 346 target bases is a legal answer of the reference.  This regime
+		   is not a throughput path: take the spans the window passes actually found (one download) instead of a bound.  CIGAR slots and the
+		   traceback's widest band are then exact for this batch. */
+		const ssw_dres* hres = bc->hres;
+		if (ssw_shim_d2h(bc->hres, bc->d_res, sizeof(ssw_dres) * (size_t)nq, c->stream) || ssw_shim_stream_sync(c->stream)) return fail(c, "result download failed: %s", ssw_shim_last_error());
+		int64_t rspan = 1;
+		for (int32_t q = 0; q < nq; ++q)
+			if (hres[q].want_cigar && hres[q].status == 0 && (int64_t)hres[q].ref_end1 - hres[q].ref_begin1 + 1 > rspan) rspan = (int64_t)hres[q].ref_end1 - hres[q].ref_begin1 + 1;
+		tri.ref_span = rspan;
+	}
+	if (trace_phase(c, &tri, tro)) return -1;
+	/* (the traceback may have reordered the query list on the device: the next target's kernels read it in bucket order again) */
+	if (tro->list_dirty && !last && ssw_shim_h2d(bc->d_qlist, bc->order, sizeof(int32_t) * (size_t)bc->nqa, c->stream)) return fail(c, "upload failed: %s", ssw_shim_last_error());
+	return 0;
+}
+
+/* the downloaded records of one target into the caller's array (column ti); CIGARs are named by their offset in the call's pool */
+static int records_out(ssw_gpu_ctx* c, const batch_call* bc, int32_t ti, int32_t refLen, ssw_gpu_result* results)
+{
+	for (int32_t q = 0; q < bc->nq; ++q) {
+		const ssw_dres* r = &bc->hres[q];
+		ssw_gpu_result* o = &results[(int64_t)q * bc->tcount + ti];
+		if (bc->qdone[q]) continue;
+		if (r->status >= 2) return fail(c, "internal error: window pass did not reproduce the forward score%s", "");
+		o->score1 = (uint16_t)r->score1; o->score2 = (uint16_t)r->score2;
+		o->ref_begin1 = r->ref_begin1; o->ref_end1 = r->ref_end1; o->read_begin1 = r->read_begin1; o->read_end1 = r->read_end1;
+		o->ref_end2 = r->ref_end2; o->cigarLen = r->cigarLen; o->cigar_off = -1; o->flag = (uint16_t)r->flag; o->status = (uint16_t)r->status;
+		o->edit_distance = r->nm;
+		if (r->score1 <= 0 && r->status == 0) { o->ref_begin1 = -1; o->read_begin1 = -1; }
+		if (r->cigarLen > 0 && r->status == 0) o->cigar_off = bc->pool.n + bc->goffs[q];
+		if (r->status == 0 && r->score1 > 0) { if (r->word) c->tm.n_word++; else c->tm.n_byte++; }
+		c->tm.cells += (bc->Q->h_off[q + 1] - bc->Q->h_off[q]) * (int64_t)refLen;
+	}
+	return 0;
+}
+
+/* The phases of a batch call, in the order they run.  Per target the fill is either the lane-model kernel (literal_fill) or a plan:
+   plan_target decides tiles, launch sizes and -- this is where side by side is chosen -- tp.conc; plan_alloc asks for the scratch; a refusal
+   goes to plan_retreat (first no side by side, then a smaller budget) and is planned again, or ends the call when nothing is left to give up. */
+static int align_batch_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
+                              const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds)
+{
+	/* ---- 1. check */
+	if (!results && !ds) return fail(c, "align_batch: NULL argument%s", "");
+	if (check_seqs(c, "align_batch", Q, T, prm)) return -1;
+	if (tfirst < 0 || tcount < 0 || tfirst + tcount > T->count) return fail(c, "align_batch: target range out of bounds%s", "");
+	if (check_scoring(c, "align_batch", prm)) return -1;
+	ssw_shim_set_device(c->device);
+	knobs_load(&c->kn);
+	if ((Q->count > 1 || tcount > 1 || ds) && ctx_side_streams(c)) return -1;      /* (one pair never leaves the main stream) */
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	const int32_t nq = Q->count;
+	if (nq == 0 || tcount == 0) return 0;
+
+	/* Alphabets.  The reference takes any int32 n (src/ssw.h:86, ssw.c:826-847).  Up to 32 letters the per-residue score profile of a query
+	   lives in LDS (the profile kernels); 33 .. 128 letters -- every value an int8 code can take -- run on the lane-model kernel, which looks
+	   its scores up in the MATRIX (n x n bytes of LDS) and is exact in every gap regime, and on the thread traceback, which reads the matrix
+	   through the cache: slow (a CPU-class path, like gapO <= gapE), but the reference's answer instead of a refusal.  n > 128: codes are int8,
+	   so only the leading 128 x 128 block of the matrix can ever be addressed -- the kernels get that block; the 8-bit bias is still the minimum
+	   over the WHOLE matrix, as ssw_init computes it (ssw.c:834-836). */
+	batch_call bc; memset(&bc, 0, sizeof bc);
+	bc.Q = Q; bc.T = T; bc.prm = prm; bc.tfirst = tfirst; bc.tcount = tcount; bc.nq = nq;
+	bc.n = prm->n > SSW_MAX_N_WIDE ? SSW_MAX_N_WIDE : prm->n;
+	bc.literal = prm->gapO <= prm->gapE || prm->n > SSW_MAX_N;
+	bc.gapO2 = (uint32_t)prm->gapO * 0x10001u; bc.gapE2 = (uint32_t)prm->gapE * 0x10001u;
+	bc.fill_form = c->kn.fill_plain ? 0 : -1;
+	mat_range(prm, &bc.minmat, &bc.maxmat, &bc.bias);
+	int rc = -1;
+
+	/* ---- 2. bucket */
+	if (batch_buckets(c, &bc, ds)) goto done;
+	if (bc.nqa == 0) {     /* nothing but empty queries */
+		rc = ds ? SSW_NOT_STREAMABLE : 0;
+		if (!ds) { for (int64_t k = 0; k < (int64_t)nq * tcount; ++k) topk_pad(&results[k]); memset(&c->tm, 0, sizeof c->tm); }
+		goto done;
+	}
+	const int nb1 = bc.nb > 0 ? bc.nb : 1;
+	bc.bplans = (bplan*)calloc((size_t)nb1, sizeof(bplan)); bc.border = (int*)malloc(sizeof(int) * (size_t)nb1);
+	bc.defer = (fill_defer*)malloc(sizeof(fill_defer) * (size_t)nb1); bc.rdefer = (ssw_reduce_args*)malloc(sizeof(ssw_reduce_args) * (size_t)nb1);
+	bc.hres = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)nq); bc.hneed = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq); bc.goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)nq);
+	memset(&c->tm, 0, sizeof c->tm);
+	c->nev = 0;
+	if (!bc.bplans || !bc.border || !bc.defer || !bc.rdefer || !bc.hres || !bc.hneed || !bc.goffs) { fail(c, "out of host memory%s", ""); goto done; }
+
+	/* ---- 3. header upload; 4. the database path, where it answers (part of) the call */
+	if (batch_header(c, &bc)) goto done;
+	rc = batch_try_db(c, &bc, results, cigar_pool, cigar_words, ds);
+	if (rc != 0) { if (rc == 1) rc = 0; goto done; }
+	rc = -1;
+
+	/* ---- 5. per target */
 	for (int32_t ti = 0; ti < tcount; ++ti) {
-		const int32_t t = tfirst + ti;
-		const int64_t refLen64 = T->h_off[t + 1] - T->h_off[t];
+		const int64_t refLen64 = T->h_off[tfirst + ti + 1] - T->h_off[tfirst + ti];
 		if (refLen64 > 0x7fffff00) { fail(c, "align_batch: target longer than 2^31 is not supported%s", ""); goto done; }
 		const int32_t refLen = (int32_t)refLen64;
-		const int8_t* d_tgt = T->d_codes + T->h_off[t];
 		const int ev_first = c->nev;
+		target_plan tp; memset(&tp, 0, sizeof tp);
+		tp.refLen = refLen; tp.d_tgt = T->d_codes + T->h_off[tfirst + ti]; tp.bp = bc.bplans;
+		tp.stride = ((int64_t)refLen + 15) / 16 * 16 + 16; tp.seg_stride = (tp.stride / 16 + 4 + 3) / 4 * 4;
 		/* (every non-empty query's record is written whole by the reduction; only empty queries, queries answered elsewhere and an EMPTY
 		   target -- no kernel runs at all: the reference's score-0 record, src/ssw.c:900-903 -- rely on zeroes) */
-		if (nqa != nq || tcount > 1 || refLen == 0) { if (ssw_shim_memset(d_res, 0, sizeof(ssw_dres) * (size_t)nq, c->stream)) { fail(c, "memset failed: %s", ssw_shim_last_error()); goto done; } }
+		if ((bc.nqa != nq || tcount > 1 || refLen == 0) && ssw_shim_memset(bc.d_res, 0, sizeof(ssw_dres) * (size_t)nq, c->stream)) { fail(c, "memset failed: %s", ssw_shim_last_error()); goto done; }
 
-		if (refLen > 0 && literal) {
-			/* scratch per alignment: 4 x [segments][16] int16 + codes + maxColumn (sized for the 16-bit kernel: 8 lanes) */
-			const int64_t seg8 = ((int64_t)maxlen + 7) / 8;
-			const int64_t lstate = (seg8 * 16 * 2 * 4 + seg8 * 16 + 64 + 15) / 16 * 16;
-			const int64_t sstr = (lstate + (int64_t)refLen * 2 + 64 + 15) / 16 * 16;
-			int64_t per = (int64_t)(c->cm_budget / (size_t)sstr); if (per < 1) per = 1;
-			/* A forward pass that leaves most of the device idle (round 6; the device holds ~50 alignments of this kernel per compute unit) runs BOTH
-			   rule sets of every query side by side instead of the 16-bit kernel after the 8-bit one saturated: 2 000 reads x 1 Mb took two kernel
-			   lengths on a sixth of the device (45 GCUPS against the reference's 63 on the box's 16 cores, round-5 verdict weak #8). */
-			const int spec = prm->score_size == 2 && !c->kn.no_lit_spec && 2 * (int64_t)nqa + 4 <= (int64_t)c->dev_cus * 48 && per >= 2 * (int64_t)nqa + 4;
-			int32_t* d_spec = 0;
-			if (spec) {
-				d_spec = (int32_t*)ensure(c, &c->cand, sizeof(int32_t) * 17 * (size_t)nq);      /* [nq counters][nq x 2 x 8 outcomes] */
-				if (!d_spec) goto done;
-				if (ssw_shim_memset(d_spec, 0, sizeof(int32_t) * (size_t)nq, c->stream)) { fail(c, "memset failed: %s", ssw_shim_last_error()); goto done; }
+		if (refLen > 0 && bc.literal) { if (literal_fill(c, &bc, &tp)) goto done; }
+		else if (refLen > 0) {
+			int allow_conc = 1;      /* (per target: the next target may try side by side again) */
+			for (;;) {
+				plan_target(c, &bc, &tp, allow_conc);
+				if (!plan_alloc(c, &tp)) break;
+				if (!plan_retreat(c, &allow_conc, &tp)) goto done;
 			}
-			void* e0 = next_event(c); void* e1 = next_event(c);
-			ssw_shim_event_record(e0, c->stream);
-			for (int pass = 0; pass < (prm->flag != 0 ? 2 : 1); ++pass)
-				for (int32_t q0 = 0; q0 < nqa; q0 += (int32_t)per) {      /* (d_qlist holds the nqa NON-EMPTY queries; empty ones keep the zeroed record) */
-					const int32_t cnt_q = nqa - q0 < per ? nqa - q0 : (int32_t)per;
-					const int64_t regions = spec && pass == 0 ? (((int64_t)cnt_q + 3) & ~(int64_t)3) + cnt_q : cnt_q;      /* (spec: one launch takes all of them, per >= 2 nqa + 4) */
-					uint8_t* d_scr = (uint8_t*)ensure(c, &c->scratch, (size_t)(sstr * regions));
-					if (!d_scr) goto done;
-					ssw_literal_args la;
-					la.spec_cnt = spec && pass == 0 ? d_spec : 0; la.spec_out = spec && pass == 0 ? d_spec + nq : 0;
-					la.tgt = d_tgt; la.refLen = refLen; la.qcodes = Q->d_codes; la.qoff = Q->d_off; la.qlist = d_qlist + q0; la.nq = cnt_q;
-					la.mat = d_mat; la.n = n; la.gapO = prm->gapO; la.gapE = prm->gapE; la.pass = pass; la.maskLen = prm->maskLen; la.bias = bias;
-					la.score_size = prm->score_size; la.flag = prm->flag; la.filters = prm->filters; la.filterd = prm->filterd; la.res = d_res;
-					la.scratch = d_scr; la.scratch_stride = sstr; la.mc_off = lstate; la.state_bytes = lstate; la.lds_stride = 0;
-					if (ssw_shim_launch_literal(&la, c->stream)) { fail(c, "literal launch failed: %s", ssw_shim_last_error()); goto done; }
-				}
-			ssw_shim_event_record(e1, c->stream);
-			c->tm.fill_launches++;
-			for (int32_t q = 0; q < nq; ++q) c->tm.fill_cells += (Q->h_off[q + 1] - Q->h_off[q]) * (int64_t)refLen;
-			note_fill_kernel(c, c->tm.fill_cells, &best_fill_cells, "k_literal (lane model of the SSE2 kernels)", 0.0, 0, 1);
-		}
-		if (refLen > 0 && !literal) {
-			const int64_t stride = ((int64_t)refLen + 15) / 16 * 16 + 16;
-			const int64_t seg_stride = (stride / 16 + 4 + 3) / 4 * 4;      /* rows of the group arrays: 16-byte aligned, padded by >= 4 words (k_reduce_seg loads four groups at a time) */
-			/* ---- plan: tile geometry and scratch of every geometry bucket.  An allocation that fails although it is within the budget
-			   (contexts of ONE process sharing a device; across processes HIP over-subscribes silently) shrinks the budget and plans
-			   again -- to a quarter the first time, a budget that only just fits leaves nothing for the rest of the call, then by
-			   halves; not when every launch is down to one pair already (a smaller budget cannot shrink them further).  The shim clears
-			   HIP's sticky error after the failed allocation, so the launches that follow a successful retry do not report it again;
-			   ssw_gpu_set_budget starts the ladder afresh.  tests/test_emu_pipeline.py runs it. */
-#define ALIGN16(x) (((size_t)(x) + 15) / 16 * 16)
-			if (!bplans) bplans = (bplan*)calloc((size_t)nb, sizeof(bplan));
-			if (!bplans) { fail(c, "out of host memory%s", ""); goto done; }
-			int max_chunk, nact, conc, conc_refused = 0;
-plan_again:
-			max_chunk = 1; nact = 0;
-			size_t tot_cm = 0, tot_sg = 0, tot_bnd = 0, tot_cand = 0, tot_q = 0, tot_cs = 0;      /* all buckets side by side */
-			size_t max_cm = 0, max_sg = 0, max_bnd = 0, max_cand = 0;                              /* one bucket at a time */
-			int any_dbl = 0, any_chunked = 0;
-			for (int b = 0; b < nb; ++b) {
-				const bucket* B = &bk[b];
-				bplan* P = &bplans[b];
-				memset(P, 0, sizeof *P);
-				if (qdone[order[B->first_q]]) continue;     /* bucket already answered by the database-search path */
-				P->active = 1; ++nact;
-				const int32_t Pq = B->P16, halo_full = halo_for(Pq, maxmat, prm->gapE);
-				const int use_x = B->use_x;     /* long queries: strip kernel, one job per chain */
-				const int gran = use_x ? 1 : 16;     /* k_fill: one workgroup = 16 tiles of one pair */
-				int32_t tile, halo, ntiles;
-				int64_t want = 1;
-				int small_call = 0;
-				if ((int64_t)halo_full * 8 * gran < refLen) {
-					/* enough chains PER LAUNCH to fill the device several times over, halo overhead <= 1/8.  A launch covers the pairs
-					   whose column-maximum arrays fit the budget (8 bytes per column and pair): a 5 Mb target leaves 1600 pairs per
-					   launch, which with 16 tiles (one workgroup) per pair would fill little more than half of the device */
-					int64_t launch_pairs = use_x ? B->npairs : (int64_t)(c->cm_budget / (size_t)(8 * stride));
-					if (launch_pairs < 1) launch_pairs = 1;
-					if (launch_pairs > B->npairs) launch_pairs = B->npairs;
-					want = (4 * 32768 + B->npairs - 1) / B->npairs;
-					if (!use_x && launch_pairs * ((want + 15) / 16) < 6000) want = 16 * ((6000 + launch_pairs - 1) / launch_pairs);   /* >= ~2 rounds of workgroups per launch */
-					int64_t maxt = refLen / ((int64_t)halo_full * 8);
-					if (want > maxt) want = maxt;
-					want = (want + gran - 1) / gran * gran; if (want < gran) want = gran;      /* whole workgroups of 16 chains */
-				}
-				{
-					/* A call that cannot fill the device anyway -- one ssw_align pair, a handful of reads -- is bound by the LATENCY of a chain, tile +
-					   halo columns in sequence: then the tiles go down to half the halo (at least 64 columns) as long as all chains of the
-					   call still fit the device at once (since round 5: down to an eighth of the halo); the recomputed halos run on compute units that would idle.  One 150-bp read against a
-					   10-kb target: 736 steps instead of 10 000 (2.3 -> 0.x ms per ssw_align call, profiles/round4_latency.txt). */
-					/* chains a latency-bound call spreads over: for the 16-lane chains TWO workgroups (32 chains, two wavefronts per SIMD) per compute
-					   unit -- a step of a lone wavefront is bound by the latency of its dependent instructions (~800 cycles for ~75), a second one hides
-					   in it, a third and fourth only share the issue port (measured: 977 workgroups on 256 CUs 0.61 ms per call, 260: 0.57) */
-					int64_t slots = use_x ? (int64_t)c->dev_wave_slots : (int64_t)c->dev_cus * (c->device_share > 1 ? 96 : 32);      /* (several caller threads: what the device holds, shared below) */
-					if (c->device_share > 1) { slots /= c->device_share; if (slots < 256) slots = 256; }      /* other caller threads' pairs are on the device too */
-					const int64_t all_pairs = npairs_total > 0 ? npairs_total : 1;
-					if (all_pairs * want < slots && halo_full < refLen) {
-						/* (round 5: an eighth of the halo, not half -- a chain's latency is tile + halo steps and the halo is fixed; one 150-bp read against
-						   1 Mb: k_fill 240 -> ~185 us of the call's 0.53 ms, profiles/round5_latency_single_pair.json) */
-						/* ... for the 16-lane chains of a call that is alone on the device; the strip kernel (two wavefronts per SIMD by its LDS) and
-						   calls that share the device with other caller threads keep half a halo: their extra chains would only queue up */
-						const int div = !use_x && c->device_share <= 1 ? 8 : 2;
-						const int64_t mint = halo_full / div > 64 ? halo_full / div : 64;
-						int64_t small = slots / all_pairs;
-						if (small > refLen / mint) small = refLen / mint;
-						if (small > want) { want = small; small_call = 1; }
-					}
-				}
-				if (want <= 1) { ntiles = 1; tile = (refLen + 15) / 16 * 16; halo = 0; }
-				else {
-					if (!small_call || want >= gran) want = (want + gran - 1) / gran * gran;      /* (a small call may have fewer tiles than a workgroup has chains: the others stay idle) */
-					tile = (int32_t)(((refLen + want - 1) / want + 15) / 16 * 16);
-					ntiles = (refLen + tile - 1) / tile; halo = (halo_full + 15) / 16 * 16;     /* (more halo is always exact; multiples of 16 keep the 16-column groups inside one tile) */
-					if (ntiles <= 1) { ntiles = 1; tile = (refLen + 15) / 16 * 16; halo = 0; }
-				}
-				const int64_t maxcols = (((int64_t)tile + halo < refLen ? (int64_t)tile + halo : refLen) + 31) / 16 * 16;
-				int64_t per_pair = 8 * stride + (use_x ? 16 * maxcols * ntiles : 0);
-				int64_t chunk = (int64_t)(c->cm_budget / (size_t)per_pair);
-				/* optional: two column-maximum buffer sets so that k_reduce of chunk i runs on a second stream beside k_fill of chunk i+1 */
-				/* measured on MI355X (config 2): overlapping costs more than it saves -- the fill runs at ~100 % VALU issue, so the
-				   reduction's waves only take slots from it (2347 ms/step with, 2160 ms without); kept as an opt-in experiment */
-				const int dbl = !use_x && chunk < B->npairs && c->kn.overlap;
-				/* Pipelined launches (round 6).  A bucket that needs several launches -- its column maxima do not fit the budget at once -- used to
-				   run them one after the other on one stream, and every launch ended with a last, partly filled round of workgroups: all
-				   workgroups of a launch take the same ~50 ms (config 2), so the device drains for most of a workgroup's duration at two or three
-				   workgroups per compute unit instead of seven -- three times per 100 000 reads at a whole-HBM budget, 25 times at 16 GiB (-4 %).
-				   Now the launches alternate between the main stream and a second stream, each with its own half of the scratch: the two
-				   launches in flight share the compute units, each one's drain and reduction is covered by the other, and launch i + 2 follows
-				   the reduction of launch i on its stream.  Same work, same records; only the order in which workgroups reach the compute
-				   units changes.  The second stream has the main stream's priority: at the LOWEST priority (the first form; SSW_GPU_PIPE_PRIO=low
-				   in the hooks build) its launches only got the slots the main stream's left over, fell behind and ran out the series alone --
-				   config 2 on one box, two / four / eight parts at the lowest priority against two at equal priority: 10 073 / 10 211 / 10 282 /
-				   10 353 GCUPS under 16 GiB, 10 377 / 10 446 / 10 423 / 10 480 under 64 GiB, 10 398-10 437 / 10 413 / 10 443 / 10 469-10 514 with
-				   the whole HBM; more than two parts at equal priority lose again (10 127 under 64 GiB: the streams share hardware queues).
-				   profiles/round6_pipeline_parts.txt. */
-				const int pipe = !use_x && !dbl && chunk < B->npairs && !c->kn.no_pipe;
-				int parts = dbl || pipe ? 2 : 1;
-				if (pipe && c->kn.pipe_parts) parts = c->kn.pipe_parts;
-				if (parts > 1) chunk = (int64_t)((c->cm_budget / (size_t)parts) / (size_t)per_pair);
-				if (chunk < 1) chunk = 1;
-				if (chunk > B->npairs) chunk = B->npairs;
-				if (!use_x && chunk < B->npairs) {
-					/* All workgroups of a launch do the same amount of work, so a launch is as slow as the CU that got one workgroup more
-					   than the others: the launches of a bucket get the same number of pairs (not full chunks and a remainder), and that
-					   number makes the workgroup count a multiple of the CU count (256 on an unpartitioned MI355X; read from the device).
-					   16 tiles per pair left 1600 workgroups per launch on a 5 Mb target: 6 or 7 per CU, 12 % lost. */
-					const int64_t bpp = (ntiles + 15) / 16;
-					int64_t nl = (B->npairs + chunk - 1) / chunk;
-					/* a pipelined series: as many launches on one stream as on the other, so that both reach the end together (5 launches were 3 + 2: the
-					   last one ran alone, its drain exposed) */
-					if (pipe && parts > 1 && !c->kn.pipe_any_count && nl % parts) nl += parts - nl % parts;
-					int64_t even = (B->npairs + nl - 1) / nl;                      /* pairs per launch if all launches are alike */
-					const int64_t ncu = c->dev_cus;
-					const int64_t unit = (ncu / (bpp > ncu ? ncu : bpp) > 0 ? ncu / (bpp > ncu ? ncu : bpp) : 1) * (B->half ? 2 : 1);      /* pairs that make one workgroup per compute unit (k_fill8: two pairs per workgroup) */
-					even = (even + unit - 1) / unit * unit;
-					if (even <= chunk) chunk = even;
-					else if (chunk >= unit) chunk = chunk / unit * unit;
-					if (B->half && (chunk & 1) && chunk > 1) --chunk;      /* whole workgroups of two pairs (a chunk of one pair stays: the second chain is dead) */
-				}
-				P->tile = tile; P->halo = halo; P->ntiles = ntiles; P->maxcols = maxcols; P->chunk = chunk; P->dbl = dbl; P->pipe = pipe && chunk < B->npairs ? parts : 0;
-				P->seg = !dbl && !c->kn.no_seg_reduce ;      /* the fill kernels also leave the maxima of 16-column groups, which is all the reduction reads */
-				P->cm_bytes = ALIGN16(4 * stride * chunk) * (P->pipe ? P->pipe : 1);      /* (pipe: one set per stream) */
-				P->sg_bytes = P->seg ? ALIGN16(4 * seg_stride * chunk) * (P->pipe ? P->pipe : 1) : 0;
-				P->bnd_bytes = use_x ? ALIGN16(16 * maxcols * ntiles * chunk) : 0;
-				P->cand_bytes = use_x ? ALIGN16(32 * ntiles * chunk) : 0;   /* 2 halves x 4 ints per job */
-				if (use_x && B->lanes == 64) { P->q_ints = chainq_queue_ints(chunk * ntiles * B->strips); P->cs_ints = chainq_cands_ints(chunk * ntiles * B->strips); }
-				P->cm_off = tot_cm; P->sg_off = tot_sg; P->bnd_off = tot_bnd; P->cand_off = tot_cand; P->q_off = tot_q; P->cs_off = tot_cs;
-				tot_cm += P->cm_bytes; tot_sg += P->sg_bytes; tot_bnd += P->bnd_bytes; tot_cand += P->cand_bytes; tot_q += P->q_ints; tot_cs += P->cs_ints;
-				if (P->cm_bytes > max_cm) max_cm = P->cm_bytes;
-				if (P->sg_bytes > max_sg) max_sg = P->sg_bytes;
-				if (P->bnd_bytes > max_bnd) max_bnd = P->bnd_bytes;
-				if (P->cand_bytes > max_cand) max_cand = P->cand_bytes;
-				if (chunk > max_chunk) max_chunk = (int)(chunk > 0x7fffffff ? 0x7fffffff : chunk);
-				any_dbl |= dbl; any_chunked |= chunk < B->npairs;
-			}
-			/* Geometry buckets side by side (round 4).  A batch of mixed read lengths -- the reference's own benchmark: 1000 reads of 25-540 bp
-			   -- is ~30 buckets with a few pairs each; one after the other on one stream every bucket pays its own partly filled last round
-			   of workgroups and the strip kernel's few long jobs leave most of the device idle.  When every bucket is ONE launch and all of
-			   them fit the budget together, each gets its own slice of the scratch buffers and its fill + reduction go to one of the side
-			   streams; the main stream continues after all of them.  SSW_GPU_SERIAL_BUCKETS=1 keeps the old order (tests compare). */
-			conc = nact > 1 && !conc_refused && !c->kn.serial_buckets && !c->kn.no_seg_reduce &&     /* (k_reducem reads group maxima only) */ !any_dbl && !any_chunked && 2 * tot_cm + 2 * tot_sg + tot_bnd + tot_cand <= c->cm_budget;
-			if (!conc) for (int b = 0; b < nb; ++b) { bplan* P = &bplans[b]; P->cm_off = P->sg_off = P->bnd_off = P->cand_off = 0; P->q_off = P->cs_off = 0; }
-			/* (side by side the buffers are the SUM over the buckets: before the budget is cut, the buckets go one after the other -- the maximum) */
-#define SSW_ALLOC_RETRY() do { if (conc) { conc_refused = 1; c->err[0] = 0; goto plan_again; } if (c->cm_budget > ((size_t)2 << 20) && max_chunk > 1) { c->cm_budget /= c->budget_shrunk ? 2 : 4; c->budget_shrunk = 1; c->err[0] = 0; goto plan_again; } goto done; } while (0)
-			unsigned char *base_cm16 = 0, *base_cm8 = 0, *base_cmB16 = 0, *base_cmB8 = 0, *base_sg16 = 0, *base_sg8 = 0, *base_bnd = 0, *base_cand = 0;
-			int32_t *base_q = 0, *base_cs = 0;
-			if (nact > 0) {
-				base_cm16 = (unsigned char*)ensure(c, &c->cm16, conc ? tot_cm : max_cm);
-				base_cm8 = (unsigned char*)ensure(c, &c->cm8, conc ? tot_cm : max_cm);
-				if (!base_cm16 || !base_cm8) SSW_ALLOC_RETRY();
-				base_cmB16 = base_cm16; base_cmB8 = base_cm8;
-				if (any_dbl) {
-					base_cmB16 = (unsigned char*)ensure(c, &c->cm16b, max_cm); base_cmB8 = (unsigned char*)ensure(c, &c->cm8b, max_cm);
-					if (!base_cmB16 || !base_cmB8) SSW_ALLOC_RETRY();
-				}
-				if (max_sg) {
-					base_sg16 = (unsigned char*)ensure(c, &c->sg16, conc ? tot_sg : max_sg); base_sg8 = (unsigned char*)ensure(c, &c->sg8, conc ? tot_sg : max_sg);
-					if (!base_sg16 || !base_sg8) SSW_ALLOC_RETRY();
-				}
-				if (max_bnd) {
-					base_bnd = (unsigned char*)ensure(c, &c->bnd, conc ? tot_bnd : max_bnd); base_cand = (unsigned char*)ensure(c, &c->cand, conc ? tot_cand : max_cand);
-					if (!base_bnd || !base_cand) SSW_ALLOC_RETRY();
-				}
-				if (conc && tot_q) {
-					base_q = (int32_t*)ensure(c, &c->queue, sizeof(int32_t) * tot_q); base_cs = (int32_t*)ensure(c, &c->cands, sizeof(int32_t) * tot_cs);
-					if (!base_q || !base_cs) SSW_ALLOC_RETRY();
-				}
-			}
-			void *ge0 = 0, *ge1 = 0; int side_used[SSW_TSTREAMS]; int nside = 0;
-			int ndefer = 0;
-			if (!defer) defer = (struct fill_defer*)malloc(sizeof(struct fill_defer) * (size_t)(nb > 0 ? nb : 1));
-			if (!rdefer) rdefer = (ssw_reduce_args*)malloc(sizeof(ssw_reduce_args) * (size_t)(nb > 0 ? nb : 1));
-			if (!defer || !rdefer) { fail(c, "out of host memory%s", ""); goto done; }
-			for (int sx = 0; sx < SSW_TSTREAMS; ++sx) side_used[sx] = 0;
-			if (conc) {
-				ge0 = next_event(c); ge1 = next_event(c);
-				if (ssw_shim_event_record(ge0, c->stream) || ssw_shim_event_record(c->ev_db, c->stream)) { fail(c, "event record failed: %s", ssw_shim_last_error()); goto done; }
-				/* largest bucket first: the side streams are served round-robin, and the device drains the big launches while the small ones fill its gaps */
-				for (int i = 0; i < nb; ++i) border[i] = i;
-				for (int i = 1; i < nb; ++i) {
-					const int v = border[i]; int j = i;
-					while (j > 0 && (int64_t)bk[border[j - 1]].npairs * bk[border[j - 1]].P16 < (int64_t)bk[v].npairs * bk[v].P16) { border[j] = border[j - 1]; --j; }
-					border[j] = v;
-				}
-			}
-			int nrdefer = 0;
-			/* side by side: the short-query buckets first (their grids are the bulk of the work and go to the hardware queues at once), then the
-			   strip kernel's launches */
-			for (int pass_x = 0; pass_x < (conc ? 2 : 1); ++pass_x) {
-			for (int bi_ = 0; bi_ < nb; ++bi_) {
-				const int b = conc ? border[bi_] : bi_;
-				const bucket* B = &bk[b];
-				const bplan* P = &bplans[b];
-				if (!P->active) continue;
-				if (conc && (B->use_x != 0) != pass_x) continue;
-				const int use_x = B->use_x, dbl = P->dbl;
-				const int32_t tile = P->tile, halo = P->halo, ntiles = P->ntiles;
-				const int64_t maxcols = P->maxcols, chunk = P->chunk;
-				void* st = c->stream;
-				if (conc) {
-					/* The runtime maps streams onto FOUR hardware queues (seen on ROCm 7.2: the context's eight streams land on queues
-					   1 2 3 4 4 3 2 1), and launches that share a queue run one after the other: the strip kernel's few, latency-bound
-					   launches all go to ONE side stream, in sequence (together they are shorter than the short-query grids beside them);
-					   the multi-bucket grids take three others.  profiles/round4_config6_timeline.txt */
-					const int sx = 5;
-					(void)nside;
-					st = c->tstream[sx];
-					if (!side_used[sx]) { side_used[sx] = 1; if (ssw_shim_stream_wait_event(st, c->ev_db)) { fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; } }
-				}
-				uint32_t* d_bnd = use_x ? (uint32_t*)(base_bnd + P->bnd_off) : 0;
-				int32_t* d_cand = use_x ? (int32_t*)(base_cand + P->cand_off) : 0;
-				if (c->kn.no_track) d_cand = 0;   /* diagnostic: always run the locate pass */
-				uint32_t* d_cmA16 = (uint32_t*)(base_cm16 + P->cm_off); uint32_t* d_cmA8 = (uint32_t*)(base_cm8 + P->cm_off);
-				uint32_t* d_cmB16 = dbl ? (uint32_t*)base_cmB16 : d_cmA16; uint32_t* d_cmB8 = dbl ? (uint32_t*)base_cmB8 : d_cmA8;
-				uint32_t* d_sg16 = P->seg ? (uint32_t*)(base_sg16 + P->sg_off) : 0; uint32_t* d_sg8 = P->seg ? (uint32_t*)(base_sg8 + P->sg_off) : 0;
-				int launch_i = 0;
-				const int pipe = conc ? 0 : P->pipe;      /* the number of parts: 0 (not pipelined), 2 (a hook: up to 8) */
-				void *pe0 = 0, *pe1 = 0;
-				if (pipe) {
-					pe0 = next_event(c); pe1 = next_event(c);
-					if (ssw_shim_event_record(pe0, c->stream)) { fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; }
-					for (int k = 0; k < pipe - 1; ++k) {
-						if (!c->pstream[k]) { c->pstream[k] = c->kn.pipe_low_prio ? ssw_shim_stream_create_low() : ssw_shim_stream_create(); c->ev_pipe[k] = ssw_shim_event_create(); }
-						if (!c->pstream[k] || !c->ev_pipe[k]) { fail(c, "stream creation failed: %s", ssw_shim_last_error()); goto done; }
-						/* (the extra streams start after everything the main stream has queued so far: the call's uploads, the record memset) */
-						if (ssw_shim_stream_wait_event(c->pstream[k], pe0)) { fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; }
-					}
-				}
-				uint32_t* const d_sgA16 = d_sg16; uint32_t* const d_sgA8 = d_sg8;
-				for (int32_t p0 = 0; p0 < B->npairs; p0 += (int32_t)chunk, ++launch_i) {
-					const int32_t np = B->npairs - p0 < chunk ? B->npairs - p0 : (int32_t)chunk;
-					const int bi = pipe ? launch_i % pipe : dbl ? (launch_i & 1) : 0;
-					uint32_t* d_cm16 = bi ? d_cmB16 : d_cmA16; uint32_t* d_cm8 = bi ? d_cmB8 : d_cmA8;
-					if (pipe) {      /* launch i: part i mod parts of the scratch; parts 1.. on the extra streams (in order on each: launch i + parts follows the reduction of launch i) */
-						st = bi ? c->pstream[bi - 1] : c->stream;
-						d_cm16 = (uint32_t*)((unsigned char*)d_cmA16 + (size_t)bi * (P->cm_bytes / (size_t)pipe)); d_cm8 = (uint32_t*)((unsigned char*)d_cmA8 + (size_t)bi * (P->cm_bytes / (size_t)pipe));
-						d_sg16 = P->seg ? (uint32_t*)((unsigned char*)d_sgA16 + (size_t)bi * (P->sg_bytes / (size_t)pipe)) : 0;
-						d_sg8 = P->seg ? (uint32_t*)((unsigned char*)d_sgA8 + (size_t)bi * (P->sg_bytes / (size_t)pipe)) : 0;
-					}
-					if (dbl && launch_i >= 2) ssw_shim_stream_wait_event(c->stream, c->ev_red[bi]);    /* the buffer set is free again */
-					ssw_fill_args fa;
-					fa.tgt = d_tgt; fa.refLen = refLen; fa.qcodes = Q->d_codes; fa.qoff = Q->d_off;
-					fa.pairs = d_pairs + B->first_pair + p0; fa.npairs = np; fa.mat = d_mat; fa.n = n;
-					fa.gapO2 = gapO2; fa.gapE2 = gapE2; fa.tile = tile; fa.halo = halo; fa.ntiles = ntiles;
-					fa.bpp = (ntiles + 15) / 16; fa.cm16 = d_cm16; fa.cm8 = d_cm8; fa.cm_stride = stride;
-					fa.sg16 = d_sg16; fa.sg8 = d_sg8; fa.seg_stride = seg_stride;
-					/* column-frame form of the recurrence whenever the bucket's scores leave room for the frame offsets below 31744 (no cell of
-					   the bucket scores more than its padded length x max(mat)); else plain int16 */
-					fa.form = 0; fa.fr_base = 0; fa.fr_kmask = 0;
-					if (fill_form != 0 && ssw_frame_params(&c->kn, (int64_t)16 * B->R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 16, &fa.fr_base, &fa.fr_kmask)) fa.form = 3;
-					/* half-row chains: single-bucket launches of the frame form only (the frame of a chain of 8 positions) */
-					int use_half = 0;
-					if (B->half && !use_x && !conc && fa.form == 3) {
-						int32_t hb = 0, hk = 0;
-						if (ssw_frame_params(&c->kn, (int64_t)16 * B->R * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 8, &hb, &hk)) { use_half = 1; fa.fr_base = hb; fa.fr_kmask = hk; }
-					}
-					int xform = 0;
-					int32_t xfr_base = 0, xfr_kmask = 0;
-					if (fill_form != 0 && B->lanes == 64 &&
-					    ssw_frame_params(&c->kn, (int64_t)B->P16 * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 64, &xfr_base, &xfr_kmask)) xform = 3;
-					void *e0 = 0, *e1 = 0;
-					if (!conc && !pipe) { e0 = next_event(c); e1 = next_event(c); ssw_shim_event_record(e0, st); }
-					if (use_x) {
-						ssw_chainx_args xa; memset(&xa, 0, sizeof xa);
-						xa.tgt = d_tgt; xa.refLen = refLen; xa.qcodes = Q->d_codes; xa.qoff = Q->d_off; xa.mat = d_mat; xa.n = n;
-						xa.gapO2 = gapO2; xa.gapE2 = gapE2; xa.gapE = prm->gapE; xa.maxmat = maxmat; xa.njobs = np * ntiles;
-						xa.pairs = fa.pairs; xa.tile = tile; xa.halo = halo; xa.ntiles = ntiles; xa.cm16 = d_cm16; xa.cm8 = d_cm8;
-						xa.cm_stride = stride; xa.bnd = d_bnd; xa.bnd_stride = maxcols; xa.cand = d_cand; xa.lanes = B->lanes;
-						xa.sg16 = d_sg16; xa.sg8 = d_sg8; xa.seg_stride = seg_stride;
-						if (B->lanes == 64) {     /* strips of all jobs behind one work queue (k_chainq) */
-							const int qgrid = chainq_grid(c, B->R, 0, n);
-							if (conc ? chainq_setup(c, &xa, B->strips, (int64_t)np * ntiles, qgrid, base_q + P->q_off, base_cs + P->cs_off, st)
-							         : chainq_prepare(c, &xa, B->strips, (int64_t)np * ntiles, qgrid)) goto done;
-							xa.form = xform; xa.fr_base = xfr_base; xa.fr_kmask = xfr_kmask; xa.tail_R = B->tailR;
-							if (c->kn.debug) fprintf(stderr, "[ssw_gpu] chainq fill: R %d (last strip %d), %d jobs x %d strips, %d wavefronts, %s tickets, form %d\n",
-							                                     B->R, B->tailR ? B->tailR : B->R, np * ntiles, B->strips, qgrid, xa.whole_jobs ? "job" : "strip", xa.form);
-							if (ssw_shim_launch_chainq(B->R, 0, &xa, qgrid, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
-							if (c->kn.debug) { const int src = ssw_shim_stream_sync(st); fprintf(stderr, "[ssw_gpu] chainq fill done (sync rc %d: %s)\n", src, src ? ssw_shim_last_error() : "ok"); }
-						} else
-						if (ssw_shim_launch_chainx(B->R, 0, &xa, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
-					} else
-					if (conc) {      /* short-query buckets side by side: their workgroups join the grid of their register class (k_fillm, below) */
-						defer[ndefer].fa = fa; defer[ndefer].R = B->R; defer[ndefer].wgs = (int64_t)np * fa.bpp; defer[ndefer].group = ssw_shim_fill_class(B->R) * 2 + (fa.form == 3);
-					} else
-					if (use_half) {
-						if (ssw_shim_launch_fill8(B->half, &fa, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
-					} else
-					if (ssw_shim_launch_fill(B->R, &fa, st)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
-					if (!conc && !pipe) ssw_shim_event_record(e1, st);      /* (pipe: one event pair around the whole series, below -- the launches overlap) */
-					if (!conc) { c->tm.fill_launches++; if (pipe) c->tm.fill_pipelined++; }
-					{
-						int64_t cols = 0;
-						for (int32_t k = 0; k < ntiles; ++k) {
-							int64_t lo = (int64_t)k * tile, hi = lo + tile < refLen ? lo + tile : refLen;
-							int64_t cf = lo - halo > 0 ? lo - halo : 0;
-							cols += hi - cf;
-						}
-						const int64_t lc = cols * (int64_t)(use_half ? 8 * B->half : B->lanes * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips)) * 2 * np;
-						c->tm.fill_cells += lc;
-						char nm[48];
-						if (use_half) snprintf(nm, sizeof nm, "k_fill8<%d,frame>", B->half);
-						else if (!use_x) snprintf(nm, sizeof nm, "k_fill<%d,%s>", B->R, fa.form == 3 ? "frame" : "int16");
-						else if (B->lanes == 64 && B->tailR) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR);
-						else if (B->lanes == 64) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
-						else snprintf(nm, sizeof nm, "k_chainx<%d,16 lanes> x %d strips", B->R, B->strips);
-						note_fill_kernel(c, lc, &best_fill_cells, nm, !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
-					}
-					ssw_reduce_args ra;
-					ra.cm16 = d_cm16; ra.cm8 = d_cm8; ra.cm_stride = stride; ra.refLen = refLen; ra.pairs = fa.pairs; ra.npairs = np;
-					ra.qoff = Q->d_off; ra.maskLen = prm->maskLen; ra.bias = bias; ra.score_size = prm->score_size;
-					ra.flag = prm->flag; ra.filters = prm->filters; ra.res = d_res; ra.cand = d_cand; ra.tile = tile; ra.ntiles = ntiles;
-					ra.sg16 = d_sg16; ra.sg8 = d_sg8; ra.seg_stride = seg_stride;
-					if (dbl) {
-						ssw_shim_event_record(c->ev_fill[bi], c->stream);
-						ssw_shim_stream_wait_event(c->stream2, c->ev_fill[bi]);
-						if (ssw_shim_launch_reduce(&ra, c->stream2)) { fail(c, "reduce launch failed: %s", ssw_shim_last_error()); goto done; }
-						ssw_shim_event_record(c->ev_red[bi], c->stream2);
-					} else
-					if (conc) { rdefer[nrdefer++] = ra; if (!use_x) ++ndefer; }      /* all reductions of the group as one grid, after the join (below) */
-					else
-					if (ssw_shim_launch_reduce(&ra, st)) { fail(c, "reduce launch failed: %s", ssw_shim_last_error()); goto done; }
-				}
-				if (dbl) {   /* everything later on the main stream sees all records of this bucket */
-					ssw_shim_stream_wait_event(c->stream, c->ev_red[0]);
-					if (launch_i > 1) ssw_shim_stream_wait_event(c->stream, c->ev_red[1]);
-				}
-				if (pipe) {   /* the main stream continues after the extra streams' last reductions; the series is timed as one (its reductions included: ~0.1 ms each) */
-					for (int k = 0; k < pipe - 1; ++k)
-						if (ssw_shim_event_record(c->ev_pipe[k], c->pstream[k]) || ssw_shim_stream_wait_event(c->stream, c->ev_pipe[k])) { fail(c, "stream join failed: %s", ssw_shim_last_error()); goto done; }
-					if (ssw_shim_event_record(pe1, c->stream)) { fail(c, "stream join failed: %s", ssw_shim_last_error()); goto done; }
-					st = c->stream;
-				}
-			}
-			if (conc && pass_x == 0 && ndefer > 0) {
-				/* one grid per (register class, form) of the deferred short-query buckets, longest chains first */
-				const size_t rec = sizeof(ssw_fill_args);
-				unsigned char* htab = (unsigned char*)calloc((rec + 16) * (size_t)ndefer + 64 * 6, 1);
-				unsigned char* dtab = (unsigned char*)ensure(c, &c->fmtab, (rec + 16) * (size_t)ndefer + 64 * 6);
-				if (!htab || !dtab) { free(htab); if (!htab) fail(c, "out of host memory%s", ""); goto done; }
-				size_t at = 0;
-				for (int gi_ = 0; gi_ < 6; ++gi_) {
-					int64_t gw[6] = { 0, 0, 0, 0, 0, 0 };      /* groups by size, largest first */
-					for (int i = 0; i < ndefer; ++i) gw[defer[i].group] += defer[i].wgs * defer[i].R;
-					int gord[6] = { 0, 1, 2, 3, 4, 5 };
-					for (int i = 1; i < 6; ++i) { const int v = gord[i]; int j = i; while (j > 0 && gw[gord[j - 1]] < gw[v]) { gord[j] = gord[j - 1]; --j; } gord[j] = v; }
-					const int g = gord[gi_];
-					int idx[SSW_RMAX + 1], ng = 0;
-					for (int i = 0; i < ndefer; ++i) if (defer[i].group == g) idx[ng++] = i;
-					if (ng == 0) continue;
-					for (int i = 1; i < ng; ++i) { const int v = idx[i]; int j = i; while (j > 0 && defer[idx[j - 1]].R < defer[v].R) { idx[j] = idx[j - 1]; --j; } idx[j] = v; }
-					const size_t a0 = at, a1 = a0 + ALIGN16(rec * (size_t)ng), a2 = a1 + ALIGN16(4 * ((size_t)ng + 1));
-					int32_t* hfirst = (int32_t*)(htab + a1); int32_t* hR = (int32_t*)(htab + a2);
-					int64_t total = 0;
-					for (int i = 0; i < ng; ++i) { memcpy(htab + a0 + rec * (size_t)i, &defer[idx[i]].fa, sizeof(ssw_fill_args)); hfirst[i] = (int32_t)total; hR[i] = defer[idx[i]].R; total += defer[idx[i]].wgs; }
-					hfirst[ng] = (int32_t)total;
-					at = a2 + ALIGN16(4 * (size_t)ng);
-					if (total > 0x7fffffff) { free(htab); fail(c, "internal error: %s", "more than 2^31 workgroups in one multi-bucket fill launch"); goto done; }
-					static const int grid_streams[3] = { 0, 1, 4 };      /* three different hardware queues (see above) */
-					const int sx = grid_streams[nside++ % 3];
-					void* st = c->tstream[sx];
-					if (!side_used[sx]) { side_used[sx] = 1; if (ssw_shim_stream_wait_event(st, c->ev_db)) { free(htab); fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; } }
-					ssw_fillm_args ma; ma.sub = (const ssw_fill_args*)(dtab + a0); ma.first_wg = (const int32_t*)(dtab + a1); ma.subR = (const int32_t*)(dtab + a2); ma.nsub = ng;
-					if (ssw_shim_h2d(dtab + a0, htab + a0, at - a0, st) || ssw_shim_launch_fillm(&ma, hR, n, g & 1 ? 3 : 0, total, st)) {
-						free(htab); fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done;
-					}
-				}
-				free(htab);
-			}
-			}      /* pass_x */
-			if (conc) {      /* the main stream continues after all of them; the group counts as one launch (its event pair brackets the side streams' work) */
-				for (int sx = 0; sx < SSW_TSTREAMS; ++sx)
-					if (side_used[sx] && (ssw_shim_event_record(c->tev[sx], c->tstream[sx]) || ssw_shim_stream_wait_event(c->stream, c->tev[sx]))) {
-						fail(c, "stream join failed: %s", ssw_shim_last_error()); goto done;
-					}
-				if (nrdefer > 0) {      /* every bucket's reduction in one grid: one workgroup per pair */
-					const size_t rec = sizeof(ssw_reduce_args), a1 = ALIGN16(rec * (size_t)nrdefer);
-					unsigned char* htab = (unsigned char*)calloc(a1 + 4 * ((size_t)nrdefer + 1) + 16, 1);
-					unsigned char* dtab = (unsigned char*)ensure(c, &c->fmtab, a1 + 4 * ((size_t)nrdefer + 1) + 16);
-					if (!htab || !dtab) { free(htab); if (!htab) fail(c, "out of host memory%s", ""); goto done; }
-					int32_t* hfirst = (int32_t*)(htab + a1);
-					int64_t total = 0;
-					for (int i = 0; i < nrdefer; ++i) { memcpy(htab + rec * (size_t)i, &rdefer[i], rec); hfirst[i] = (int32_t)total; total += rdefer[i].npairs; }
-					hfirst[nrdefer] = (int32_t)total;
-					ssw_reducem_args rm; rm.sub = (const ssw_reduce_args*)dtab; rm.first_wg = (const int32_t*)(dtab + a1); rm.nsub = nrdefer;
-					const int bad = ssw_shim_h2d(dtab, htab, a1 + 4 * ((size_t)nrdefer + 1), c->stream) || ssw_shim_launch_reducem(&rm, total, c->stream);
-					free(htab);
-					if (bad) { fail(c, "reduce launch failed: %s", ssw_shim_last_error()); goto done; }
-				}
-				ssw_shim_event_record(ge1, c->stream);
-				c->tm.fill_launches++;
-			}
+			if (tp.conc) { if (fill_side_by_side(c, &bc, &tp)) goto done; }
+			else for (int b = 0; b < bc.nb; ++b) if (tp.bp[b].active && fill_bucket_series(c, &bc, &tp, b)) goto done;
 		}
 		ssw_shim_event_record(c->ev_a, c->stream);
 		CALL_TRACE("fill + reduction enqueued");
 
-		if (refLen > 0 && !literal) {   /* read_end1 always (ssw.c:342-351); begin position only when asked for (ssw.c:916) */
-			win_in wi; memset(&wi, 0, sizeof wi);
-			wi.Q = Q; wi.prm = prm; wi.d_tgt = d_tgt; wi.refLen = refLen; wi.d_mat = d_mat; wi.n = n; wi.maxmat = maxmat; wi.minmat = minmat;
-			wi.fill_form = fill_form; wi.d_res = d_res; wi.g = geom;
-			/* a batch of many buckets: the k_capture launches (one small, latency-bound grid per bucket) side by side -- a bucket keeps its
-			   side stream for both passes (the reverse pass reads what the locate pass wrote) */
-			int nwin = 0, wused[SSW_TSTREAMS];
-			for (int b = 0; b < nb; ++b) if (!qdone[order[bk[b].first_q]] && !window_on_strips(&bk[b], n)) ++nwin;
-			const int fan = nwin > 2 && !c->kn.serial_buckets;
-			for (int sx = 0; sx < SSW_TSTREAMS; ++sx) wused[sx] = 0;
-			if (fan && ssw_shim_event_record(c->ev_db, c->stream)) { fail(c, "event record failed: %s", ssw_shim_last_error()); goto done; }
-			for (int pass = 0; pass < (prm->flag != 0 ? 2 : 1); ++pass)
-				for (int b = 0; b < nb; ++b) {
-					const bucket* B = &bk[b];
-					if (qdone[order[B->first_q]]) continue;
-					void* st = 0;
-					if (fan && !window_on_strips(B, n)) {
-						const int sx = b % SSW_TSTREAMS;
-						st = c->tstream[sx];
-						if (!wused[sx]) { wused[sx] = 1; if (ssw_shim_stream_wait_event(st, c->ev_db)) { fail(c, "stream wait failed: %s", ssw_shim_last_error()); goto done; } }
-					}
-					if (window_pass(c, &wi, B, pass, d_qlist + B->first_q, B->nq, st)) goto done;
-				}
-			for (int sx = 0; sx < SSW_TSTREAMS; ++sx)
-				if (wused[sx] && (ssw_shim_event_record(c->tev[sx], c->tstream[sx]) || ssw_shim_stream_wait_event(c->stream, c->tev[sx]))) {
-					fail(c, "stream join failed: %s", ssw_shim_last_error()); goto done;
-				}
-		}
+		if (refLen > 0 && !bc.literal && window_phase(c, &bc, &tp)) goto done;
 		ssw_shim_event_record(c->ev_b, c->stream);
 		CALL_TRACE("window passes enqueued");
 
-		/* traceback (+ SAM-style rewrite) of the alignments whose record asks for a CIGAR */
 		trace_out tro; memset(&tro, 0, sizeof tro);
-		if ((prm->flag & 7) != 0 && refLen > 0) {
-			const int32_t halo_max = halo_for((maxlen + 15) / 16 * 16, maxmat, prm->gapE);
-			trace_in tri; memset(&tri, 0, sizeof tri);
-			tri.Q = Q; tri.prm = prm; tri.d_tgt = d_tgt; tri.d_mat = d_mat; tri.n = n; tri.d_res = d_res; tri.nslots = nq;
-			tri.ids = order; tri.nids = nqa; tri.d_list = d_qlist; tri.hneed = hneed; tri.maxlen = maxlen; tri.ref_span = halo_max < refLen ? halo_max : refLen;
-			tri.list_on_device = 1;
-			if (literal) {
-				/* gapO <= gapE: the halo argument (every gap base costs at least gapE) does not bound an alignment's reference span -- a gap base can
-				   cost gapO, and with gapO = 0 nothing at all: 33 read bases against 346 target bases is a legal answer of the reference.  This regime
-				   is not a throughput path: take the spans the window passes actually found (one download) instead of a bound.  CIGAR slots and the
-				   traceback's widest band are then exact for this batch. */
-				if (ssw_shim_d2h(hres, d_res, sizeof(ssw_dres) * (size_t)nq, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
-				int64_t rspan = 1;
-				for (int32_t q = 0; q < nq; ++q)
-					if (hres[q].want_cigar && hres[q].status == 0 && (int64_t)hres[q].ref_end1 - hres[q].ref_begin1 + 1 > rspan) rspan = (int64_t)hres[q].ref_end1 - hres[q].ref_begin1 + 1;
-				tri.ref_span = rspan;
-			}
-			if (trace_phase(c, &tri, &tro)) goto done;
-			if (tro.list_dirty && ti + 1 < tcount && ssw_shim_h2d(d_qlist, order, sizeof(int32_t) * (size_t)nqa, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
-		}
-		uint32_t* const d_cig = tro.d_cig;
+		if ((prm->flag & 7) != 0 && refLen > 0 && batch_trace(c, &bc, &tp, ti + 1 == tcount, &tro)) goto done;
 		ssw_shim_event_record(c->ev_c, c->stream);
 		CALL_TRACE("traceback enqueued / negotiated");
 
 		if (chainq_check(c)) goto done;
-		if (ssw_shim_d2h(hres, d_res, sizeof(ssw_dres) * (size_t)nq, c->stream) || ssw_shim_stream_sync(c->stream)) {
+		if (ssw_shim_d2h(bc.hres, bc.d_res, sizeof(ssw_dres) * (size_t)nq, c->stream) || ssw_shim_stream_sync(c->stream)) {
 			fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
 		}
-		/* CIGARs: pack the used slots into one device pool, one download */
-		int64_t* goffs = 0; int64_t gwords = 0;
-		for (int32_t q = 0; q < nq; ++q) if (hres[q].cigarLen > 0 && hres[q].status == 0) gwords += hres[q].cigarLen;
-		if (gwords > 0) {
-			goffs = (int64_t*)malloc(sizeof(int64_t) * (size_t)nq);
-			if (!goffs) { fail(c, "out of host memory%s", ""); goto done; }
-			int64_t at = 0;
-			for (int32_t q = 0; q < nq; ++q) { goffs[q] = at; if (hres[q].cigarLen > 0 && hres[q].status == 0) at += hres[q].cigarLen; }
-			int64_t* d_goff = (int64_t*)ensure(c, &c->goff, sizeof(int64_t) * (size_t)nq);
-			uint32_t* d_gpool = (uint32_t*)ensure(c, &c->gpool, sizeof(uint32_t) * (size_t)gwords);
-			if (!d_goff || !d_gpool || stage_reserve(c, &pool, gwords)) { free(goffs); goto done; }
-			if (nq <= 4) {      /* a handful of alignments: every CIGAR straight from its slot (no offset upload, no gather launch) */
-				for (int32_t q = 0; q < nq; ++q)
-					if (hres[q].cigarLen > 0 && hres[q].status == 0 &&
-					    ssw_shim_d2h(pool.words + pool.n + goffs[q], d_cig + hres[q].cigar_off, sizeof(uint32_t) * (size_t)hres[q].cigarLen, c->stream)) {
-						fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); free(goffs); goto done;
-					}
-			} else {
-			ssw_gather_args ga; ga.src = d_cig; ga.res = d_res; ga.dst_off = d_goff; ga.dst = d_gpool; ga.nq = nq;
-			if (ssw_shim_h2d(d_goff, goffs, sizeof(int64_t) * (size_t)nq, c->stream) || ssw_shim_launch_gather(&ga, c->stream) ||
-			    ssw_shim_d2h(pool.words + pool.n, d_gpool, sizeof(uint32_t) * (size_t)gwords, c->stream)) {
-				fail(c, "CIGAR download failed: %s", ssw_shim_last_error()); free(goffs); goto done;
-			}
-			}
-		}
-		for (int32_t q = 0; q < nq; ++q) {
-			const ssw_dres* r = &hres[q];
-			ssw_gpu_result* o = &results[(int64_t)q * tcount + ti];
-			if (qdone[q]) continue;
-			if (r->status >= 2) { fail(c, "internal error: window pass did not reproduce the forward score%s", ""); free(goffs); goto done; }
-			o->score1 = (uint16_t)r->score1; o->score2 = (uint16_t)r->score2;
-			o->ref_begin1 = r->ref_begin1; o->ref_end1 = r->ref_end1; o->read_begin1 = r->read_begin1; o->read_end1 = r->read_end1;
-			o->ref_end2 = r->ref_end2; o->cigarLen = r->cigarLen; o->cigar_off = -1; o->flag = (uint16_t)r->flag; o->status = (uint16_t)r->status;
-			o->edit_distance = r->nm;
-			if (r->score1 <= 0 && r->status == 0) { o->ref_begin1 = -1; o->read_begin1 = -1; }
-			if (r->cigarLen > 0 && r->status == 0) o->cigar_off = pool.n + goffs[q];
-			if (r->status == 0 && r->score1 > 0) { if (r->word) c->tm.n_word++; else c->tm.n_byte++; }
-			c->tm.cells += (Q->h_off[q + 1] - Q->h_off[q]) * (int64_t)refLen;
-		}
-		pool.n += gwords;
-		free(goffs);
+		int64_t gwords = 0;
+		if (cigars_to_stage(c, bc.hres, nq, bc.d_res, tro.d_cig, &bc.pool, bc.goffs, nq <= 4, &gwords)) goto done;
+		if (records_out(c, &bc, ti, refLen, results)) goto done;
+		bc.pool.n += gwords;
 		ssw_shim_event_record(c->ev_d, c->stream);
 		CALL_TRACE("results + CIGARs on the host");
 		if (ssw_shim_stream_sync(c->stream)) { fail(c, "stream sync failed: %s", ssw_shim_last_error()); goto done; }
-		for (int e = ev_first; e + 1 < c->nev; e += 2) fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
-		locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
-		trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
+		for (int e = ev_first; e + 1 < c->nev; e += 2) bc.fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
+		bc.locate_ms += ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+		bc.trace_ms += ssw_shim_event_elapsed_ms(c->ev_b, c->ev_c);
 	}
-	{
-		double total = ssw_shim_event_elapsed_ms(c->ev_t0, c->ev_d);
-		c->tm.total_ms = total; c->tm.fill_ms = fill_ms; c->tm.locate_ms = locate_ms; c->tm.trace_ms = trace_ms;
-		reduce_ms = total - fill_ms - locate_ms - trace_ms; if (reduce_ms < 0) reduce_ms = 0;
-		c->tm.reduce_ms = reduce_ms;   /* reduction + transfers: everything that is not one of the three timed phases */
-	}
-	if (cigar_pool) { *cigar_pool = pool.words; pool.words = 0; }
-	if (cigar_words) *cigar_words = pool.n;
+
+	/* ---- 6. totals */
+	batch_totals(c, &bc, cigar_pool, cigar_words);
 	rc = 0;
 done:
-	free(pool.words); free(order); free(pairs); free(hres); free(hneed); free(bk); free(qdone); free(bplans); free(border); free(defer); free(rdefer); free(hhdr);
+	/* a failed call may have launches queued on the side streams: nothing of it may still run when the caller frees or reuses the buffers
+	   (SSW_NOT_STREAMABLE is no failure: batch_try_db returns it before anything goes to a side stream, and the caller goes on) */
+	if (rc != 0 && rc != SSW_NOT_STREAMABLE) ctx_drain(c);
+	batch_call_free(&bc);
 	return rc;
 }
 

@@ -19,7 +19,7 @@ void* ssw_shim_stream_create(void) { return (void*)1; }
 void* ssw_shim_stream_create_low(void) { return (void*)1; }
 void ssw_shim_stream_destroy(void*) {}
 int ssw_shim_stream_sync(void*) { return 0; }
-/* SSW_EMU_MALLOC_LIMIT_MB=<n>: a single device allocation above n MiB fails (the out-of-memory path of the host driver: SSW_ALLOC_RETRY) */
+/* SSW_EMU_MALLOC_LIMIT_MB=<n>: a single device allocation above n MiB fails (the out-of-memory path of the host driver: plan_retreat) */
 void* ssw_shim_malloc(size_t bytes)
 {
 	const char* e = getenv("SSW_EMU_MALLOC_LIMIT_MB");

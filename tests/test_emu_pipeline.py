@@ -502,7 +502,7 @@ def test_long_reads_of_different_padded_lengths_share_a_launch(ectx):
 
 
 def test_allocation_failure_shrinks_the_budget_and_retries(emu_lib_path, monkeypatch):
-    """SSW_ALLOC_RETRY: a device allocation that fails although it is within the budget (contexts of one process sharing a device) cuts
+    """plan_retreat: a device allocation that fails although it is within the budget (contexts of one process sharing a device) cuts
     the budget and plans the launches again.  The emulator's allocator refuses single allocations above SSW_EMU_MALLOC_LIMIT_MB."""
     rng = np.random.default_rng(12)
     ref = random_ref(30000, 5, 4)
