@@ -262,5 +262,31 @@ SSW_DEV void xl_row_shr2_sub_keep(u32& dst, u32 v, u32 b)
 	asm("s_nop 4\n\tv_sub_u32_dpp %0, %1, %2 row_shr:2 row_mask:0xf bank_mask:0xf" : "+v"(dst) : "v"(v), "v"(b));
 }
 #endif
+/* row_shr:N with zero where the row has no lane N to the left (bound_ctrl: one instruction; the `keep` form needs a copy first) */
+#ifdef SSW_SIMT_EMU
+template <int N> SSW_DEV u32 xl_row_shr_zero(u32 v) { return xl_row_shr_keep<N>(0u, v); }
+#else
+template <int N> SSW_DEV u32 xl_row_shr_zero(u32 v) { return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x110 + N, 0xf, 0xf, true); }
+#endif
+/* a DPP move that lands only in the quads of a row named by BANK (bit q: lanes 4q .. 4q+3); the other lanes, and lanes whose source lies
+   outside the row, keep `old`.  CTRL: quad_perm (< 0x100), row_shl:n (0x100 + n), row_shr:n (0x110 + n), row_ror:n (0x120 + n).  Two of these
+   and one maximum fold TWO registers into one while halving the span each value is spread over (fill_flush8's group maxima). */
+#ifdef SSW_SIMT_EMU
+template <int CTRL, int BANK> SSW_DEV u32 xl_dpp_banks(u32 old, u32 v)
+{
+	const int l = emu::cur->lane, i = l & 15;
+	int src = i;
+	if (CTRL < 0x100) src = (i & ~3) | ((CTRL >> (2 * (i & 3))) & 3);
+	else if ((CTRL & 0x1f0) == 0x100) src = i + (CTRL & 15);
+	else if ((CTRL & 0x1f0) == 0x110) src = i - (CTRL & 15);
+	else src = (i - (CTRL & 15)) & 15;
+	const bool ok = src >= 0 && src < 16 && ((BANK >> (i >> 2)) & 1);
+	return emu::exchange(v, (l & ~15) | (src & 15), ok, old);
+}
+#else
+template <int CTRL, int BANK> SSW_DEV u32 xl_dpp_banks(u32 old, u32 v) { return (u32)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, 0xf, BANK, false); }
+#endif
+#define DPP_QUAD_SWAP1 0xB1      /* quad_perm:[1,0,3,2] */
+#define DPP_QUAD_SWAP2 0x4E      /* quad_perm:[2,3,0,1] */
 
 #endif /* SSW_LANES_H */

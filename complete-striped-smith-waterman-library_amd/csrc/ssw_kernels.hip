@@ -352,16 +352,66 @@ __global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(R <= 10 ? 7 : 1, 8) k_fi
  *     T(j) = max(T(j-1) - gapE, v(j-8) - gapO)
  *     M(j) = max(v(j) .. v(j-7), T(j))        maximum of column j over rows < P16  =  max(maximum over rows < P8, M(j))
  * (a value that enters a region of zero scores travels down-right for free for 7 more columns and can only go on through one horizontal
- * gap; vertical and second gaps never beat that when gapO > gapE -- the only regime of the frame form).  Position 7 parks v (true value)
- * beside the chain's maximum; the flush takes the 8-column window from the ring and scans T over the 16 columns of a group, carried
- * from group to group in LDS, from the chain's first traversal column on (inside the halo).
+ * gap; vertical and second gaps never beat that when gapO > gapE -- the only regime of the frame form).  Position 7 computes none of this:
+ * it parks what it has in registers anyway -- its running maximum, the open F that leaves its last row and the H of that row one column
+ * back, all raw frame values -- and the 16 lanes of the row turn the 16 steps of a trip into true values at the top of the next trip
+ * (fill_stage8: both chains from one phi); the flush takes the 8-column window from the v ring and scans T over the 16 columns of a group,
+ * carried from group to group in LDS, from the chain's first traversal column on (inside the halo).
  *
  * LDS map: the profile of k_fill with lane index chain * 8 + position (so the 16 lanes of a row read 16 different bank groups), then per
- * row of 16 lanes the target ring (160 B), per chain 64 x u32 finished maxima and 64 + 8 x u32 parked v (the first 8 mirrored behind the
- * ring), and one carry word per chain.
+ * row of 16 lanes
+ *     160 B          target ring
+ *     2 x 192 B      per chain what position 7 parked in the 16 steps of the last trip: 16 x maximum, 16 x open F, 16 x H of the last row
+ *                    as it stood BEFORE the step (the column before; renormalised in the register with everything else)
+ *     2 x 128 B      per chain 32 x u32 finished maxima, un-framed (written by the stage of steps s .. s+15, read by the flush of columns
+ *                    s-16 .. s-1 one trip later: 25 live slots)
+ *     2 x 288 B      per chain 64 + 8 x u32 v (the first 8 mirrored behind the ring: the flush reads 9 consecutive columns with immediates)
+ *     16 B           one carry word per chain
+ * (in this order every ring access of the stage and the flush is an immediate below 1 KiB on ONE base register, which is what a
+ * ds_read2_b32 can encode: no address arithmetic per access)
  * ================================================================================================ */
+#define CRING8_BYTES 128
 #define VRING8_BYTES 288      /* 64 + 8 mirrored entries: the flush reads 9 consecutive columns with immediates */
-#define CHAIN8_BYTES (RING_BYTES + 2 * 256 + 2 * VRING8_BYTES + 16)
+#define PARK8_BYTES 192
+#define CHAIN8_BYTES (RING_BYTES + 2 * CRING8_BYTES + 2 * VRING8_BYTES + 2 * PARK8_BYTES + 16)
+
+/* H and E of k_fill8 are no arrays but R scalars each: a nest of one-word structs taken apart by a constant index, and the rows of a step,
+   the initial state and the renormalisation are pack expansions over that index.  An array that is indexed inside loops the compiler first
+   turns into ONE vector value (R = 19: H, a tuple of 32 registers; E no longer fits the budget for this and stays scalar); it then builds
+   the next step's tuple beside the live one and copies all 32 registers at the back edge of the trip -- 16 v_mov_b64 of the 28 moves per
+   trip (docs/NOTEBOOK.md, "Half-row chains, second pass").  Structs are left alone and fall apart into their words. */
+template <int R> struct Rows8 { u32 v; Rows8<R - 1> up; };
+template <> struct Rows8<1> { u32 v; };
+template <int I, int R> SSW_DEV u32& row_at(Rows8<R>& a) { if constexpr (I == 0) return a.v; else return row_at<I - 1>(a.up); }
+template <int... I> struct RowSeq {};
+template <int N, int... I> struct RowSeqTo : RowSeqTo<N - 1, N - 1, I...> {};
+template <int... I> struct RowSeqTo<0, I...> { typedef RowSeq<I...> type; };
+template <int R, int... I> SSW_DEV void rows_set(Rows8<R>& a, u32 v, RowSeq<I...>) { ((row_at<I>(a) = v), ...); }
+template <int R, int... I> SSW_DEV void rows_sub(Rows8<R>& a, u32 k, RowSeq<I...>) { ((row_at<I>(a) -= k), ...); }
+
+/* row r of chain_rows_fr<R, 0, R, true>; x: diag + score, formed by the row above -- before that row's H was replaced, so that the old H[r]
+   dies one instruction before the new one is born and both can live in one register */
+template <int R, int r>
+SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& f, u32& cm, u32 c1, u32 gapE2, u32 fl)
+{
+	u32& Hr = row_at<r>(H); u32& Er = row_at<r>(E);
+	const u32 xn = r + 1 < R ? Hr + sc[(r + 1) >> 2][(r + 1) & 3] : 0u;
+	const u32 h = pk_max3_fr(x, Er, f);
+	const u32 t = h - c1;
+	Er = pk_max3_fr(Er, t, fl);
+	f = pk_max(f, t);
+	if (r != R - 1) f -= gapE2;      /* the last row leaves f OPEN */
+	if ((r & 1) == 1) cm = pk_max3_fr(cm, row_at<(r > 0 ? r - 1 : 0)>(H), h);
+	else if (r == R - 1) cm = pk_max(cm, h);
+	Hr = h;
+	x = xn;
+}
+template <int R, int... I>
+SSW_DEV void chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32& cm, u32 c1, u32 gapE2, u32 fl, RowSeq<I...>)
+{
+	u32 x = d + sc[0][0];
+	(chain_row8<R, I>(sc, H, E, x, f, cm, c1, gapE2, fl), ...);
+}
 
 /* profile of two pairs: word ((b*C + c)*16 + chain*8 + p)*4 + k = scores of residue b against rows p*R + 4c + k of pair `chain`.  All 8R rows
    are live (zero score below the read); a pair that does not exist gets dead rows: its chain stays at the floor */
@@ -388,46 +438,83 @@ SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const i
 	}
 }
 
-/* the 16 lanes of a row finish traversal columns [base, base + 16) of ONE of their two chains: the chain's own maximum (16-bit rule), the
-   closed form of the eight rows below it (8-bit rule), and the maxima over the group.  Every group is scanned, stored or not: T runs from the
-   chain's first column */
-SSW_DEV void fill_flush8(unsigned char* lds, u32 outc, u32 outv, u32 carry, int base, int l16, int store_from, int ncols, bool live,
-                         uint32_t* o16, uint32_t* o8, uint32_t* g16, uint32_t* g8, int fr_base, int fr_kmask, int gapE, int gapO)
+/* the 16 lanes of a row turn what position 7 of BOTH chains parked during the steps [s1, s1 + 16) into true values: the chain's maximum into
+   its ring, v(c) = max3(F, Hlast + 2 gapE, phi + gapE) - (phi + gapE) into the v ring (and its mirror).  One phi serves both: lane l takes
+   step s1 + l of either chain, and all 16 steps lie in one renormalisation period (Hlast was parked as the register stood, already
+   dropped with the rest).  Steps 0..6 are the null columns before the chain's first, where H sits at the floor and F below it: v = 0 */
+SSW_DEV void fill_stage8(unsigned char* lds, u32 rbl, int s1, bool low8, u32 lgd, int fr_base, int fr_kmask, int gapE, u32 gE2)
+{
+	/* phi(column + 1) of step s1 + l: the open F and Hlast + 2 gapE are one gapE above the column's frame.  s1 and the period are multiples
+	   of 16, so the lane's share l * gapE (lgd, packed) adds to a wavefront-uniform term */
+	const u32 ph = pk_dup(fr_base + ((s1 & fr_kmask) + 2) * gapE) + lgd;
+	const u32 sc = rbl + 2 * PARK8_BYTES + 4u * ((u32)s1 & 16u), sv = rbl + 2 * PARK8_BYTES + 2 * CRING8_BYTES + 4u * ((u32)s1 & 48u);
+	const bool mir = ((u32)s1 & 48u) == 0 && low8;
+#pragma unroll
+	for (u32 ch = 0; ch < 2; ++ch) {
+		const u32 p = rbl + ch * PARK8_BYTES;
+		const u32 cm = lds_ld32(lds, p), f = lds_ld32(lds, p + 64u), h = lds_ld32(lds, p + 128u);
+		const u32 vv = pk_max3_fr(f, h + 2u * gE2, ph) - ph;
+		lds_st32(lds, sc + ch * CRING8_BYTES, cm - (ph - gE2));
+		lds_st32(lds, sv + ch * VRING8_BYTES, vv);
+		if (mir) lds_st32(lds, sv + ch * VRING8_BYTES + 256u, vv);      /* slots 0..7 once more behind the ring */
+	}
+}
+
+/* the 16 lanes of a row finish traversal columns [base, base + 16) of their two chains: the chain's own maximum (16-bit rule), the closed
+   form of the eight rows below it (8-bit rule), and the maxima over the group.  Predicates, ring slots and store offsets are the same for
+   both chains (chain B's arrays lie cm_stride / seg_stride further on); the T scans are the chains' own.  Every group is scanned, stored
+   or not: T runs from the chain's first column */
+SSW_DEV void fill_flush8(unsigned char* lds, u32 rb, int base, int l16, int store_from, int ncols, bool live1,
+                         uint32_t* o16, uint32_t* o8, int64_t cm_stride, uint32_t* gq, int gapE, int gapO)
 {
 	const int tc = base + l16;
-	const bool in = live && tc >= store_from && tc < ncols;
-	/* column tc was finished by position 7 at step tc + 7; v is parked as a true value, the maximum in the frame of that step */
-	const u32 i8 = lds_ld32(lds, outc + 4u * ((u32)(tc + 7) & 63u)) - pk_dup(fr_phi(tc + 7, 7, 8, fr_base, fr_kmask, gapE));
-	/* v of columns tc - 8 .. tc: slots (tc - 1) & 63 and the eight behind it (mirrored past the end of the ring).  Columns before the chain's
-	   first one: position 7 spends steps 0..6 on the null columns the target ring starts with, where every row is dead -- H stays at the floor and
-	   F below it, so what it parks is v = 0; the slot of column -8 keeps the zero it was initialised with */
-	u32 v[9];
-	const u32 va = outv + 4u * ((u32)(tc - 1) & 63u);
-#pragma unroll
-	for (int k = 0; k < 9; ++k) v[k] = lds_ld32(lds, va + 4u * k);
-	u32 w = pk_max3_nonneg(v[1], v[2], v[3]);
-	w = pk_max3_nonneg(w, v[4], v[5]);
-	w = pk_max3_nonneg(w, v[6], v[7]);
-	w = pk_max(w, v[8]);
-	/* T in the group's own frame, T(base + l) + l * gapE, is a running maximum: a prefix scan over the row, lane 0 taking the previous
-	   group's last value (lane 15 presents it to row_ror:1) */
+	const bool in = tc >= store_from && tc < ncols;
+	/* column tc was finished by position 7 at step tc + 7: that is its slot in both rings.  v of columns tc - 8 .. tc: slot (tc - 1) & 63 and
+	   the eight behind it (mirrored past the end of the ring); the slot of column -8 keeps the zero it was initialised with */
+	const u32 ca = rb + 2 * PARK8_BYTES + 4u * ((u32)(tc + 7) & 31u), va = rb + 2 * PARK8_BYTES + 2 * CRING8_BYTES + 4u * ((u32)(tc - 1) & 63u);
+	const u32 carry = rb + 2 * PARK8_BYTES + 2 * CRING8_BYTES + 2 * VRING8_BYTES;
 	const int lg = l16 * gapE;
-	u32 x = pk_adds(v[0], pk_dup(lg - gapO));
-	const u32 y = l16 == 15 ? lds_ld32(lds, carry) : x;
-	x = pk_max(x, xl_row_ror<1>(y));
-	x = pk_max(x, xl_row_shr_keep<2>(x, x));
-	x = pk_max(x, xl_row_shr_keep<4>(x, x));
-	x = pk_max(x, xl_row_shr_keep<8>(x, x));
-	if (l16 == 15) lds_st32(lds, carry, pk_adds(x, pk_dup(-16 * gapE)));
-	const u32 i16 = pk_max(pk_max(w, i8), pk_adds(x, pk_dup(-lg)));
-	if (in) { o16[tc] = i16; o8[tc] = i8; }
-	if (g16) {
-		u32 m16 = in ? i16 : 0u, m8 = in ? i8 : 0u;
-		m16 = pk_max(m16, xl_row_ror<1>(m16)); m8 = pk_max(m8, xl_row_ror<1>(m8));
-		m16 = pk_max(m16, xl_row_ror<2>(m16)); m8 = pk_max(m8, xl_row_ror<2>(m8));
-		m16 = pk_max(m16, xl_row_ror<4>(m16)); m8 = pk_max(m8, xl_row_ror<4>(m8));
-		m16 = pk_max(m16, xl_row_ror<8>(m16)); m8 = pk_max(m8, xl_row_ror<8>(m8));
-		if (live && l16 == 0 && base >= store_from && base < ncols) { g16[base >> 4] = m16; g8[base >> 4] = m8; }
+	const u32 up = pk_dup(lg), dn = pk_dup(-lg - gapO);
+	u32 i16[2], i8[2];
+#pragma unroll
+	for (u32 ch = 0; ch < 2; ++ch) {
+		i8[ch] = lds_ld32(lds, ca + ch * CRING8_BYTES);
+		u32 v[9];
+#pragma unroll
+		for (int k = 0; k < 9; ++k) v[k] = lds_ld32(lds, va + ch * VRING8_BYTES + 4u * k);
+		u32 w = pk_max3_nonneg(v[1], v[2], v[3]);
+		w = pk_max3_nonneg(w, v[4], v[5]);
+		w = pk_max3_nonneg(w, v[6], v[7]);
+		w = pk_max3_nonneg(w, v[8], i8[ch]);
+		/* T in the group's own frame and one gapO up, T(base + l) + l * gapE + gapO, is a running maximum of non-negative terms
+		   v(c - 8) + l * gapE: a prefix scan over the row in which the zero that row_shr fills in is neutral, lane 0 taking the previous
+		   group's last value (lane 15 presents it to row_ror:1; that one may have sunk below zero) */
+		u32 x = v[0] + up;
+		const u32 y = l16 == 15 ? lds_ld32(lds, carry + 4u * ch) : x;
+		x = pk_max(x, xl_row_ror<1>(y));
+		x = pk_max(x, xl_row_shr_zero<2>(x));
+		x = pk_max(x, xl_row_shr_zero<4>(x));
+		x = pk_max(x, xl_row_shr_zero<8>(x));
+		if (l16 == 15) lds_st32(lds, carry + 4u * ch, pk_adds(x, pk_dup(-16 * gapE)));
+		i16[ch] = pk_max(w, pk_adds(x, dn));
+	}
+	if (in) {
+		o16[tc] = i16[0]; o8[tc] = i8[0];
+		if (live1) { o16[cm_stride + tc] = i16[1]; o8[cm_stride + tc] = i8[1]; }
+	}
+	if (gq) {
+		/* four group maxima (2 chains x 2 rules) in 13 instructions: each fold puts two registers into one and halves the span of a value --
+		   A | B on the halves of a row, then 16-bit | 8-bit rule on the quads of a half -- and two quad swaps finish all four at once.  Quad q
+		   ends up with chain q >> 1, rule q & 1, and its first lane stores it (gq: that lane's array) */
+		u32 m[4];
+#pragma unroll
+		for (int k = 0; k < 4; ++k) m[k] = in ? (k & 1 ? i8[k >> 1] : i16[k >> 1]) : 0u;
+		const u32 x16 = pk_max(xl_dpp_banks<0x128, 0xc>(m[0], m[2]), xl_dpp_banks<0x128, 0x3>(m[2], m[0]));
+		const u32 x8 = pk_max(xl_dpp_banks<0x128, 0xc>(m[1], m[3]), xl_dpp_banks<0x128, 0x3>(m[3], m[1]));
+		u32 y = pk_max(xl_dpp_banks<0x114, 0xa>(x16, x8), xl_dpp_banks<0x104, 0x5>(x8, x16));
+		y = pk_max(y, xl_dpp_banks<DPP_QUAD_SWAP1, 0xf>(y, y));
+		y = pk_max(y, xl_dpp_banks<DPP_QUAD_SWAP2, 0xf>(y, y));
+		if ((l16 & 3) == 0 && (live1 || l16 < 8) && base >= store_from && base < ncols) gq[base >> 4] = y;
 	}
 }
 
@@ -441,7 +528,10 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	const bool live1 = 2 * pg + 1 < a.npairs;
 	const int gapEi = (int)(a.gapE2 & 0xffffu), gapOi = (int)(a.gapO2 & 0xffffu);
 	const u32 prof_bytes = (u32)(a.n + 1) * G::PSTRIDE;
-	const u32 ring = prof_bytes + (u32)grp * CHAIN8_BYTES, outc = ring + RING_BYTES, outv = outc + 512, carry = outv + 2 * VRING8_BYTES;      /* (chain 1: + 256 / + VRING8_BYTES / + 4) */
+	const u32 ring = prof_bytes + (u32)grp * CHAIN8_BYTES;
+	/* what follows the target ring on ONE base register (opaque: the compiler otherwise folds the constants apart again and rebuilds a base for
+	   every pair of accesses).  Chain 1: + PARK8_BYTES / + CRING8_BYTES / + VRING8_BYTES / + 4 */
+	const u32 rb = opaque(ring + RING_BYTES), outv = rb + 2 * PARK8_BYTES + 2 * CRING8_BYTES, carry = outv + 2 * VRING8_BYTES;
 	const u32 nulloff = (u32)a.n * G::PSTRIDE;
 
 	{   /* score profiles of the two pairs, shared by the 16 rows of the workgroup */
@@ -470,10 +560,10 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	uint32_t* o16 = a.cm16 + (int64_t)(2 * pg) * a.cm_stride + c_first;      /* (pair 2 pg + 1: + cm_stride / + seg_stride) */
 	uint32_t* o8 = a.cm8 + (int64_t)(2 * pg) * a.cm_stride + c_first;
 	const int store_from = tile_lo - c_first;
-	uint32_t* g16 = a.sg16 ? a.sg16 + (int64_t)(2 * pg) * a.seg_stride + (c_first >> 4) : (uint32_t*)0;
-	uint32_t* g8 = a.sg16 ? a.sg8 + (int64_t)(2 * pg) * a.seg_stride + (c_first >> 4) : (uint32_t*)0;
+	/* the group maxima come out of the flush one per quad of the row -- chain l16 >> 3, rule (l16 >> 2) & 1 -- and this is the quad's array */
+	uint32_t* gq = a.sg16 ? (l16 & 4 ? a.sg8 : a.sg16) + (int64_t)(2 * pg + (l16 >> 3)) * a.seg_stride + (c_first >> 4) : (uint32_t*)0;
 
-	/* target ring as in k_fill; the parked v of the columns before the first are zero, T starts below every score */
+	/* target ring as in k_fill; v of the columns before the first is zero, T starts below every score */
 	lds_st16(lds, ring + 2u * (48 + l16), nulloff);
 	{
 		int code = l16 < ncols ? tg[l16] : a.n;
@@ -484,7 +574,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	}
 #pragma unroll
 	for (int k = 0; k < 9; ++k) lds_st32(lds, outv + 4u * (u32)(l16 + 16 * k), 0u);      /* (both chains' rings: 144 words) */
-	if (l16 < 2) lds_st32(lds, carry + 4u * l16, pk_dup(-gapOi));
+	if (l16 < 2) lds_st32(lds, carry + 4u * l16, 0u);      /* T = -gapO, held one gapO up (fill_flush8) */
 	u32 nxt;
 	{
 		const int tc = 16 + l16;
@@ -496,21 +586,22 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 
 	const u32 zero0 = pk_dup(fr_phi(0, pos, 8, a.fr_base, a.fr_kmask, gapEi) - gapEi);
 	u32 fl = zero0 + a.gapE2;
-	u32 H[R], E[R];
-#pragma unroll
-	for (int r = 0; r < R; ++r) { H[r] = zero0; E[r] = fl; }
+	typedef typename RowSeqTo<R>::type Rows;
+	Rows8<R> H, E;
+	rows_set(H, zero0, Rows()); rows_set(E, fl, Rows());
 	u32 Hlast = zero0, Fout = zero0 + a.gapE2, cmout = zero0, hsave = zero0;
 	const u32 lane_prof = (u32)(ch * 8 + pos) * 16u;
-	const u32 gO = a.gapO2 - a.gapE2, gE = a.gapE2, gE2 = 2u * a.gapE2;
+	const u32 gO = a.gapO2 - a.gapE2, gE = a.gapE2;
 	const u32 gEv = opaque(gE);
 	u32 fin = 0;
-	const u32 park = outc + (u32)ch * 256u, parkv = outv + (u32)ch * VRING8_BYTES;      /* position 7 of each chain parks what it finishes */
+	const u32 park = rb + (u32)ch * PARK8_BYTES, rbl = opaque(rb + 4u * (u32)l16);      /* position 7 of each chain parks, every lane of the row reads one step back */
+	const u32 lgd = pk_dup(l16 * gapEi);
+	const bool low8 = l16 < 8;
 
 	for (int s0 = 0; s0 < nsteps; s0 += 16) {
 		if (s0 > 0 && (s0 & a.fr_kmask) == 0) {
 			const u32 k = (u32)(a.fr_kmask + 1) * a.gapE2;
-#pragma unroll
-			for (int r = 0; r < R; ++r) { H[r] -= k; E[r] -= k; }
+			rows_sub(H, k, Rows()); rows_sub(E, k, Rows());
 			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl -= k;
 		}
 		{   /* stage target columns [s0+16, s0+32), prefetch [s0+32, s0+48) */
@@ -522,45 +613,35 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 			if (code < 0 || code > a.n) code = a.n;
 			nxt = (u32)code * G::PSTRIDE;
 		}
-		wave_lds_fence();
-		if (s0 >= 32) {   /* columns [s0-32, s0-16) are complete in the rings, and so are the eight before them */
-			fill_flush8(lds, outc, outv, carry, s0 - 32, l16, store_from, ncols, true, o16, o8, g16, g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
-			fill_flush8(lds, outc + 256, outv + VRING8_BYTES, carry + 4, s0 - 32, l16, store_from, ncols, live1, o16 + a.cm_stride, o8 + a.cm_stride,
-			            g16 ? g16 + a.seg_stride : g16, g16 ? g8 + a.seg_stride : g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
-		}
-		wave_lds_fence();
+		wave_lds_fence();      /* what position 7 parked in the last 16 steps is visible to the row */
+		if (s0 >= 16) fill_stage8(lds, rbl, s0 - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE);
+		wave_lds_fence();      /* one fence for both chains: the rings are complete up to step s0 - 1 */
+		if (s0 >= 32)          /* columns [s0-32, s0-16) are complete in the rings, and so are the eight before them */
+			fill_flush8(lds, rb, s0 - 32, l16, store_from, ncols, live1, o16, o8, a.cm_stride, gq, gapEi, gapOi);
 		const u32 rp = ring + 2u * (u32)((s0 - pos) & 63);
-		const u32 ob = park + 4u * (u32)(s0 & 63), obv = parkv + 4u * (u32)(s0 & 63);
-		const bool lap = (s0 & 63) == 0;
 #pragma unroll
 		for (int j = 0; j < 16; ++j) {
 			const u32 paddr = lds_ld16(lds, rp + 2u * j) + lane_prof;
 			u32x4 sc[C];
 #pragma unroll
 			for (int c = 0; c < C; ++c) sc[c] = lds_ld128(lds, paddr + 256u * c);
-			const u32 hp = Hlast + gE2;                           /* H of the chain's last row one column back, two columns' frames ahead */
+			const u32 hprev = Hlast;                              /* H of the chain's last row one column back */
 			const u32 hin = xl_row_shr2_umax(Hlast, fl); fl += gE;
 			xl_row_shr2_sub_keep(fin, Fout, gEv);
 			u32 f = fin, d = hsave;
 			u32 cm = xl_row_shr2_zero(cmout);
-			chain_rows_fr<R, 0, R, true>(sc, H, E, d, f, cm, gO, gE, fl);
-			hsave = hin; Hlast = H[R - 1]; Fout = f; cmout = cm;
-			/* what enters the row below the chain, as a true value: max(0, Htop(c-1), Ftop(c)) -- all three one gapE above the column's frame (f is OPEN) */
-			const u32 vv = pk_max3_fr(f, hp, fl) - fl;
-			if (pos == 7) {
-				lds_st32(lds, ob + 4u * j, cm); lds_st32(lds, obv + 4u * j, vv);
-				if (j < 8 && lap) lds_st32(lds, obv + 256u + 4u * j, vv);      /* slots 0..7 once more behind the ring */
+			chain_rows_fr8(sc, H, E, d, f, cm, gO, gE, fl, Rows());
+			hsave = hin; Hlast = row_at<R - 1>(H); Fout = f; cmout = cm;
+			if (pos == 7) {      /* raw: the frame of this step (hprev: one gapE below it) */
+				lds_st32(lds, park + 4u * j, cm); lds_st32(lds, park + 64u + 4u * j, f); lds_st32(lds, park + 128u + 4u * j, hprev);
 			}
 		}
 	}
 	wave_lds_fence();
+	fill_stage8(lds, rbl, nsteps - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE);
+	wave_lds_fence();
 	for (int base = nsteps - 32; base < nsteps; base += 16)
-		if (base >= 0) {
-			fill_flush8(lds, outc, outv, carry, base, l16, store_from, ncols, true, o16, o8, g16, g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
-			fill_flush8(lds, outc + 256, outv + VRING8_BYTES, carry + 4, base, l16, store_from, ncols, live1, o16 + a.cm_stride, o8 + a.cm_stride,
-			            g16 ? g16 + a.seg_stride : g16, g16 ? g8 + a.seg_stride : g8, a.fr_base, a.fr_kmask, gapEi, gapOi);
-			wave_lds_fence();
-		}
+		if (base >= 0) fill_flush8(lds, rb, base, l16, store_from, ncols, live1, o16, o8, a.cm_stride, gq, gapEi, gapOi);
 }
 
 /* register budget per class as for k_fill: up to 9 rows per position 72 registers, up to 15 96, beyond that 128.  (R8 = 19 held to 96
