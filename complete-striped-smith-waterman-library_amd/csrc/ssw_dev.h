@@ -212,6 +212,14 @@ typedef struct {
 	ssw_vmap vm;
 } ssw_capture_args;
 
+/* explicit pair lists (ssw_gpu_align_pairs): one job of k_fillpairs, or of the strip kernel's pair mode, = up to two (query, target) pairs,
+   the low and the high 16-bit half of every register.  k_fillpairs: both queries have the same row class R = ceil(len / 16); strip kernel:
+   the same bucket (win_bucket_key: jobs of several strips pair queries of one padded length) */
+typedef struct {
+	int32_t qa, qb;          /* query of the low / high half; qb = -1: the high half is idle */
+	int32_t ta, tb;          /* target of the low / high half (tb = ta when qb = -1); windows of the window table when the launch has one */
+} ssw_pjob;
+
 /*
  * generic chain kernel (k_chainx): one 16-lane chain per job with its OWN profile; queries of any length are cut
  * into row strips of 16R rows that the chain processes one after the other, handing the bottom boundary
@@ -261,7 +269,28 @@ typedef struct {
 	ssw_vmap vm;             /* capture mode only */
 	int32_t banded;          /* capture mode, k_chainq, capped reverse pass: strips walk a diagonal band of the window (accepted only with cap_half_finish's proof) */
 	int32_t tail_R;          /* fill mode, k_chainq: > 0: the LAST of the `strips` strips has tail_R (1, 2 or 4) rows per lane instead of R (all jobs of the launch have the same padded length) */
+	const ssw_pjob* pjobs;   /* pair mode of the fill (k_chainq, ssw_shim_launch_chainq with mode 2): njobs jobs, one tile each, no halo; their targets / windows
+	                            through vm.tcodes / vm.toff / vm.win; column maxima [job][cm_stride], best cells to cand[job][half][4] */
 } ssw_chainx_args;
+
+/* pair mode of the strip kernel: the column maxima of its jobs -> final records (k_reduce_pairs, one workgroup per job).  Half h of job j
+   is read up to its OWN column count; records as k_fillpairs writes them */
+typedef struct {
+	const ssw_pjob* jobs;
+	int32_t njobs;
+	const int64_t* qoff;
+	const int64_t* toff;     /* target offsets ... */
+	const ssw_win* win;      /* ... or the window table that ta / tb index */
+	const uint32_t* cm16;    /* [njobs][cm_stride] */
+	const uint32_t* cm8;
+	int64_t cm_stride;
+	const int32_t* cand;     /* [job][half][4]: best cell tracked by the fill = value, column, row, - */
+	int32_t maskLen, bias, score_size;
+	struct ssw_out_rec* out; /* [2 * njobs]: low half of job j at 2j, high half at 2j + 1 */
+	int32_t* counters;       /* optional: [0] alignments decided under 16-bit rules, [1] under 8-bit rules */
+	int32_t mark_word;       /* records decided under 16-bit rules carry SSW_OUT_WORD in their status */
+	int32_t* err;            /* error word of the call (as ssw_chainx_args.err): raised when the tracked best cell is not the first column of the maximum */
+} ssw_reduce_pairs_args;
 
 /*
  * literal lane model (k_literal): for gap penalties with gapO <= gapE the reference's answer depends on its striped
@@ -341,13 +370,6 @@ typedef struct {
 	uint32_t* dst;
 	int32_t nq;
 } ssw_gather_args;
-
-/* explicit pair lists (ssw_gpu_align_pairs): one job of k_fillpairs = up to two (query, target) pairs, the low and the high 16-bit half of
-   every register; both queries have the same row class R = ceil(len / 16) */
-typedef struct {
-	int32_t qa, qb;          /* query of the low / high half; qb = -1: the high half is idle */
-	int32_t ta, tb;          /* target of the low / high half (tb = ta when qb = -1); windows of ssw_fillpairs_args.win when that is set */
-} ssw_pjob;
 
 typedef struct {
 	const int8_t* qcodes;
@@ -484,7 +506,8 @@ int ssw_shim_launch_reducem(const ssw_reducem_args* a, int64_t total_pairs, void
 int ssw_shim_launch_capture(int R, const ssw_capture_args* a, void* stream);
 int64_t ssw_shim_capture_lds_need(int R, int n);   /* dynamic LDS of one k_capture<R> workgroup */
 int ssw_shim_launch_chainx(int R, int capture, const ssw_chainx_args* a, void* stream);
-int ssw_shim_launch_chainq(int R, int capture, const ssw_chainx_args* a, int max_workgroups, void* stream);   /* 64-lane chains behind a work queue */
+int ssw_shim_launch_chainq(int R, int capture, const ssw_chainx_args* a, int max_workgroups, void* stream);   /* 64-lane chains behind a work queue; capture 0: fill, 1: window pass, 2: pair mode of the fill */
+int ssw_shim_launch_reduce_pairs(const ssw_reduce_pairs_args* a, void* stream);
 int ssw_shim_chainq_resident(int R, int capture, int n);   /* wavefronts of k_chainq<R> the device holds at once (0: unknown) */
 int ssw_shim_launch_literal(const ssw_literal_args* a, void* stream);
 int ssw_shim_launch_trace(const ssw_trace_args* a, void* stream);

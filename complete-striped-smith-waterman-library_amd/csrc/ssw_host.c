@@ -768,7 +768,8 @@ static void note_fill_kernel(ssw_gpu_ctx* c, int64_t cells, int64_t* best_cells,
 }
 
 /* the error word of this call's work-queue launches: a strip that waited for the one above it for 30 seconds gave up (never seen; it
-   would mean a broken queue) and raised it -- checked once, before results are handed out.  One word per call, apart from the queue
+   would mean a broken queue) and raised it, or -- pair mode -- k_reduce_pairs found a job whose tracked best cell is not the first column
+   of its maximum (never seen either: one tile, no halo) -- checked once, before results are handed out.  One word per call, apart from the queue
    buffers: those are reused (and zeroed) from launch to launch without a host round trip. */
 static int chainq_check(ssw_gpu_ctx* c)
 {
@@ -777,7 +778,8 @@ static int chainq_check(ssw_gpu_ctx* c)
 	c->queue_used = 0;
 	if (ssw_shim_d2h(&e, c->qerr.p, sizeof e, c->stream) || ssw_shim_stream_sync(c->stream)) return fail(c, "download failed: %s", ssw_shim_last_error());
 	if (ssw_shim_memset(c->qerr.p, 0, sizeof e, c->stream)) return fail(c, "memset failed: %s", ssw_shim_last_error());
-	return e ? fail(c, "internal error: a strip of the work queue timed out waiting for the strip above it%s", "") : 0;
+	return e ? fail(c, "internal error in the strip kernel's work queue: a strip timed out waiting for the strip above it, or a job's best cell "
+	                   "disagrees with its column maxima%s", "") : 0;
 }
 
 /* work-queue launches of the 64-lane strip kernel (k_chainq): zeroed ticket counter + completion flags (q: items + 2 ints), one best-cell
@@ -2757,8 +2759,11 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
  *   database search's gates): k_fillpairs, jobs of two pairs that share the row class R = ceil(len / 16), one chain per job,
  *   final records in one launch per R (and per chunk of the scratch budget).  Planning is a counting sort by (R, target-length
  *   class): O(npairs), no comparison sort.
- *   flag != 0: the pairs that pass the score gate then go through one batched reverse pass and traceback (pairs_flagged);
- *   everything else (empty sequences, longer sequences, gapO <= gapE, wide alphabets, large scores): one internal
+ *   long class (gapO > gapE, n <= 32, queries 769..65535 residues, targets 1..65000 columns, a job's scratch within half the budget;
+ *   no max(mat) gate): the strip kernel's pair mode, k_chainq<R,pairs,form> behind its work queue + k_reduce_pairs, one series of
+ *   launches per bucket of win_bucket_key; its jobs continue the numbering of k_fillpairs' jobs, records in the same arrays.
+ *   flag != 0: the pairs of both classes that pass the score gate then go through one batched reverse pass and traceback (pairs_flagged);
+ *   everything else (empty sequences, queries of 641..768 residues, longer targets, gapO <= gapE, wide alphabets, large scores): one internal
  *   batch per distinct target over the subset of its queries, gathered into a temporary set on the device (k_seqgather) --
  *   exact, and slow: a batch call per target.
  * ------------------------------------------------------------------------------------------------ */
@@ -2770,6 +2775,32 @@ static inline int64_t ps_tlen(const pair_src* s, const ssw_gpu_seqs* T, int64_t 
 static inline int32_t ps_tid(const pair_src* s, int64_t i) { return s->tbeg ? (int32_t)i : s->tidx[i]; }
 
 #define PJ_TCLS 2048      /* target-length classes of the planner: 32 columns each (65000 columns: 2031 classes) */
+#define PJ_KEY_FALLBACK 0xffffffffu
+#define PJ_KEY_LONG 0xfffffffeu      /* the strip kernel's pair mode (queries of 769 residues and more) */
+#define PJ_LONG_MIN 769
+#define PJ_LONG_MAX 65535
+
+/* a pair of the long class on its way into jobs: sorted by bucket key, then query length, then target length (the two halves of a job and
+   the jobs of a launch finish together), then position */
+typedef struct { int32_t key, len; int64_t tl, i; } plong;
+static int plong_cmp(const void* a, const void* b)
+{
+	const plong* x = (const plong*)a; const plong* y = (const plong*)b;
+	if (x->key != y->key) return x->key < y->key ? -1 : 1;
+	if (x->len != y->len) return x->len < y->len ? -1 : 1;
+	if (x->tl != y->tl) return x->tl < y->tl ? -1 : 1;
+	return x->i < y->i ? -1 : x->i > y->i;
+}
+/* jobs [j0, j0 + jn) of the long class share the strip shape b; maxt: their longest target */
+typedef struct { bucket b; int64_t j0, jn, maxt; } plong_bucket;
+/* scratch of ONE job of the pair mode against a target of tl columns: two rows of column maxima, the boundary records of the strip
+   hand-off, queue flag + best-cell record per strip, the job's best cells and its two records */
+static int64_t plong_cm_stride(int64_t tl) { return (tl + 15) / 16 * 16 + 16; }
+static int64_t plong_bnd_cols(int64_t tl) { return (tl + 31) / 16 * 16; }
+static int64_t plong_job_bytes(int64_t tl, int32_t strips)
+{
+	return 8 * plong_cm_stride(tl) + 16 * plong_bnd_cols(tl) + 36 * (int64_t)strips + 32 + 2 * (int64_t)sizeof(ssw_gpu_result);
+}
 
 static double wall_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
@@ -2854,15 +2885,20 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
                          int32_t maxmat, int32_t minmat, cigar_stage* st)
 {
 	win_geom geom;
-	win_geom_fill(&geom, &c->kn, prm->n);      /* (queries here are <= 640 residues) */
-	enum { NKEY = SSW_RMAX + 64 + 41 };        /* bucket keys of queries up to 640 residues: win_bucket_key */
-	int64_t kfirst[NKEY + 1]; int32_t kp16[NKEY];
-	memset(kfirst, 0, sizeof kfirst); memset(kp16, 0, sizeof kp16);
+	win_geom_fill(&geom, &c->kn, prm->n);
+	/* bucket keys (win_bucket_key): up to SSW_RMAX + 64 + 41 for queries of the short class (<= 640 residues), SSW_RMAX + 64 + P16 / 16 for the
+	   strip kernel's pair mode -- the key arrays are sized from the longest query of the list */
+	int32_t maxq = 0;
+	for (int64_t k = 0; k < nrec; ++k) { const int64_t i = pix[k]; const int32_t len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]); if (len > maxq) maxq = len; }
+	const int NKEY = SSW_RMAX + 64 + (maxq + 15) / 16 + 1;
+	int64_t* kfirst = (int64_t*)calloc((size_t)NKEY + 1, sizeof(int64_t));
+	int64_t* kpos = (int64_t*)malloc(sizeof(int64_t) * (size_t)NKEY);
+	int32_t* kp16 = (int32_t*)calloc((size_t)NKEY, sizeof(int32_t));
 	int32_t* key = (int32_t*)malloc(sizeof(int32_t) * (size_t)(nrec > 0 ? nrec : 1));
 	int64_t* order = (int64_t*)malloc(sizeof(int64_t) * (size_t)(nrec > 0 ? nrec : 1));
 	ssw_dres* hs = 0; int32_t* hvq = 0; int64_t* poff = 0; surv_range* rg = 0;
 	int rc = -1;
-	if (!key || !order) { fail(c, "out of host memory%s", ""); goto out; }
+	if (!kfirst || !kpos || !kp16 || !key || !order) { fail(c, "out of host memory%s", ""); goto out; }
 	int64_t ns = 0; int32_t maxlen = 0; int64_t maxt = 0;
 	for (int64_t k = 0; k < nrec; ++k) {
 		ssw_gpu_result* o = &rec[k];
@@ -2885,11 +2921,8 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 	if (ns == 0) { rc = 0; goto out; }
 	if (ns > 0x7fffff00) { fail(c, "%s: more than 2^31 flagged pairs in one call", src->who); goto out; }
 	for (int b = 0; b < NKEY; ++b) kfirst[b + 1] += kfirst[b];
-	{
-		int64_t pos[NKEY];
-		memcpy(pos, kfirst, sizeof pos);
-		for (int64_t k = 0; k < nrec; ++k) if (key[k] >= 0) order[pos[key[k] & 0xffff]++] = k;
-	}
+	memcpy(kpos, kfirst, sizeof(int64_t) * (size_t)NKEY);
+	for (int64_t k = 0; k < nrec; ++k) if (key[k] >= 0) order[kpos[key[k] & 0xffff]++] = k;
 	hs = (ssw_dres*)malloc(sizeof(ssw_dres) * (size_t)ns); hvq = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)ns);
 	if (!hs || !hvq) { fail(c, "out of host memory%s", ""); goto out; }
 	for (int64_t v = 0; v < ns; ++v) {
@@ -2908,7 +2941,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 	if (ssw_shim_h2d(d_sres, hs, sizeof(ssw_dres) * (size_t)ns, c->stream) || ssw_shim_h2d(d_maps, hvq, sizeof(int32_t) * 3 * (size_t)ns, c->stream)) {
 		fail(c, "upload failed: %s", ssw_shim_last_error()); goto out;
 	}
-	poff = (int64_t*)malloc(sizeof(int64_t) * (size_t)ns); rg = (surv_range*)malloc(sizeof(surv_range) * NKEY);
+	poff = (int64_t*)malloc(sizeof(int64_t) * (size_t)ns); rg = (surv_range*)malloc(sizeof(surv_range) * (size_t)NKEY);
 	if (!poff || !rg) { fail(c, "out of host memory%s", ""); goto out; }
 	int nrg = 0;
 	for (int kk = 0; kk < NKEY; ++kk) {
@@ -2931,7 +2964,7 @@ static int pairs_flagged(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_se
 	}
 	rc = 0;
 out:
-	free(key); free(order); free(hs); free(hvq); free(poff); free(rg);
+	free(kfirst); free(kpos); free(kp16); free(key); free(order); free(hs); free(hvq); free(poff); free(rg);
 	return rc;
 }
 
@@ -2987,6 +3020,10 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	/* (flagged pairs: the window kernels reach a job's target through a 64-bit base and keep their column indices relative to it, so the size
 	   of the resident set does not matter -- unlike the flagged database search's survivors) */
 	const int kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db;
+	/* the strip kernel's pair mode (k_chainq<R,pairs,..>): no max(mat) gate -- ssw_frame_params picks the form per bucket */
+	win_geom geom;
+	win_geom_fill(&geom, &c->kn, n);
+	const int long_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && !c->kn.no_db && geom.xlanes == 64 && geom.xrmax <= 16;
 
 	/* ---- plan: counting sort of the kernel's pairs by (R, target-length class); the rest to the fallback list */
 	const int64_t nkeys = (int64_t)40 * PJ_TCLS;
@@ -2994,6 +3031,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	uint32_t* key = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)np);
 	int64_t* perm = (int64_t*)malloc(sizeof(int64_t) * (size_t)np);
 	int64_t* fb = 0; int64_t nfb = 0;
+	plong* lk = 0; plong_bucket* lb = 0; int64_t nlong = 0; int nlb = 0;
 	ssw_pjob* jobs = 0; int64_t* jix = 0; ssw_gpu_result* stage = 0;
 	ssw_gpu_result* fbrec = 0; int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0;      /* select mode */
 	unsigned char* d_brec = 0; int8_t* d_mat = 0; int64_t nj = 0;
@@ -3005,7 +3043,14 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	for (int64_t i = 0; i < np; ++i) {
 		const int64_t ql = Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]], tl = ps_tlen(src, T, i);
 		const int R = (int)((ql + 15) / 16);
-		if (!kern_ok || ql < 1 || ql > 640 || tl < 1 || tl > 65000 || (int64_t)n * ((R + 3) / 4) * 256 > 65535) { key[i] = 0xffffffffu; ++nfb; continue; }
+		if (long_ok && ql >= PJ_LONG_MIN && ql <= PJ_LONG_MAX && tl >= 1 && tl <= 65000) {
+			/* (queries of 641 .. 768 residues: neither class, the fallback) */
+			int32_t P16q; bucket B;
+			const int32_t kk = win_bucket_key(&geom, (int32_t)ql, &P16q);
+			win_bucket_shape(&B, &geom, kk, P16q);
+			if (plong_job_bytes(tl, B.strips) <= (int64_t)(c->cm_budget / 2)) { key[i] = PJ_KEY_LONG; ++nlong; continue; }
+		}
+		if (!kern_ok || ql < 1 || ql > 640 || tl < 1 || tl > 65000 || (int64_t)n * ((R + 3) / 4) * 256 > 65535) { key[i] = PJ_KEY_FALLBACK; ++nfb; continue; }
 		key[i] = (uint32_t)((R - 1) * PJ_TCLS + (tl >> 5 < PJ_TCLS ? tl >> 5 : PJ_TCLS - 1));
 		kcount[key[i] + 1]++;
 	}
@@ -3014,7 +3059,22 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	if (nfb > 0) { fb = (int64_t*)malloc(sizeof(int64_t) * (size_t)nfb); if (!fb) { fail(c, "out of host memory%s", ""); goto done; } }
 	{
 		int64_t f = 0;
-		for (int64_t i = 0; i < np; ++i) { if (key[i] == 0xffffffffu) fb[f++] = i; else perm[kcount[key[i]]++] = i; }      /* kcount[k] ends as the end of class k */
+		for (int64_t i = 0; i < np; ++i) {
+			if (key[i] == PJ_KEY_FALLBACK) fb[f++] = i;
+			else if (key[i] != PJ_KEY_LONG) perm[kcount[key[i]]++] = i;      /* kcount[k] ends as the end of class k */
+		}
+	}
+	if (nlong > 0) {
+		lk = (plong*)malloc(sizeof(plong) * (size_t)nlong); lb = (plong_bucket*)malloc(sizeof(plong_bucket) * (size_t)nlong);
+		if (!lk || !lb) { fail(c, "out of host memory%s", ""); goto done; }
+		int64_t f = 0;
+		for (int64_t i = 0; i < np; ++i) {
+			if (key[i] != PJ_KEY_LONG) continue;
+			int32_t P16q;
+			lk[f].len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]); lk[f].key = win_bucket_key(&geom, lk[f].len, &P16q);
+			lk[f].tl = ps_tlen(src, T, i); lk[f].i = i; ++f;
+		}
+		qsort(lk, (size_t)nlong, sizeof(plong), plong_cmp);
 	}
 
 	if (bm && nfb > 0) {      /* select mode: what the candidates outside the envelope score, before the device holds anything of this call */
@@ -3024,9 +3084,9 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, &st, &acc)) goto done;
 		memset(&c->tm, 0, sizeof c->tm);
 	}
-	if (nk > 0) {
+	if (nk + nlong > 0) {
 		/* jobs: neighbours of one R (sorted by target length: the two halves and the chains of a workgroup finish together) */
-		const int64_t njmax = nk / 2 + 40;
+		const int64_t njmax = nk / 2 + 40 + nlong;
 		jobs = (ssw_pjob*)malloc(sizeof(ssw_pjob) * (size_t)njmax);
 		jix = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)njmax);
 		if (!jobs || !jix) { fail(c, "out of host memory%s", ""); goto done; }
@@ -3047,6 +3107,26 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			}
 		}
 		rfirst[40] = nj;
+		/* ... then the long class in the same numbering: neighbours of one bucket (win_bucket_key: jobs of several strips pair queries of ONE
+		   padded length; a query without a partner runs with an idle high half) */
+		for (int64_t k = 0; k < nlong; ) {
+			int64_t k1 = k; int32_t p16 = 0;
+			plong_bucket* L = &lb[nlb++];
+			memset(L, 0, sizeof *L);
+			L->j0 = nj;
+			while (k1 < nlong && lk[k1].key == lk[k].key) { const int32_t P = (lk[k1].len + 15) / 16 * 16; if (P > p16) p16 = P; if (lk[k1].tl > L->maxt) L->maxt = lk[k1].tl; ++k1; }
+			win_bucket_shape(&L->b, &geom, lk[k].key, p16);
+			for (; k < k1; k += 2) {
+				const int64_t pa = lk[k].i, pb = k + 1 < k1 ? lk[k + 1].i : -1;
+				ssw_pjob* j = &jobs[nj];
+				j->qa = qidx[pa]; j->ta = ps_tid(src, pa);
+				j->qb = pb >= 0 ? qidx[pb] : -1; j->tb = ps_tid(src, pb >= 0 ? pb : pa);
+				jix[2 * nj] = pa; jix[2 * nj + 1] = pb;
+				++nj;
+			}
+			k = k1;
+			L->jn = nj - L->j0;
+		}
 		/* the call's small inputs: matrix + jobs in one upload */
 		const size_t hdr_mat = ((size_t)n * n + 15) / 16 * 16;
 		unsigned char* d_hdr = (unsigned char*)ensure(c, &c->pairs, hdr_mat + sizeof(ssw_pjob) * (size_t)nj);
@@ -3122,9 +3202,67 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			snprintf(nm, sizeof nm, "k_fillpairs<%d,%s>", R, fr ? "frame" : "int16+max3");
 			note_fill_kernel(c, rcells, &kbest, nm, fr ? 7.5 : 9.5, R, 1);
 		}
+		/* ---- the long class: per bucket, launches of the strip kernel's pair mode behind its work queue, each followed by k_reduce_pairs
+		   (records as k_fillpairs leaves them, two per job, into the same arrays) */
+		for (int b = 0; b < nlb; ++b) {
+			const plong_bucket* L = &lb[b]; const bucket* B = &L->b;
+			const int64_t stride = plong_cm_stride(L->maxt), bcols = plong_bnd_cols(L->maxt);
+			int64_t jpl = (int64_t)(c->cm_budget / 2) / plong_job_bytes(L->maxt, B->strips);      /* (>= 1: every pair passed the planner's gate with its own target) */
+			if (jpl < 1) jpl = 1;
+			if (jpl > L->jn) jpl = L->jn;
+			if (jpl * B->strips > 0x7ffffff0 / 2) jpl = 0x7ffffff0 / 2 / B->strips;
+			uint32_t* d_cm16 = (uint32_t*)ensure(c, &c->cm16, (size_t)(4 * stride * jpl));
+			uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
+			uint32_t* d_bnd = (uint32_t*)ensure(c, &c->bnd, (size_t)(16 * bcols * jpl));
+			int32_t* d_cand = (int32_t*)ensure(c, &c->cand, (size_t)(32 * jpl));
+			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
+			if (!d_cm16 || !d_cm8 || !d_bnd || !d_cand || !d_out) goto done;
+			int32_t fr_base = 0, fr_kmask = 0;
+			const int xform = !c->kn.fill_plain && ssw_frame_params(&c->kn, (int64_t)B->P16 * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 64, &fr_base, &fr_kmask) ? 3 : 0;
+			/* wavefronts of the launch: the occupancy of the WINDOW pass of this R, which has the pair mode's LDS footprint (two target rings) but
+			   fewer registers -- where registers bound the pair mode (R = 4, frame form: 3 per SIMD against 4) some wavefronts of the grid start
+			   when others end.  Harmless: tickets are drawn in dependency order, a waiting strip's predecessor was drawn by a wavefront that runs. */
+			const int qgrid = chainq_grid(c, B->R, 1, n);
+			const int64_t rows = (int64_t)64 * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips);
+			int64_t bcells = 0;
+			for (int64_t a0 = 0; a0 < L->jn; a0 += jpl) {
+				const int64_t nl = L->jn - a0 < jpl ? L->jn - a0 : jpl;
+				ssw_chainx_args xa; memset(&xa, 0, sizeof xa);
+				xa.qcodes = Q->d_codes; xa.qoff = Q->d_off; xa.mat = d_mat; xa.n = n; xa.gapO2 = gapO2; xa.gapE2 = gapE2; xa.gapE = prm->gapE; xa.maxmat = maxmat;
+				xa.njobs = (int32_t)nl; xa.pjobs = d_jobs + L->j0 + a0; xa.vm.tcodes = T->d_codes; xa.vm.toff = T->d_off; xa.vm.win = src->d_win;
+				xa.ntiles = 1; xa.cm16 = d_cm16; xa.cm8 = d_cm8; xa.cm_stride = stride; xa.bnd = d_bnd; xa.bnd_stride = bcols; xa.cand = d_cand; xa.lanes = 64;
+				if (chainq_prepare(c, &xa, B->strips, nl, qgrid)) goto done;
+				xa.form = xform; xa.fr_base = fr_base; xa.fr_kmask = fr_kmask; xa.tail_R = B->tailR;
+				if (c->kn.debug) fprintf(stderr, "[ssw_gpu] chainq pair fill: R %d (last strip %d), %lld jobs x %d strips, %d wavefronts, %s tickets, form %d\n",
+				                                     B->R, B->tailR ? B->tailR : B->R, (long long)nl, B->strips, qgrid, xa.whole_jobs ? "job" : "strip", xa.form);
+				void* e0 = next_event(c); void* e1 = next_event(c);
+				ssw_shim_event_record(e0, c->stream);
+				if (ssw_shim_launch_chainq(B->R, 2, &xa, qgrid, c->stream)) { fail(c, "fill launch failed: %s", ssw_shim_last_error()); goto done; }
+				ssw_shim_event_record(e1, c->stream);
+				ssw_reduce_pairs_args ra; memset(&ra, 0, sizeof ra);
+				ra.jobs = xa.pjobs; ra.njobs = xa.njobs; ra.qoff = Q->d_off; ra.toff = T->d_off; ra.win = src->d_win; ra.cm16 = d_cm16; ra.cm8 = d_cm8; ra.cm_stride = stride;
+				ra.cand = d_cand; ra.maskLen = prm->maskLen; ra.bias = bias; ra.score_size = prm->score_size;
+				ra.out = bm ? d_out + 2 * (L->j0 + a0) : d_out; ra.counters = d_cnt; ra.mark_word = prm->flag != 0; ra.err = xa.err;
+				if (ssw_shim_launch_reduce_pairs(&ra, c->stream)) { fail(c, "reduce launch failed: %s", ssw_shim_last_error()); goto done; }
+				/* same stream: the next launch of the loop reuses the scratch only after this download */
+				if (!bm && ssw_shim_d2h(stage + 2 * (L->j0 + a0), d_out, sizeof(struct ssw_out_rec) * 2 * (size_t)nl, c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+				c->tm.fill_launches++;
+				for (int64_t j = L->j0 + a0; j < L->j0 + a0 + nl; ++j) {
+					const int64_t La = ps_tlen(src, T, jix[2 * j]), Lb = jix[2 * j + 1] >= 0 ? ps_tlen(src, T, jix[2 * j + 1]) : 0;
+					bcells += rows * 2 * (La > Lb ? La : Lb);
+				}
+			}
+			kcells += bcells;
+			char nm[48];      /* (R <= 16, strips <= 256, tail <= 4: at most 46 characters; snprintf cuts anything longer) */
+			const int nlen = B->tailR ? snprintf(nm, sizeof nm, "k_chainq<%d,pairs,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR)
+			                          : snprintf(nm, sizeof nm, "k_chainq<%d,pairs,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
+			if (nlen >= (int)sizeof nm && c->kn.debug) fprintf(stderr, "[ssw_gpu] fill kernel name cut to %d characters\n", (int)sizeof nm - 1);
+			note_fill_kernel(c, bcells, &kbest, nm, xform == 3 ? 6.5 : 9.0, B->R, B->strips);
+		}
 		int32_t cnt[DB_COUNTERS] = { 0, 0, 0, 0 };
 		ssw_shim_event_record(c->ev_d, c->stream);
 		if (ssw_shim_d2h(cnt, d_cnt, sizeof cnt, c->stream) || ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+		if (chainq_check(c)) goto done;      /* (the long class: a strip that gave up waiting, or a best cell that is not the maximum's first column) */
 		for (int e = 0; e + 1 < c->nev; e += 2) c->tm.fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
 		c->tm.fill_cells = kcells; c->tm.n_word = cnt[0]; c->tm.n_byte = cnt[1];      /* (the reduction is fused into the fill: reduce_ms stays 0) */
 		if (!bm) {
@@ -3173,7 +3311,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			for (int64_t g = 0; g < ng; ++g) {
 				if (bm->sel[g].best < 0) continue;
 				const int64_t i = bm->cand_off[g] + bm->sel[g].best;
-				if (key[i] == 0xffffffffu) { ++nfw; wlist[ng - nfw] = i; wg[ng - nfw] = g; }
+				if (key[i] == PJ_KEY_FALLBACK) { ++nfw; wlist[ng - nfw] = i; wg[ng - nfw] = g; }
 				else { wlist[nin] = i; wg[nin] = g; wrec[nin] = results[g]; ++nin; }
 			}
 			if (nin > 0 && pairs_flagged(c, Q, T, qidx, src, wlist, wrec, nin, prm, d_mat, maxmat, minmat, &st)) goto done;
@@ -3204,11 +3342,12 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	}
 	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
 		const int64_t i = perm[k]; acc.t.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
+	for (int64_t k = 0; k < nlong; ++k) acc.t.cells += (int64_t)lk[k].len * lk[k].tl;
 	acc.t.total_ms = wall_ms() - t_start;
 	c->tm = acc.t;
 	rc = 0;
 done:
-	free(kcount); free(key); free(perm); free(fb); free(jobs); free(jix); free(stage); free(st.words);
+	free(kcount); free(key); free(perm); free(fb); free(lk); free(lb); free(jobs); free(jix); free(stage); free(st.words);
 	free(fbrec); free(slot); free(wlist); free(wrec);
 	return rc;
 }

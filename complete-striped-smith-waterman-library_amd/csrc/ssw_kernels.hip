@@ -1103,6 +1103,44 @@ SSW_DEV void pj_rows(const unsigned char* lds, u32 pa_next, u32 pb_next, u32x4 (
 	}
 }
 
+/* What the reference's rules make of one half's best score bv (first column bc) against its nc columns (src/ssw.c:881-899, 376 / 578): the
+   8-bit versus 16-bit decision, status 1 where it returns NULL, and the columns [lo_edge, up_from) masked out of the second best */
+struct PairRules { int word, status, maskLen, lo_edge, up_from; bool use8; };
+SSW_DEV PairRules pj_rules(int len, int nc, int bv, int bc, int maskLen_arg, int bias, int score_size)
+{
+	PairRules r;
+	const bool padded = (len & 15) >= 1 && (len & 15) <= 8;
+	r.maskLen = maskLen_arg >= 0 ? maskLen_arg : len / 2;
+	const bool have_byte = score_size == 0 || score_size == 2, have_word = score_size == 1 || score_size == 2;
+	r.word = 0; r.status = 0;
+	if (have_byte && bv < 255 - bias) r.word = 0;
+	else if (have_word) r.word = 1;
+	else r.status = 1;
+	r.use8 = r.word && padded;
+	r.lo_edge = 0; r.up_from = 0;
+	if (r.status == 0 && bv > 0) {
+		r.lo_edge = bc - r.maskLen > 0 ? bc - r.maskLen : 0;
+		const int hi_edge = bc + r.maskLen > nc ? nc : bc + r.maskLen;
+		r.up_from = r.word ? hi_edge : hi_edge + 1;
+	}
+	return r;
+}
+/* the final record of one half (one thread): best cell (bv, bc, br), second best (s2, i2) */
+SSW_DEV void pj_emit(ssw_out_rec* out, int32_t* counters, int mark_word, int status, int word, int bv, int bc, int br, int len, int maskLen, int s2, int i2)
+{
+	ssw_out_rec o;
+	o.score1 = 0; o.score2 = 0; o.ref_begin1 = -1; o.ref_end1 = 0; o.read_begin1 = -1; o.read_end1 = 0; o.ref_end2 = 0;
+	o.cigarLen = 0; o.edit_distance = 0; o.cigar_off = -1; o.flag = 0;
+	o.status = (uint16_t)(status | (mark_word && word && status == 0 && bv > 0 ? SSW_OUT_WORD : 0));
+	if (status == 0 && bv > 0) {
+		o.score1 = (uint16_t)bv; o.ref_end1 = bc; o.read_end1 = br < len - 1 ? br : len - 1;
+		if (maskLen >= 15) { o.score2 = (uint16_t)s2; o.ref_end2 = s2 > 0 ? i2 : 0; }
+		else { o.score2 = 0; o.ref_end2 = -1; }
+	}
+	*out = o;
+	if (counters && status == 0 && bv > 0) atomicAdd(counters + (word ? 0 : 1), 1);
+}
+
 /* start (in tcodes) and column count of target / window t of a k_fillpairs launch */
 SSW_DEV int64_t pj_tstart(const ssw_fillpairs_args& a, int t) { return a.win ? a.win[t].start : a.toff[t]; }
 SSW_DEV int pj_tcols(const ssw_fillpairs_args& a, int t) { return a.win ? a.win[t].len : (int)(a.toff[t + 1] - a.toff[t]); }
@@ -1301,19 +1339,11 @@ SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
 			if (v > bv || (v == bv && v > 0 && cc < bc)) { bv = v; bc = cc; br = w; }
 		}
 		wave_lds_fence();
-		const bool padded = (len & 15) >= 1 && (len & 15) <= 8;
-		const int maskLen = a.maskLen >= 0 ? a.maskLen : len / 2;
-		const bool have_byte = a.score_size == 0 || a.score_size == 2, have_word = a.score_size == 1 || a.score_size == 2;
-		int word = 0, status = 0;
-		if (have_byte && bv < 255 - a.bias) word = 0;
-		else if (have_word) word = 1;
-		else status = 1;
+		const PairRules pr = pj_rules(len, nc, bv, bc, a.maskLen, a.bias, a.score_size);
+		const int word = pr.word, status = pr.status, maskLen = pr.maskLen, lo_edge = pr.lo_edge, up_from = pr.up_from;
 		int s2 = 0, i2 = 0x7fffffff;
 		if (status == 0 && bv > 0) {
-			const uint32_t* arr = (word && padded) ? o8 : o16;
-			const int lo_edge = bc - maskLen > 0 ? bc - maskLen : 0;
-			const int hi_edge = bc + maskLen > nc ? nc : bc + maskLen;
-			const int up_from = word ? hi_edge : hi_edge + 1;
+			const uint32_t* arr = pr.use8 ? o8 : o16;
 			for (int c = l16; c < nc; c += 16) {
 				if (c < lo_edge || c >= up_from) {
 					const int v = (int)((arr[c] >> (16 * h)) & 0xffffu);
@@ -1329,17 +1359,7 @@ SSW_DEV void fillpairs_pass(const ssw_fillpairs_args& a, unsigned char* lds)
 				const int v = (int)lds_ld32(lds, red + 16u * k), cc = (int)lds_ld32(lds, red + 16u * k + 4);
 				if (v > s2 || (v == s2 && cc < i2)) { s2 = v; i2 = cc; }
 			}
-			ssw_out_rec o;
-			o.score1 = 0; o.score2 = 0; o.ref_begin1 = -1; o.ref_end1 = 0; o.read_begin1 = -1; o.read_end1 = 0; o.ref_end2 = 0;
-			o.cigarLen = 0; o.edit_distance = 0; o.cigar_off = -1; o.flag = 0;
-			o.status = (uint16_t)(status | (a.mark_word && word && status == 0 && bv > 0 ? SSW_OUT_WORD : 0));
-			if (status == 0 && bv > 0) {
-				o.score1 = (uint16_t)bv; o.ref_end1 = bc; o.read_end1 = br < len - 1 ? br : len - 1;
-				if (maskLen >= 15) { o.score2 = (uint16_t)s2; o.ref_end2 = s2 > 0 ? i2 : 0; }
-				else { o.score2 = 0; o.ref_end2 = -1; }
-			}
-			a.out[2 * job + h] = o;
-			if (a.counters && status == 0 && bv > 0) atomicAdd(a.counters + (word ? 0 : 1), 1);
+			pj_emit(a.out + 2 * job + h, a.counters, a.mark_word, status, word, bv, bc, br, len, maskLen, s2, i2);
 		}
 		wave_lds_fence();
 	}
@@ -1614,6 +1634,40 @@ __global__ void __launch_bounds__(256) k_reducem(ssw_reducem_args m)
 	reduce_seg_body(a, (int)blockIdx.x - m.first_wg[s], lds);
 }
 
+/* k_reduce_pairs: the column maxima of the strip kernel's pair mode -> final records, one workgroup per job.  Half h is scanned over
+   the columns of its OWN target or window only (beyond them the array holds the partner's columns and decayed values of its own);
+   rules and record as at the end of k_fillpairs (pj_rules / pj_emit), the row of the best cell from the fill's tracking. */
+__global__ void __launch_bounds__(256) k_reduce_pairs(ssw_reduce_pairs_args a)
+{
+	SSW_DYN_LDS(lds);
+	const int tid = (int)threadIdx.x, job = (int)blockIdx.x;
+	const ssw_pjob jb = a.jobs[job];
+	const uint32_t* c16 = a.cm16 + (int64_t)job * a.cm_stride;
+	const uint32_t* c8 = a.cm8 + (int64_t)job * a.cm_stride;
+	for (int h = 0; h < 2; ++h) {
+		const int q = h ? jb.qb : jb.qa, t = h ? jb.tb : jb.ta;
+		if (q < 0) continue;      /* uniform in the workgroup */
+		const int len = (int)(a.qoff[q + 1] - a.qoff[q]);
+		const int nc = a.win ? a.win[t].len : (int)(a.toff[t + 1] - a.toff[t]);
+		int bv = 0, bc = 0x7fffffff;
+		for (int c = tid; c < nc; c += 256) { const int v = half16(c16[c], h); if (v > bv) { bv = v; bc = c; } }
+		block_argmax(lds, tid, bv, bc);
+		const PairRules pr = pj_rules(len, nc, bv, bc, a.maskLen, a.bias, a.score_size);
+		int s2 = 0, i2 = 0x7fffffff;
+		if (pr.status == 0 && bv > 0) {
+			const uint32_t* arr = pr.use8 ? c8 : c16;
+			for (int c = tid; c < nc; c += 256)
+				if (c < pr.lo_edge || c >= pr.up_from) { const int v = half16(arr[c], h); if (v > s2) { s2 = v; i2 = c; } }
+		}
+		block_argmax(lds, tid, s2, i2);
+		if (tid == 0) {
+			const int32_t* cd = a.cand + ((int64_t)job * 2 + h) * 4;
+			if (bv > 0 && (cd[0] != bv || cd[1] != bc)) atomicAdd(a.err, 1);      /* one tile, no halo: the tracked cell IS the first column of the maximum */
+			pj_emit(a.out + 2 * (int64_t)job + h, a.counters, a.mark_word, pr.status, pr.word, bv, bc, cd[2], len, pr.maskLen, s2, i2);
+		}
+	}
+}
+
 /* ================================================================================================
  * k_capture: one chain per alignment; tracks the best cell (value, first column, smallest row) of a
  * window.  reverse == 0: columns [ref_end1 - halo, ref_end1] forward -> read_end1.
@@ -1849,14 +1903,14 @@ template <int PS> SSW_DEV u32 strip_code_off(const StripCtx& x, int h, int tc, b
    in).  Only the lane whose OWN rows beat that -- the lane holding the new record cell, not every lane below it -- records: value,
    column, smallest row.  (Columns outside the target only decay; the test on tc keeps the hand-written contract explicit.  The
    branch-free form of k_filldb's db_record, one v_bfi per row, measured 13 ms slower on config 4's fill.) */
-template <int R>
+template <int R, bool PAIRS = false>
 SSW_DEV void strip_record(u32 now, u32 pre, int tc, const StripCtx& x, const u32 (&H)[R], int (&sv)[2], int (&stc)[2], int (&srow)[2], int phi = 0)
 {
 	if (now != pre && x.mine && tc >= 0 && tc < x.ncols) {
 #pragma unroll
 		for (int h = 0; h < 2; ++h) {
 			const int nv = (int)((now >> (16 * h)) & 0xffffu), ov = (int)((pre >> (16 * h)) & 0xffffu);
-			if (nv > ov) {
+			if (nv > ov && (!PAIRS || tc < x.ncols2[h])) {      /* (pair mode: a half only records inside its OWN target) */
 				sv[h] = nv - phi; stc[h] = tc; srow[h] = 0x7fffffff;      /* (frame form: now / pre / H carry + phi of that column) */
 #pragma unroll
 				for (int k = R - 1; k >= 0; --k) if ((int)((H[k] >> (16 * h)) & 0xffffu) == nv) srow[h] = x.row0 + x.l16 * R + k;
@@ -1881,11 +1935,15 @@ SSW_DEV void strip_group_max(const u32x4& rec, bool valid, int base, const Strip
 /* FR (fill mode only): column-frame form of the recurrence (chain_rows_fr).  Boundary records travel between strips as TRUE values:
    the staging lanes add phi of the column when a record enters the boundary-in ring (lane 0 meets column tc at step tc) and
    subtract the parking lane's when it leaves the boundary-out ring (lane GL-1 finishes column tc at step tc + GL - 1). */
-template <int R, bool CAPTURE, bool MASK8, int GL, bool CM3 = false, bool FR = false>
+/* PAIRS (fill mode only): every query half runs against its OWN target -- the two target rings of capture mode (x.tg2 / x.ncols2, per-half
+   profile entries), the recurrence, boundary hand-off and column maxima of the fill.  x.ncols is the larger of the two column counts;
+   past its own count a half reads the null code, and k_reduce_pairs reads each half's maxima up to its own count only. */
+template <int R, bool CAPTURE, bool MASK8, int GL, bool CM3 = false, bool FR = false, bool PAIRS = false>
 SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st, const u32 (&m8)[R])
 {
 	typedef StripGeom<R, GL> G;
 	constexpr int C = G::C, RB = G::RB;
+	constexpr bool TWO = CAPTURE || PAIRS;      /* one target ring per query half */
 	const int l16 = x.l16;             /* lane within the chain (0..GL-1) */
 	const bool stg = l16 < 16;         /* the 16 lanes that stage the rings and flush the boundary records */
 	const u32 fr_c1 = x.gapO2 - x.gapE2;
@@ -1899,14 +1957,14 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 	};
 	/* rings: target columns -GL..-1 null, 0..15 now, 16..31 in flight; boundary-in likewise */
 	lds_st16(lds, x.ring + 2u * (RB - GL + l16), x.nulloff);
-	if (CAPTURE) lds_st16(lds, x.ringb + 2u * (RB - GL + l16), x.nulloff);
+	if (TWO) lds_st16(lds, x.ringb + 2u * (RB - GL + l16), x.nulloff);
 	u32 nxt = 0, nxtb = 0;
 	if (stg) {
-		const u32 off = strip_code_off<G::PSTRIDE>(x, 0, l16, CAPTURE);
+		const u32 off = strip_code_off<G::PSTRIDE>(x, 0, l16, TWO);
 		lds_st16(lds, x.ring + 2u * l16, off);
 		lds_st16(lds, x.ring + 2u * (RB + l16), off);
-		nxt = strip_code_off<G::PSTRIDE>(x, 0, 16 + l16, CAPTURE);
-		if (CAPTURE) {
+		nxt = strip_code_off<G::PSTRIDE>(x, 0, 16 + l16, TWO);
+		if (TWO) {
 			const u32 offb = strip_code_off<G::PSTRIDE>(x, 1, l16, true);
 			lds_st16(lds, x.ringb + 2u * l16, offb);
 			lds_st16(lds, x.ringb + 2u * (RB + l16), offb);
@@ -1945,7 +2003,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 		const u32 pa0 = lds_ld16(lds, x.ring + r0) + lane_prof;
 #pragma unroll
 		for (int c = 0; c < C; ++c) sc_n[c] = lds_ld128(lds, pa0 + G::CSTRIDE * c);
-		if (CAPTURE) {
+		if (TWO) {
 			const u32 pb0 = lds_ld16(lds, x.ringb + r0) + lane_prof;
 #pragma unroll
 			for (int c = 0; c < C; ++c) sb_n[c] = lds_ld128(lds, pb0 + G::CSTRIDE * c);
@@ -1966,14 +2024,14 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 			const int p = (s0 + 16 + l16) & (RB - 1);
 			lds_st16(lds, x.ring + 2u * p, nxt);
 			if (p < 32) lds_st16(lds, x.ring + 2u * (RB + p), nxt);
-			if (CAPTURE) {
+			if (TWO) {
 				lds_st16(lds, x.ringb + 2u * p, nxtb);
 				if (p < 32) lds_st16(lds, x.ringb + 2u * (RB + p), nxtb);
 			}
 			lds_st128(lds, x.bin + 16u * (p & 63), nb);
 			const int tc = s0 + 32 + l16;
-			nxt = strip_code_off<G::PSTRIDE>(x, 0, tc, CAPTURE);
-			if (CAPTURE) nxtb = strip_code_off<G::PSTRIDE>(x, 1, tc, true);
+			nxt = strip_code_off<G::PSTRIDE>(x, 0, tc, TWO);
+			if (TWO) nxtb = strip_code_off<G::PSTRIDE>(x, 1, tc, true);
 			nb = zero4;
 			if (take && tc < x.bnd_avail) nb = *(const u32x4*)(x.bnd + 4 * (int64_t)tc);
 			nb = bnd_in(nb, tc);
@@ -2001,7 +2059,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 			u32x4 sc[C];
 #pragma unroll
 			for (int c = 0; c < C; ++c) sc[c] = sc_n[c];
-			if (CAPTURE) {   /* the upper query half looks at its own target column */
+			if (TWO) {   /* the upper query half looks at its own target column */
 #pragma unroll
 				for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -2012,11 +2070,11 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 			/* (the ring entries of step s+2 are requested FIRST: asked for after the score chunks, hipcc gave them a register of the last
 			   chunk's unused rows -- R = 10 uses 10 of 12 -- and had to wait for every load in flight before it could issue them) */
 			const u32 pa_next = lds_ld16(lds, x.ring + rpo + 2u * (j + 2));
-			const u32 pb_next = CAPTURE ? lds_ld16(lds, x.ringb + rpo + 2u * (j + 2)) : 0u;
+			const u32 pb_next = TWO ? lds_ld16(lds, x.ringb + rpo + 2u * (j + 2)) : 0u;
 #pragma unroll
 			for (int c = 0; c + 1 < C; ++c) sc_n[c] = lds_ld128(lds, pa_n + G::CSTRIDE * c);
 			sc_n[C - 1] = lds_ld_rows<R - 4 * (C - 1)>(lds, pa_n + G::CSTRIDE * (C - 1));      /* the last chunk: only the rows that exist */
-			if (CAPTURE) {
+			if (TWO) {
 #pragma unroll
 				for (int c = 0; c + 1 < C; ++c) sb_n[c] = lds_ld128(lds, pb_n + G::CSTRIDE * c);
 				sb_n[C - 1] = lds_ld_rows<R - 4 * (C - 1)>(lds, pb_n + G::CSTRIDE * (C - 1));
@@ -2034,7 +2092,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 			   the next column run: the compare that feeds it is a whole step old by then, while at the end of its own step the scalar
 			   unit would wait for the vector compare every time (config 4's fill: 1602 -> 1546 ms).  H still holds that column.
 			   (k_filldb, where the branch is taken in most steps, got slower with the same change.) */
-			if (!CAPTURE && pend != 0ull) strip_record<R>(sbest, prep, tc - 1, x, st.H, sv, stc, srow, FR ? (int)((fl - x.gapE2) & 0xffffu) : 0);
+			if (!CAPTURE && pend != 0ull) strip_record<R, PAIRS>(sbest, prep, tc - 1, x, st.H, sv, stc, srow, FR ? (int)((fl - x.gapE2) & 0xffffu) : 0);
 			if (FR) { fl += x.gapE2; sbest += x.gapE2; }      /* the lane's record follows the frame of its column */
 			const u32 pre = pk_max(sbest, cm);   /* fill: the lane's running record and this column's rows above */
 #pragma unroll
@@ -2043,7 +2101,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 				const u32 sv = sc[r >> 2][r & 3];
 				u32 h;
 				if (FR) {
-					h = pk_max3_fr(CAPTURE ? pk_addw(d, sv) : d + sv, st.E[r], f);
+					h = pk_max3_fr(TWO ? pk_addw(d, sv) : d + sv, st.E[r], f);
 					const u32 t = h - fr_c1;
 					st.E[r] = pk_max3_fr(st.E[r], t, fl);
 					f = pk_max(f, t) - x.gapE2;
@@ -2096,7 +2154,7 @@ SSW_DEV void run_strip(unsigned char* lds, const StripCtx& x, ChainState<R>& st,
 			}
 		}
 	}
-	if (!CAPTURE && pend != 0ull) strip_record<R>(sbest, prep, x.nsteps - 1 - l16, x, st.H, sv, stc, srow, FR ? (int)((fl - x.gapE2) & 0xffffu) : 0);
+	if (!CAPTURE && pend != 0ull) strip_record<R, PAIRS>(sbest, prep, x.nsteps - 1 - l16, x, st.H, sv, stc, srow, FR ? (int)((fl - x.gapE2) & 0xffffu) : 0);
 	wave_lds_fence();
 	for (int base = x.nsteps - GL - 16; base < x.nsteps - GL + 16; base += 16) {
 		const int tc = base + l16;
@@ -2344,17 +2402,21 @@ template <int R, bool CAPTURE> struct QueueGeom {
 	static constexpr u32 EXTRA = (CAPTURE ? 2u : 1u) * RINGB + BND_RING_BYTES + BOUT;   /* the 768-byte reduction scratch aliases the boundary-in ring */
 };
 
-template <int R, bool CAPTURE, int FORM>
+/* PAIRS (fill mode): a job is an ssw_pjob -- up to two (query, target) pairs, one per 16-bit half, each half against its own target or
+   window (a.vm.tcodes / toff / win, as k_fillpairs reaches them): one tile per job, no halo, two target rings.  The queue, the strip
+   hand-off, the tail strip and the best-cell records are the fill mode's; k_reduce_pairs turns the column maxima into records. */
+template <int R, bool CAPTURE, int FORM, bool PAIRS = false>
 __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 {
 	constexpr int GL = 64;
+	constexpr bool TWO = CAPTURE || PAIRS;
 	typedef StripGeom<R, GL> G;
-	typedef QueueGeom<R, CAPTURE> QG;
+	typedef QueueGeom<R, TWO> QG;
 	SSW_DYN_LDS(lds);
 	const int tid = (int)threadIdx.x, l16 = tid;
 	const u32 prof_bytes = (u32)(a.n + 1) * G::PSTRIDE;
 	StripCtx x;
-	x.prof = 0; x.ring = prof_bytes; x.ringb = x.ring + (CAPTURE ? QG::RINGB : 0u); x.bin = x.ringb + QG::RINGB;
+	x.prof = 0; x.ring = prof_bytes; x.ringb = x.ring + (TWO ? QG::RINGB : 0u); x.bin = x.ringb + QG::RINGB;
 	x.bout = x.bin + BND_RING_BYTES; x.nulloff = (u32)a.n * G::PSTRIDE; x.bmask = 31u;
 	const u32 red = x.bin;
 	x.l16 = l16; x.gapO2 = a.gapO2; x.gapE2 = a.gapE2; x.n = a.n; x.tg = a.tgt;
@@ -2386,7 +2448,23 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 			if (!a.whole_jobs && tid == 0 && !dev_flag_wait(flags + (int64_t)job * S + sidx - 1)) atomicAdd(a.err, 1);   /* error word: the host fails the call */
 			dev_fence();
 		}
-		if (!CAPTURE) {
+		if (PAIRS) {
+			const ssw_pjob jb = a.pjobs[job];
+			qa = a.qcodes + a.qoff[jb.qa]; lena = (int)(a.qoff[jb.qa + 1] - a.qoff[jb.qa]);
+			if (jb.qb >= 0) { qb = a.qcodes + a.qoff[jb.qb]; lenb = (int)(a.qoff[jb.qb + 1] - a.qoff[jb.qb]); }
+			rows_total = ((lena > lenb ? lena : lenb) + 15) & ~15;
+			rowsa = (lena + 15) & ~15; rowsb = qb ? (lenb + 15) & ~15 : rows_total;
+			p8a = (lena + 7) & ~7; p8b = qb ? (lenb + 7) & ~7 : rows_total;
+			x.tg2[0] = a.vm.tcodes + (a.vm.win ? a.vm.win[jb.ta].start : a.vm.toff[jb.ta]);
+			x.ncols2[0] = a.vm.win ? a.vm.win[jb.ta].len : (int)(a.vm.toff[jb.ta + 1] - a.vm.toff[jb.ta]);
+			if (jb.qb >= 0) {
+				x.tg2[1] = a.vm.tcodes + (a.vm.win ? a.vm.win[jb.tb].start : a.vm.toff[jb.tb]);
+				x.ncols2[1] = a.vm.win ? a.vm.win[jb.tb].len : (int)(a.vm.toff[jb.tb + 1] - a.vm.toff[jb.tb]);
+			} else x.tg2[1] = x.tg2[0];      /* idle high half: no columns, every code the null code */
+			x.ncols = x.ncols2[0] > x.ncols2[1] ? x.ncols2[0] : x.ncols2[1];
+			x.o16 = a.cm16 + (int64_t)job * a.cm_stride; x.o8 = a.cm8 + (int64_t)job * a.cm_stride;
+			active = true;
+		} else if (!CAPTURE) {
 			const int pair = job / a.ntiles, t = job - pair * a.ntiles;
 			const ssw_pair pr = a.pairs[pair];
 			qa = a.qcodes + a.qoff[pr.qa]; lena = (int)(a.qoff[pr.qa + 1] - a.qoff[pr.qa]);
@@ -2483,7 +2561,7 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 				if (floorv > st.best[h]) { st.best[h] = floorv; st.btc[h] = 0x7fffffff; st.brow[h] = 0; }
 			}
 		}
-		build_profile_strip<RR, GL, FORM == 3 ? (CAPTURE ? 3 : 2) : 0>(lds, x.prof, l16, GL, a.mat, a.n, qa, lena, rev, rowsa, qb, lenb, rev, rowsb, x.row0, (int)(a.gapE2 & 0xffffu));
+		build_profile_strip<RR, GL, FORM == 3 ? (TWO ? 3 : 2) : 0>(lds, x.prof, l16, GL, a.mat, a.n, qa, lena, rev, rowsa, qb, lenb, rev, rowsb, x.row0, (int)(a.gapE2 & 0xffffu));
 		u32 m8[RR];
 		bool need_mask = false;
 		if (!CAPTURE) {
@@ -2497,8 +2575,8 @@ __global__ void __launch_bounds__(64) k_chainq(ssw_chainx_args a)
 #pragma unroll
 			for (int q = 0; q < RR; ++q) m8[q] = 0;
 		}
-		if (!CAPTURE && need_mask) run_strip<RR, CAPTURE, true, GL, false, FORM == 3>(lds, x, st, m8);
-		else run_strip<RR, CAPTURE, false, GL, FORM == 3, FORM == 3>(lds, x, st, m8);
+		if (!CAPTURE && need_mask) run_strip<RR, CAPTURE, true, GL, false, FORM == 3, PAIRS>(lds, x, st, m8);
+		else run_strip<RR, CAPTURE, false, GL, FORM == 3, FORM == 3, PAIRS>(lds, x, st, m8);
 
 		/* chain-wide winner of this strip merged with the strips above: value, then first column, then smallest row */
 		for (int h = 0; h < 2; ++h) {
@@ -4422,6 +4500,14 @@ extern "C" int ssw_shim_launch_reducem(const ssw_reducem_args* a, int64_t total_
 	return SSW_LAUNCH_OK();
 }
 
+extern "C" int ssw_shim_launch_reduce_pairs(const ssw_reduce_pairs_args* a, void* stream)
+{
+	ssw_reduce_pairs_args args = *a;
+	if (args.njobs <= 0) return 0;
+	SSW_LAUNCH(k_reduce_pairs, ssw_reduce_pairs_args, args, args.njobs, 256, 256 * 8, stream);
+	return SSW_LAUNCH_OK();
+}
+
 extern "C" int ssw_shim_launch_capture(int R, const ssw_capture_args* a, void* stream)
 {
 	ssw_capture_args args = *a;
@@ -4472,6 +4558,8 @@ extern "C" int ssw_shim_launch_chainx(int R, int capture, const ssw_chainx_args*
 extern "C" int ssw_shim_launch_chainq(int R, int capture, const ssw_chainx_args* a, int max_workgroups, void* stream)
 {
 	ssw_chainx_args args = *a;
+	const bool pairs = capture == 2;      /* pair mode of the fill: two target rings like a window pass */
+	if (pairs) capture = 0;
 	if (capture) { args.nlist = args.njobs; args.njobs = (args.njobs + 1) / 2; }
 	if (args.njobs <= 0 || args.strips <= 0) return 0;
 	const int64_t items = (int64_t)args.njobs * args.strips;
@@ -4479,8 +4567,10 @@ extern "C" int ssw_shim_launch_chainq(int R, int capture, const ssw_chainx_args*
 	int64_t grid = args.whole_jobs ? args.njobs : items;
 	if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
 	switch (R) {
-#define X(r) case r: { const size_t ldsb = (size_t)(args.n + 1) * StripGeom<r, 64>::PSTRIDE + (capture ? QueueGeom<r, true>::EXTRA : QueueGeom<r, false>::EXTRA); \
-		if (capture && args.form == 3) SSW_LAUNCH((k_chainq<r, true, 3>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
+#define X(r) case r: { const size_t ldsb = (size_t)(args.n + 1) * StripGeom<r, 64>::PSTRIDE + (capture || pairs ? QueueGeom<r, true>::EXTRA : QueueGeom<r, false>::EXTRA); \
+		if (pairs && args.form == 3) SSW_LAUNCH((k_chainq<r, false, 3, true>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
+		else if (pairs) SSW_LAUNCH((k_chainq<r, false, 0, true>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
+		else if (capture && args.form == 3) SSW_LAUNCH((k_chainq<r, true, 3>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
 		else if (capture) SSW_LAUNCH((k_chainq<r, true, 0>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
 		else if (args.form == 3) SSW_LAUNCH((k_chainq<r, false, 3>), ssw_chainx_args, args, grid, 64, ldsb, stream); \
 		else SSW_LAUNCH((k_chainq<r, false, 0>), ssw_chainx_args, args, grid, 64, ldsb, stream); } break;

@@ -76,8 +76,10 @@ typedef struct {
 	int64_t n_word;        /* alignments decided under 16-bit semantics */
 	int64_t n_byte;        /* alignments decided under 8-bit semantics */
 	/* the fill kernel that evaluated most cells in the call (for roofline accounting) */
-	char fill_kernel[48];  /* e.g. "k_fill<10,frame>", "k_chainq<12,frame> x 14 strips", "k_filldb<19,frame>" */
-	double fill_ops_per_row; /* VALU instructions of the recurrence per (row, column) of a query pair in that kernel: 6.5 (column frame) / 7.5 / 8.5 / 9 */
+	char fill_kernel[48];  /* e.g. "k_fill<10,frame>", "k_chainq<12,frame> x 14 strips", "k_chainq<12,pairs,frame> x 13 strips + 1 of 1", "k_filldb<19,frame>" */
+	double fill_ops_per_row; /* VALU instructions of the recurrence per (row, column) of a query pair in that kernel: 6.5 (column frame) / 7.5 / 8.5 / 9.
+	                            k_chainq<R,pairs,..> reports the batch fill's 6.5 / 9 although it merges the two halves' profile entries per row
+	                            (one more instruction): a roofline computed from it is understated for that kernel */
 	int32_t fill_rows_per_lane;
 	int32_t fill_strips;
 	int64_t db_repeats;    /* (rounds 1-2: workgroups of the database search that repeated in the int16 form; always 0 since the column-frame form) */
@@ -135,8 +137,14 @@ int ssw_gpu_align_batch(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
  * Fast path (one fused kernel, k_fillpairs: two pairs per 16-lane chain, each half of a register against its own target): gapO > gapE,
  * n <= 32, max(mat) <= 49, queries of 1..640 residues (n x ceil(ceil(len/16)/4) x 256 < 64 KiB), targets of 1..65 000 columns; with
  * flag != 0 the pairs that pass src/ssw.c:916 then go through ONE batched reverse pass and traceback (whatever the size of the target set).
- * Every other pair -- empty sequences, longer ones, gapO <= gapE, wider alphabets, larger scores -- is answered exactly but SLOWLY: one
- * internal ssw_gpu_align_batch per distinct target over the subset of its queries (gathered on the device).
+ * Fast path of long reads (the strip kernel's pair mode, k_chainq<R,pairs,form>: two pairs per 64-lane chain, row strips behind a work
+ * queue, then k_reduce_pairs): gapO > gapE, n <= 32, queries of 769..65 535 residues, targets of 1..65 000 columns, one job's scratch
+ * (about 24 bytes per target column) within half of ssw_gpu_get_budget; no limit on max(mat) -- the form of the recurrence follows the
+ * scores.  Same records, same flagged phases, pairs of both envelopes in one call in any order.
+ * Queries of 641..768 residues are on NEITHER fast path (k_fillpairs ends at 40 rows per lane, the strip kernel's pair mode starts where
+ * every query has at least two strips).  They and every other pair -- empty sequences, gapO <= gapE, wider alphabets, larger scores of
+ * short reads, targets over 65 000 columns -- are answered exactly but SLOWLY: one internal ssw_gpu_align_batch per distinct target over
+ * the subset of its queries (gathered on the device).
  */
 int ssw_gpu_align_pairs(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
                         const int32_t* qidx, const int32_t* tidx, int64_t npairs,
@@ -158,14 +166,16 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
  * as for ssw_gpu_align_pairs; every phase stays within ssw_gpu_get_budget(ctx) (the window table, 32 bytes per pair, is an input of the call
  * like the job list, not scratch).
  *
- * Fast path: ssw_gpu_align_pairs' envelope with "target" read as "window" (gapO > gapE, n <= 32, max(mat) <= 49, queries of 1..640
- * residues, windows of 1..65 000 columns), for EVERY flag and whatever the size of the resident target set (2^31 residues and more).  On
- * that path no target residue is copied: the fill, the reverse pass, the traceback and mark_mismatch read the window where it lies, through
- * a per-pair (64-bit start, length) table built on the device.  Everything else -- longer windows or queries, empty ones, gapO <= gapE,
- * wider alphabets, larger scores -- is answered exactly and may be slow: those windows are gathered on the device into temporary sets
- * (identical windows once) and handed to ssw_gpu_align_pairs' path; ssw_gpu_timing.win_copied counts their residues.
+ * Fast path: ssw_gpu_align_pairs' two envelopes with "target" read as "window" -- gapO > gapE, n <= 32, windows of 1..65 000 columns and
+ * either queries of 1..640 residues with max(mat) <= 49 (k_fillpairs) or queries of 769..65 535 residues (the strip kernel's pair mode,
+ * any max(mat), a job's scratch within half the budget) --, for EVERY flag and whatever the size of the resident target set (2^31 residues
+ * and more).  On that path no target residue is copied: the fill, the reverse pass, the traceback and mark_mismatch read the window where it
+ * lies, through a per-pair (64-bit start, length) table built on the device.  Everything else -- queries of 641..768 residues, longer
+ * windows, empty ones, gapO <= gapE, wider alphabets, larger scores of short reads -- is answered exactly and may be slow: those windows
+ * are gathered on the device into temporary sets (identical windows once) and handed to ssw_gpu_align_pairs' path;
+ * ssw_gpu_timing.win_copied counts their residues.
  * Not provided (yet): a multi-device pool variant, a CLI option, a strand flag per pair (both strands: ssw_gpu_seqs_with_revcomp on the
- * reads and qidx = count + i), a wider envelope (queries over 640 residues, windows over 65 000 columns on the fast path).
+ * reads and qidx = count + i), a wider envelope (queries of 641..768 residues, windows over 65 000 columns on the fast path).
  */
 int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
                           const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
@@ -187,11 +197,11 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const s
  *               maskLen, score_size and mark_mismatch (window-relative positions); a group without an eligible candidate -- an empty group
  *               too -- gets ssw_gpu_search_topk's padding record (zeros, ref_begin1 = read_begin1 = -1, cigar_off = -1);
  *   cigar_pool  (optional, malloc()ed, caller frees) the winners' CIGARs in group order.
- * The forward fill runs once over all candidates (k_fillpairs, as for ssw_gpu_align_windows: no target residue is copied inside the
- * envelope); the selection runs on the device (k_groupbest); one record per GROUP comes to the host; the reverse pass, the traceback and
+ * The forward fill runs once over all candidates (k_fillpairs and, for reads of 769 residues and more, the strip kernel's pair mode, as for
+ * ssw_gpu_align_windows: no target residue is copied inside the two envelopes); the selection runs on the device (k_groupbest); one record per GROUP comes to the host; the reverse pass, the traceback and
  * mark_mismatch run over the winners only (ssw_gpu_timing.best_flagged), their fill records reused.
- * Candidates outside the fast-path envelope (empty ones, reads over 640 residues, windows over 65 000 columns, gapO <= gapE, alphabets over
- * 32 letters, max(mat) > 49) are exact in any mix, inside one group too: they take ssw_gpu_align_windows' fallback at flag 0 first, their
+ * Candidates outside the fast-path envelopes (empty ones, reads of 641..768 residues, windows over 65 000 columns, gapO <= gapE, alphabets
+ * over 32 letters, max(mat) > 49 with reads up to 640 residues) are exact in any mix, inside one group too: they take ssw_gpu_align_windows' fallback at flag 0 first, their
  * records are uploaded beside the fill's, the DEVICE selects over everything, and those of them that win take the fallback once more
  * with the caller's flag.
  * Memory: the state that outlives a fill launch -- 48 bytes of record and 4 bytes of slot map per candidate, 64 bytes of output (record +
@@ -203,7 +213,7 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const s
  * another context.  ngroups == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for ssw_gpu_align_windows.
  * ssw_gpu_last_timing: reduce_ms is the device time of k_groupbest; best_flagged the winners handed to the reverse pass / traceback.
  * Not provided (yet): a multi-device pool variant, a CLI option, more than the best two per group, building the survivor list of the
- * flagged stage on the device (the winners' records make one round trip to the host).
+ * flagged stage on the device (the winners' records make one round trip to the host), a fast path for reads of 641..768 residues.
  */
 typedef struct {
 	int32_t best;          /* position in the candidate list of the group's best eligible candidate; -1: none */
