@@ -423,6 +423,22 @@ typedef struct {
 	                                record of an empty target (zeros, ref_begin1 = read_begin1 = -1, cigar_off = -1) when the group has no eligible candidate */
 } ssw_groupbest_args;
 
+/* Best k candidate windows per read (ssw_gpu_align_windows_topk): k_groupbest's inputs, eligibility and order, k ranks per group.  Rank
+   r >= 1 is reported only while its score1 >= score1(rank 0) - max_drop (max_drop < 0: no cut); the slots past the last reported rank
+   hold pos -1 and the record of an empty target.  n_eligible counts the eligible candidates whatever k and max_drop are. */
+typedef struct {
+	const struct ssw_out_rec* rec;
+	const int32_t* slot;         /* candidate -> index into rec */
+	const int64_t* cand_off;     /* ngroups + 1 */
+	int64_t ngroups;
+	int32_t min_score;
+	int32_t k;                   /* 1 .. SSW_GPU_GROUP_TOPK_MAX; ngroups * k <= 0x7fffff00 */
+	int32_t max_drop;
+	int32_t* pos;                /* [ngroups][k] */
+	int32_t* n_eligible;         /* [ngroups] */
+	struct ssw_out_rec* out;     /* [ngroups][k]: the ranked candidates' records as the fill wrote them (SSW_OUT_WORD kept) */
+} ssw_grouptopk_args;
+
 /* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
 typedef struct {
 	const int8_t* src;
@@ -522,6 +538,7 @@ int ssw_shim_launch_seqgather(const ssw_seqgather_args* a, void* stream);
 int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream);
 int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefront per query */
 int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream);   /* one DPP row of 16 lanes per group */
+int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stream);   /* the same geometry, k ranks per group */
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

@@ -2973,8 +2973,18 @@ out:
 static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, const pair_src* src,
                             const int64_t* list, int64_t nl, const ssw_gpu_params* prm, ssw_gpu_result* results, cigar_stage* st, call_acc* acc);
 
-/* select mode of the pair list (ssw_gpu_align_windows_best): the pairs are candidates in groups, `results` has one record per GROUP */
-typedef struct { const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel; } best_mode;
+/* select mode of the pair list: the pairs are candidates in groups.  ssw_gpu_align_windows_best (k == 0): `results` has one record per
+   GROUP, `sel` the selections.  ssw_gpu_align_windows_topk (k >= 1): `results` has k records per group, slot g * k + r for rank r, `pos`
+   their positions in the group and `n_eligible` one count per group */
+typedef struct {
+	const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel;
+	int32_t k, max_drop; int32_t* pos; int32_t* n_eligible;
+} best_mode;
+/* device bytes of the per-group output behind the call-long record array: record + selection (64) / k records, k positions and a count */
+static size_t best_out_bytes(const best_mode* bm)
+{
+	return bm->k ? (size_t)bm->ngroups * ((sizeof(struct ssw_out_rec) + 4) * (size_t)bm->k + 4) : 64 * (size_t)bm->ngroups;
+}
 
 /* windows_fallback over the candidates list[0 .. nl) of a select-mode call, records to out[0 .. nl) in list order (the candidates' four
    arrays are compacted, so that the fallback's "pair index" is the position in the list) */
@@ -2997,8 +3007,9 @@ out:
 
 /* The pair list of the entry points, arguments checked by the caller: planning, launch loop, flagged phases, fallback and pool assembly.
    They differ only in where a pair's target starts and how long it is (pair_src) -- and, with `bm` (select mode), in what happens to the
-   fill's records: they stay on the device in one call-long array, k_groupbest selects per group after the last fill launch, one record and
-   one selection per group come to the host, and only the winners go on to the flagged phases.  The candidates outside the envelope take
+   fill's records: they stay on the device in one call-long array, k_groupbest (k_grouptopk: the best k) selects per group after the last
+   fill launch, one record and one selection per group (k records and positions) come to the host, and only the winners go on to the
+   flagged phases.  The candidates outside the envelope take
    the fallback at flag 0 FIRST (their records join the device array, so that the selection happens in one place) and, where they win and
    flag != 0, once more with the caller's flag. */
 static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src,
@@ -3035,7 +3046,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	ssw_pjob* jobs = 0; int64_t* jix = 0; ssw_gpu_result* stage = 0;
 	ssw_gpu_result* fbrec = 0; int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0;      /* select mode */
 	unsigned char* d_brec = 0; int8_t* d_mat = 0; int64_t nj = 0;
-	const int64_t nout = bm ? bm->ngroups : np;
+	const int64_t nout = bm ? bm->ngroups * (bm->k ? bm->k : 1) : np;
 	cigar_stage st; memset(&st, 0, sizeof st);
 	call_acc acc; memset(&acc, 0, sizeof acc);
 	int rc = -1;
@@ -3135,8 +3146,9 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (!d_hdr || !d_cnt) goto done;
 		if (!bm && !stage) { fail(c, "out of host memory%s", ""); goto done; }
 		/* select mode: the records of ALL fill launches stay on the device (two per job, then the fallback's), followed by the per-group output.
-		   An input / output of the call like the window table, not scratch under the budget: 48 bytes per candidate */
-		if (bm && !(d_brec = (unsigned char*)ensure(c, &c->brec, sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb) + 64 * (size_t)bm->ngroups))) goto done;
+		   An input / output of the call like the window table, not scratch under the budget: 48 bytes per candidate; 64 per group, or with
+		   k ranks (ssw_gpu_align_windows_topk) 52 k + 4 per group */
+		if (bm && !(d_brec = (unsigned char*)ensure(c, &c->brec, sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb) + best_out_bytes(bm)))) goto done;
 		d_mat = (int8_t*)d_hdr;
 		ssw_pjob* d_jobs = (ssw_pjob*)(d_hdr + hdr_mat);
 		c->nev = 0;
@@ -3276,10 +3288,10 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		}
 	}
 	if (bm) {
-		/* ---- select: candidate -> record slot, k_groupbest, one selection + one record per group to the host */
+		/* ---- select: candidate -> record slot, k_groupbest (k_grouptopk), one selection + one record (k positions + k records) per group to the host */
 		const int64_t ng = bm->ngroups;
 		const size_t rec_bytes = sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb);
-		if (!d_brec && !(d_brec = (unsigned char*)ensure(c, &c->brec, rec_bytes + 64 * (size_t)ng))) goto done;
+		if (!d_brec && !(d_brec = (unsigned char*)ensure(c, &c->brec, rec_bytes + best_out_bytes(bm)))) goto done;
 		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + 4 * (size_t)np);      /* (4 bytes per candidate, 8 per group) */
 		slot = (int32_t*)malloc(sizeof(int32_t) * (size_t)np);
 		if (!d_map) goto done;
@@ -3287,42 +3299,62 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		for (int64_t j = 0; j < nj; ++j)
 			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) slot[jix[2 * j + h]] = (int32_t)(2 * j + h);
 		for (int64_t f = 0; f < nfb; ++f) slot[fb[f]] = (int32_t)(2 * nj + f);
-		ssw_groupbest_args ga; memset(&ga, 0, sizeof ga);
-		ga.rec = (const struct ssw_out_rec*)d_brec; ga.cand_off = (const int64_t*)d_map; ga.slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1));
-		ga.ngroups = ng; ga.min_score = bm->min_score;
-		ga.out = (struct ssw_out_rec*)(d_brec + rec_bytes); ga.sel = (struct ssw_best_rec*)(d_brec + rec_bytes + sizeof(struct ssw_out_rec) * (size_t)ng);
-		if ((nfb > 0 && ssw_shim_h2d((void*)(ga.rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
-		    ssw_shim_h2d((void*)ga.cand_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)ga.slot, slot, 4 * (size_t)np, c->stream)) {
+		const int32_t K = bm->k;
+		const struct ssw_out_rec* d_rec = (const struct ssw_out_rec*)d_brec;
+		const int64_t* d_off = (const int64_t*)d_map; const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1));
+		unsigned char* d_sel = d_brec + rec_bytes;      /* best: [ng] records, [ng] selections; top-k: [nout] records, [nout] positions, [ng] counts */
+		if ((nfb > 0 && ssw_shim_h2d((void*)(d_rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
+		    ssw_shim_h2d((void*)d_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)d_slot, slot, 4 * (size_t)np, c->stream)) {
 			fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
 		}
 		ssw_shim_event_record(c->ev_a, c->stream);
-		if (ssw_shim_launch_groupbest(&ga, c->stream)) { fail(c, "groupbest launch failed: %s", ssw_shim_last_error()); goto done; }
-		ssw_shim_event_record(c->ev_b, c->stream);
-		if (ssw_shim_d2h(results, ga.out, sizeof(ssw_gpu_result) * (size_t)ng, c->stream) || ssw_shim_d2h(bm->sel, ga.sel, sizeof(ssw_gpu_best) * (size_t)ng, c->stream) ||
-		    ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+		if (K) {
+			ssw_grouptopk_args ta; memset(&ta, 0, sizeof ta);
+			ta.rec = d_rec; ta.cand_off = d_off; ta.slot = d_slot; ta.ngroups = ng; ta.min_score = bm->min_score; ta.k = K; ta.max_drop = bm->max_drop;
+			ta.out = (struct ssw_out_rec*)d_sel; ta.pos = (int32_t*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)nout); ta.n_eligible = ta.pos + nout;
+			if (ssw_shim_launch_grouptopk(&ta, c->stream)) { fail(c, "grouptopk launch failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(c->ev_b, c->stream);
+			if (ssw_shim_d2h(results, ta.out, sizeof(ssw_gpu_result) * (size_t)nout, c->stream) || ssw_shim_d2h(bm->pos, ta.pos, 4 * (size_t)nout, c->stream) ||
+			    ssw_shim_d2h(bm->n_eligible, ta.n_eligible, 4 * (size_t)ng, c->stream) || ssw_shim_stream_sync(c->stream)) {
+				fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
+			}
+		} else {
+			ssw_groupbest_args ga; memset(&ga, 0, sizeof ga);
+			ga.rec = d_rec; ga.cand_off = d_off; ga.slot = d_slot; ga.ngroups = ng; ga.min_score = bm->min_score;
+			ga.out = (struct ssw_out_rec*)d_sel; ga.sel = (struct ssw_best_rec*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)ng);
+			if (ssw_shim_launch_groupbest(&ga, c->stream)) { fail(c, "groupbest launch failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(c->ev_b, c->stream);
+			if (ssw_shim_d2h(results, ga.out, sizeof(ssw_gpu_result) * (size_t)ng, c->stream) || ssw_shim_d2h(bm->sel, ga.sel, sizeof(ssw_gpu_best) * (size_t)ng, c->stream) ||
+			    ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+		}
 		c->tm.reduce_ms = ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
 		/* ---- the winners alone go on: the fused path's through the reverse pass and the traceback (their fill records reused), the others
-		   through the fallback once more with the caller's flag */
-		int64_t nin = 0, nfw = 0; int64_t* wg = 0;
+		   through the fallback once more with the caller's flag.  One survivor list over all output slots; top-k: every slot that holds a
+		   candidate (pairs_flagged applies the reference's gate, and takes the fill's word mark out of the records it leaves alone) */
+		int64_t nin = 0, nfw = 0, ngate = 0; int64_t* wg = 0;
 		if (prm->flag != 0) {
-			wlist = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)ng); wrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)ng);
+			wlist = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)nout); wrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nout);
 			if (!wlist || !wrec) { fail(c, "out of host memory%s", ""); goto done; }
-			wg = wlist + ng;      /* wlist: the fused path's winners from the front, the fallback's from the back; wg: their groups */
-			for (int64_t g = 0; g < ng; ++g) {
-				if (bm->sel[g].best < 0) continue;
-				const int64_t i = bm->cand_off[g] + bm->sel[g].best;
-				if (key[i] == PJ_KEY_FALLBACK) { ++nfw; wlist[ng - nfw] = i; wg[ng - nfw] = g; }
-				else { wlist[nin] = i; wg[nin] = g; wrec[nin] = results[g]; ++nin; }
-			}
+			const int64_t per = K ? K : 1;      /* output slots of a group */
+			wg = wlist + nout;      /* wlist: the fused path's winners from the front, the fallback's from the back; wg: their output slots */
+			for (int64_t g = 0; g < ng; ++g)
+				for (int64_t o = g * per; o < (g + 1) * per; ++o) {
+					const int32_t p = K ? bm->pos[o] : bm->sel[g].best;
+					if (p < 0) break;
+					const int64_t i = bm->cand_off[g] + p;
+					if (!(prm->flag == 2 && (int)results[o].score1 < prm->filters)) ++ngate;      /* ssw.c:916 */
+					if (key[i] == PJ_KEY_FALLBACK) { ++nfw; wlist[nout - nfw] = i; wg[nout - nfw] = o; }
+					else { wlist[nin] = i; wg[nin] = o; wrec[nin] = results[o]; ++nin; }
+				}
 			if (nin > 0 && pairs_flagged(c, Q, T, qidx, src, wlist, wrec, nin, prm, d_mat, maxmat, minmat, &st)) goto done;
 			for (int64_t k = 0; k < nin; ++k) results[wg[k]] = wrec[k];
 		}
 		timing_add(&acc, &c->tm);
 		if (nfw > 0) {
-			if (best_fallback(c, Q, T, qidx, src, wlist + (ng - nfw), nfw, prm, wrec, &st, &acc)) goto done;
-			for (int64_t k = 0; k < nfw; ++k) results[wg[ng - nfw + k]] = wrec[k];
+			if (best_fallback(c, Q, T, qidx, src, wlist + (nout - nfw), nfw, prm, wrec, &st, &acc)) goto done;
+			for (int64_t k = 0; k < nfw; ++k) results[wg[nout - nfw + k]] = wrec[k];
 		}
-		acc.t.best_flagged = nin + nfw;
+		acc.t.best_flagged = K ? ngate : nin + nfw;
 	}
 	if (!bm && nfb > 0 && (src->tbeg ? windows_fallback(c, Q, T, qidx, src, fb, nfb, prm, results, &st, &acc)
 	                          : pairs_fallback(c, Q, T, qidx, tidx, fb, nfb, prm, results, &st, &acc))) goto done;
@@ -3527,7 +3559,8 @@ static int align_windows_best_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, cons
 	}
 	pair_src src; memset(&src, 0, sizeof src);
 	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows_best";
-	best_mode bm; bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.sel = sel;
+	best_mode bm; memset(&bm, 0, sizeof bm);
+	bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.sel = sel;
 	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
 }
 
@@ -3539,6 +3572,67 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
 	if (!c) return fail(0, "align_windows_best: NULL context%s", "");
 	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
 	return ctx_leave(c, align_windows_best_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, min_score, sel, results, cigar_pool, cigar_words));
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Best k candidate windows per read (ssw_gpu_align_windows_topk): the same select mode with k ranks per group (k_grouptopk).
+ * Device state that outlives a fill launch, an input / output of the call like the window table: per candidate 48 bytes of record + 4 of
+ * slot map (+ the 32 of the window table), per group 52 k + 4 bytes of output (k records of 48, k positions, one count) + 8 of offsets.
+ * ------------------------------------------------------------------------------------------------ */
+static int align_windows_topk_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t ng,
+                                     const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, const ssw_gpu_params* prm,
+                                     int32_t k, int32_t min_score, int32_t max_drop, int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results,
+                                     uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	char msg[200];
+	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
+	if (cigar_words) *cigar_words = 0;
+	if (k < 1 || k > SSW_GPU_GROUP_TOPK_MAX) {
+		snprintf(msg, sizeof msg, "k = %d", k);
+		return fail(c, "align_windows_topk: k must be 1 .. 64 (%s)", msg);
+	}
+	if (ng < 0 || (ng > 0 && (!cand_off || !pos || !n_eligible || !results))) return fail(c, "align_windows_topk: NULL argument%s", "");
+	if (check_common(c, "align_windows_topk", Q, T, prm)) return -1;
+	if (ng == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }
+	if (ng > 0x7fffff00 / k) {
+		snprintf(msg, sizeof msg, "%lld groups x %d", (long long)ng, k);
+		return fail(c, "align_windows_topk: more than 2^31 output slots in one call (%s)", msg);
+	}
+	if (cand_off[0] != 0) {
+		snprintf(msg, sizeof msg, "group 0 starts at candidate %lld", (long long)cand_off[0]);
+		return fail(c, "align_windows_topk: cand_off[0] must be 0 (%s)", msg);
+	}
+	for (int64_t g = 0; g < ng; ++g)
+		if (cand_off[g + 1] < cand_off[g]) {
+			snprintf(msg, sizeof msg, "group %lld: candidates [%lld, %lld)", (long long)g, (long long)cand_off[g], (long long)cand_off[g + 1]);
+			return fail(c, "align_windows_topk: cand_off decreases (%s)", msg);
+		}
+	const int64_t np = cand_off[ng];
+	if (np > 0x7fffff00) return fail(c, "align_windows_topk: %s", "more than 2^31 candidates in one call");
+	if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) return fail(c, "align_windows_topk: NULL argument%s", "");
+	if (windows_check(c, "align_windows_topk", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
+	if (np == 0) {      /* empty groups only */
+		memset(&c->tm, 0, sizeof c->tm);
+		for (int64_t o = 0; o < ng * k; ++o) { topk_pad(&results[o]); pos[o] = -1; }
+		memset(n_eligible, 0, sizeof(int32_t) * (size_t)ng);
+		return 0;
+	}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows_topk";
+	best_mode bm; memset(&bm, 0, sizeof bm);
+	bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.k = k; bm.max_drop = max_drop; bm.pos = pos; bm.n_eligible = n_eligible;
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
+}
+
+int ssw_gpu_align_windows_topk(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t ngroups,
+                               const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                               const ssw_gpu_params* prm, int32_t k, int32_t min_score, int32_t max_drop,
+                               int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows_topk: NULL context%s", "");
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_topk_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, k, min_score, max_drop, pos, n_eligible,
+	                                              results, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------

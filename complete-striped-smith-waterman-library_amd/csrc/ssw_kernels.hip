@@ -4272,6 +4272,89 @@ __global__ void __launch_bounds__(256) k_groupbest(ssw_groupbest_args a)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * k_grouptopk (ssw_grouptopk_args): the best k eligible candidates of every group (ssw_gpu_align_windows_topk), in k_groupbest's order and
+ * on its geometry -- one DPP row of 16 lanes per group, the 64-bit key score1 << 32 | ~position, 0 for "none".  Keys are distinct (the
+ * position is part of them), so rank r is the row-wide maximum of the keys STRICTLY BELOW rank r - 1's: a selection by repeated maximum,
+ * a pure function of the keys.  A lane loads the keys of its strided positions once and keeps the first GT_CACHE of them (positions
+ * below 16 x GT_CACHE) in registers; a larger group re-reads slot map and records of the rest at every rank (rare: typical groups hold
+ * 2..50 candidates).  A row stops at k, at the first empty maximum or at the max_drop cut; the rank loop is wavefront-uniform (it runs
+ * while any row of the wavefront goes on), so that every lane meets every rotation.  The winner's 48-byte record goes out as three
+ * 16-byte pieces (lanes 0..2), its position from lane 3; when the loop has ended the 16 lanes of a row fill the row's remaining slots
+ * with the padding record and -1, a piece per lane and turn.  No LDS, no atomics, no waiting.
+ * ------------------------------------------------------------------------------------------------ */
+#define GT_CACHE 4
+SSW_DEV unsigned long long gt_key(const ssw_grouptopk_args& a, int64_t c0, int64_t p, int lo)
+{
+	const u32* r = (const u32*)(a.rec + a.slot[c0 + p]);
+	const u32 s = r[0] & 0xffffu, st = (r[10] >> 16) & ~(u32)SSW_OUT_WORD;      /* as k_groupbest reads them */
+	return st == 0 && (int)s >= lo ? ((unsigned long long)s << 32) | (u32)~(u32)p : 0ull;
+}
+template <int N> SSW_DEV unsigned long long gt_rowmax(unsigned long long v)
+{
+	const unsigned long long o = gb_ror<N>(v);
+	return v > o ? v : o;
+}
+
+__global__ void __launch_bounds__(256) k_grouptopk(ssw_grouptopk_args a)
+{
+	const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;      /* (a row is inside the list or outside it as a whole) */
+	const int l = (int)threadIdx.x & 15;
+	const bool live = g < a.ngroups;
+	const int lo = a.min_score > 1 ? a.min_score : 1;
+	const int k = a.k;
+	unsigned long long kc[GT_CACHE];
+	u32 cnt = 0;
+	int64_t c0 = 0, n = 0;
+#pragma unroll
+	for (int j = 0; j < GT_CACHE; ++j) kc[j] = 0;
+	if (live) {
+		c0 = a.cand_off[g];
+		n = a.cand_off[g + 1] - c0;
+#pragma unroll
+		for (int j = 0; j < GT_CACHE; ++j)
+			if (l + 16 * j < n) { kc[j] = gt_key(a, c0, l + 16 * j, lo); cnt += kc[j] != 0; }
+		for (int64_t p = l + 16 * GT_CACHE; p < n; p += 16) cnt += gt_key(a, c0, p, lo) != 0;
+	}
+	cnt += xl_row_ror<8>(cnt); cnt += xl_row_ror<4>(cnt); cnt += xl_row_ror<2>(cnt); cnt += xl_row_ror<1>(cnt);
+	const int64_t o0 = g * k;      /* first slot of the group (ngroups x k <= 0x7fffff00: the host's check) */
+	unsigned long long prev = ~0ull;
+	int first = 0, nr = 0;         /* score1 of rank 0; ranks written */
+	bool go = live && cnt != 0;
+	for (int r = 0; r < k && wave_any(go); ++r) {
+		unsigned long long m = 0;
+		if (go) {
+#pragma unroll
+			for (int j = 0; j < GT_CACHE; ++j) if (kc[j] < prev && kc[j] > m) m = kc[j];
+			for (int64_t p = l + 16 * GT_CACHE; p < n; p += 16) {
+				const unsigned long long key = gt_key(a, c0, p, lo);
+				if (key < prev && key > m) m = key;
+			}
+		}
+		m = gt_rowmax<8>(m); m = gt_rowmax<4>(m); m = gt_rowmax<2>(m); m = gt_rowmax<1>(m);
+		if (!go) continue;
+		const int s = (int)(u32)(m >> 32);
+		if (r == 0) first = s;
+		if (m == 0 || (a.max_drop >= 0 && s < first - a.max_drop)) { go = false; continue; }
+		const int pos = (int)~(u32)m;
+		if (l < 3) ((u32x4*)(a.out + o0 + r))[l] = ((const u32x4*)(a.rec + a.slot[c0 + pos]))[l];
+		else if (l == 3) a.pos[o0 + r] = pos;
+		prev = m;
+		nr = r + 1;
+	}
+	if (!live) return;
+	if (l == 0) a.n_eligible[g] = (int32_t)cnt;
+	/* the slots past the last rank: four pieces of work per slot (three of the padding record, the position) */
+	for (int w = 4 * nr + l; w < 4 * k; w += 16) {
+		const int r = w >> 2, piece = w & 3;
+		if (piece == 3) { a.pos[o0 + r] = -1; continue; }
+		u32x4 v = { 0u, 0u, 0u, 0u };
+		if (piece == 0) { v.y = 0xffffffffu; v.w = 0xffffffffu; }      /* ref_begin1, read_begin1 */
+		else if (piece == 2) { v.x = 0xffffffffu; v.y = 0xffffffffu; }      /* cigar_off */
+		((u32x4*)(a.out + o0 + r))[piece] = v;
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------
  * k_selftest: (a) the cross-lane primitives applied to the lane id, so that tests can pin the DPP semantics the
  * chains rely on (and that the CPU emulator assumes) on real hardware; (b) a packed-int16 VALU issue-rate probe
  * (8 independent v_pk_add_i16/v_pk_max_i16/v_pk_sub_u16 chains) whose measured rate is the roofline's "peak".
@@ -4459,7 +4542,16 @@ extern "C" int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stre
 	return SSW_LAUNCH_OK();
 }
 
-/* several buckets in one grid: hR = the rows per lane of the nsub sub-launches (host copy: sizes the LDS), all of one register class and form */
+extern "C" int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stream)
+{
+	ssw_grouptopk_args args = *a;
+	if (args.ngroups <= 0) return 0;
+	if (args.k < 1) return -2;
+	SSW_LAUNCH(k_grouptopk, ssw_grouptopk_args, args, (args.ngroups + 15) / 16, 256, 0, stream);
+	return SSW_LAUNCH_OK();
+}
+
+/* several buckets in one grid: hR =the rows per lane of the nsub sub-launches (host copy: sizes the LDS), all of one register class and form */
 extern "C" int ssw_shim_fill_class(int R) { return R <= 10 ? 0 : R <= 16 ? 1 : 2; }
 extern "C" int ssw_shim_launch_fillm(const ssw_fillm_args* a, const int32_t* hR, int n, int form, int64_t total_wgs, void* stream)
 {

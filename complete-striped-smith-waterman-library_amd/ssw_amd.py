@@ -122,6 +122,11 @@ def load(path=None):
         L.ssw_gpu_align_windows_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_windows_best.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows_topk"):
+        L.ssw_gpu_align_windows_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_topk.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -425,6 +430,59 @@ class Context(object):
                 v = res[f]
                 res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
         return sel, res, cig
+
+    def align_windows_topk(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, mat, n, k, min_score=0, max_drop=-1, rebase=False, gapO=3,
+                           gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None):
+        """best k candidate windows per read (ssw_gpu_align_windows_topk): align_windows_best's groups and ranking, k ranks per group; rank
+        r >= 1 only while its score1 >= score1(rank 0) - max_drop (max_drop < 0: no cut)
+        -> (pos int32 [ngroups, k] -- positions in the group, -1 past the last --, n_eligible int32 [ngroups], records [ngroups, k] of
+        RESULT_DTYPE -- the empty record where pos is -1 --, uint32 CIGAR pool in (group, rank) order).  rebase=True adds the chosen
+        candidate's tbeg to ref_begin1, ref_end1 and ref_end2 where they are >= 0.  `out`: (pos, n_eligible, records) to fill."""
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1:
+            raise ValueError("cand_off must be a 1-D array of ngroups + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        ng = int(co.shape[0]) - 1
+        if ng > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[ngroups] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        k = int(k)
+        kk = max(k, 0)                                # (the library refuses k < 1; the arrays only have to exist)
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            pos = np.zeros((ng, kk), dtype=np.int32)
+            nel = np.zeros(ng, dtype=np.int32)
+            res = np.zeros((ng, kk), dtype=RESULT_DTYPE)
+        else:
+            pos, nel, res = out
+            if pos.dtype != np.int32 or nel.dtype != np.int32 or res.dtype != RESULT_DTYPE or pos.shape != (ng, kk) or nel.shape != (ng,) or \
+                    res.shape != (ng, kk) or not pos.flags["C_CONTIGUOUS"] or not nel.flags["C_CONTIGUOUS"] or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be C-contiguous arrays: int32 [ngroups, k], int32 [ngroups], RESULT_DTYPE [ngroups, k]")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_align_windows_topk(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), ng, qi.ctypes.data_as(C.c_void_p),
+                                                 ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                 C.byref(p), k, int(min_score), int(max_drop), pos.ctypes.data_as(C.c_void_p),
+                                                 nel.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                                 C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_align_windows_topk: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase and ng > 0:
+            hit = pos >= 0
+            wb = np.zeros((ng, kk), dtype=np.int64)
+            wb[hit] = tb[(co[:-1, None] + pos)[hit]]
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                v = res[f]
+                res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
+        return pos, nel, res, cig
 
     def search_db(self, queries, targets, mat, n, gapO=3, gapE=1, maskLen=-1, score_size=2, chunk=0, on_chunk=None):
         """streamed database search (ssw_gpu_search_db): on_chunk(target_first, hits[nq, target_count] of HIT_DTYPE) is called for

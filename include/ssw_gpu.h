@@ -70,7 +70,7 @@ typedef struct {
 	int64_t fill_cells;    /* DP cells actually evaluated by the fill kernel (padding + halo included) */
 	int64_t cells;         /* sum of readLen*refLen over the batch (the GCUPS numerator) */
 	double reduce_ms;      /* score1/score2/end-position reduction (ssw_gpu_search_topk: the device time of the k_topk selection;
-	                          ssw_gpu_align_windows_best: of the k_groupbest selection) */
+	                          ssw_gpu_align_windows_best / _topk: of the k_groupbest / k_grouptopk selection) */
 	double locate_ms;      /* read_end1 + reverse (begin position) passes */
 	double trace_ms;       /* banded traceback + CIGAR re-score */
 	int64_t n_word;        /* alignments decided under 16-bit semantics */
@@ -87,7 +87,8 @@ typedef struct {
 	                           fill_ms brackets each series as a whole -- fill_ms / fill_launches is then the series' time per launch, not a kernel's duration */
 	int64_t win_copied;    /* ssw_gpu_align_windows: target residues copied into temporary sets by the call (0 when every pair took the fast path;
 	                          always 0 for the other entry points) */
-	int64_t best_flagged;  /* ssw_gpu_align_windows_best: pairs the call handed to the reverse pass and the traceback -- the winners, never more than ngroups;
+	int64_t best_flagged;  /* ssw_gpu_align_windows_best: pairs the call handed to the reverse pass and the traceback -- the winners, never more than ngroups
+	                          (ssw_gpu_align_windows_topk: the reported slots that pass src/ssw.c:916, never more than ngroups * k);
 	                          0 with flag 0 and for the other entry points */
 	/* new fields are only ever appended here; ssw_gpu_last_timing_sized lets a caller built against an older header keep its layout */
 } ssw_gpu_timing;
@@ -212,8 +213,9 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const s
  * decreasing cand_off, more than 0x7fffff00 candidates, an index or window out of range (ssw_gpu_align_windows' text), sequences of
  * another context.  ngroups == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for ssw_gpu_align_windows.
  * ssw_gpu_last_timing: reduce_ms is the device time of k_groupbest; best_flagged the winners handed to the reverse pass / traceback.
- * Not provided (yet): a multi-device pool variant, a CLI option, more than the best two per group, building the survivor list of the
+ * Not provided (yet): a multi-device pool variant, a CLI option, building the survivor list of the
  * flagged stage on the device (the winners' records make one round trip to the host), a fast path for reads of 641..768 residues.
+ * More than the best two per group: ssw_gpu_align_windows_topk.
  */
 typedef struct {
 	int32_t best;          /* position in the candidate list of the group's best eligible candidate; -1: none */
@@ -227,6 +229,44 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
                                const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
                                const ssw_gpu_params* params, int32_t min_score,
                                ssw_gpu_best* sel, ssw_gpu_result* results,
+                               uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Best k candidate windows per read: ssw_gpu_align_windows_best with k ranks per group -- the primary alignment of a read AND its
+ * secondaries (the other loci of a repeat, the alternate haplotype, the second strand) with begin positions and CIGARs, and the number of
+ * near-best hits a mapping quality is computed from, in one call and one forward fill.
+ * Groups, candidates, eligibility (status 0, score1 > 0, score1 >= min_score) and ranking (score1 descending, then position in the group
+ * ascending; identical windows are distinct candidates) are exactly ssw_gpu_align_windows_best's.  1 <= k <= SSW_GPU_GROUP_TOPK_MAX.
+ *   pos[g * k + r]      position, relative to cand_off[g], of the r-th ranked eligible candidate of group g; -1 past the last.  Rank r >= 1 is
+ *                       reported only if its score1 >= score1(rank 0) - max_drop (max_drop < 0: no cut; 0: ties with the best only); the
+ *                       order is descending, so the cut truncates the list: every slot after the first -1 is -1.
+ *   n_eligible[g]       eligible candidates of the group, whatever k and max_drop are (as ssw_gpu_best.n_eligible).
+ *   results[g * k + r]  bit for bit the record ssw_gpu_align_windows gives for that single pair with the caller's flag, filters, filterd,
+ *                       maskLen, score_size and mark_mismatch (window-relative positions); slots with pos == -1 hold ssw_gpu_search_topk's
+ *                       padding record (zeros, ref_begin1 = read_begin1 = -1, cigar_off = -1).
+ *   cigar_pool          (optional, malloc()ed, caller frees) the CIGARs in (g, r) order.
+ * pos and n_eligible do not depend on params->flag.  With k = 1, pos / results / the pool equal sel.best / results / the pool of
+ * ssw_gpu_align_windows_best; with k = 2 and max_drop < 0, pos[2 g + 1] == sel[g].second and results[2 g + 1].score1 == sel[g].second_score1.
+ * The forward fill runs once over all candidates as for ssw_gpu_align_windows_best; the selection runs on the device (k_grouptopk: one
+ * 16-lane row per group, rank by rank); k records per group come to the host; ONE survivor list of all reported slots goes through the
+ * reverse pass, the traceback and mark_mismatch, the fill records reused.  Candidates outside the fast-path envelopes are treated as
+ * there: the fallback at flag 0 first, the device ranks everything, those that place take the fallback once more with the caller's flag.
+ * Memory (inputs / outputs of the call like the window table, not scratch under ssw_gpu_get_budget): per candidate 48 bytes of record and
+ * 4 of slot map, per group 52 k + 4 bytes of output (k records, k positions, one count) and 8 of offsets.
+ * Errors (-1 with a message, before anything is launched or written): k outside 1..SSW_GPU_GROUP_TOPK_MAX, a NULL array, cand_off[0] != 0,
+ * a decreasing cand_off, more than 0x7fffff00 candidates, ngroups * k beyond 0x7fffff00, an index or window out of range
+ * (ssw_gpu_align_windows' text), sequences of another context.  ngroups == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the
+ * context lock as for ssw_gpu_align_windows.
+ * ssw_gpu_last_timing: reduce_ms is the device time of k_grouptopk; best_flagged the reported slots that pass src/ssw.c:916 (all of them
+ * unless flag == 2 and score1 < filters) -- the pairs handed to the reverse pass / traceback, never more than ngroups * k, 0 at flag 0.
+ * Not provided (yet): a multi-device pool variant, a CLI option, a strand flag per pair, building the survivor list on the device.
+ */
+#define SSW_GPU_GROUP_TOPK_MAX 64
+int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                               const int64_t* cand_off, int64_t ngroups,
+                               const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                               const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t max_drop,
+                               int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results,
                                uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);

@@ -299,6 +299,74 @@ class BatchAligner {
     free(pool);
   }
 
+  // The best k candidate windows of every read (ssw_gpu_align_windows_topk): AlignWindowsBest's candidate lists and ranking, k ranks per
+  // read -- the primary alignment and its secondaries.  (*alignments)[i] holds one Alignment per REPORTED rank (at most k; fewer where
+  // fewer candidates qualify or max_drop cuts the list: rank r >= 1 is reported only while its sw_score >= sw_score(rank 0) - max_drop,
+  // max_drop < 0 for no cut), (*hits)[i][r] its candidate index and s_align flag, (*eligible)[i] how many candidates qualified whatever
+  // k and max_drop are.  One forward fill over all candidates, the selection on the device, begin positions and CIGARs for the
+  // reported ranks only.
+  struct WindowHit {
+    int32_t candidate;
+    uint16_t flag;
+  };
+  void AlignWindowsTopK(const std::vector<std::string>& queries, const std::vector<std::vector<Window> >& candidates, const Filter& filter, int32_t k,
+                        std::vector<std::vector<Alignment> >* alignments, std::vector<std::vector<WindowHit> >* hits, std::vector<int32_t>* eligible,
+                        int32_t maskLen, int32_t min_score = 0, int32_t max_drop = -1, bool rebase = false) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::AlignWindowsTopK: no reference sequences");
+    if (candidates.size() != queries.size()) throw std::runtime_error("BatchAligner::AlignWindowsTopK: one candidate list per query");
+    if (k < 1 || k > SSW_GPU_GROUP_TOPK_MAX) throw std::runtime_error("BatchAligner::AlignWindowsTopK: k out of range");
+    const int32_t nq = (int32_t)queries.size();
+    alignments->assign(queries.size(), std::vector<Alignment>());
+    hits->assign(queries.size(), std::vector<WindowHit>());
+    eligible->assign(queries.size(), 0);
+    if (nq == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0), cand_off(1, 0), tbeg;
+    std::vector<int32_t> qidx, tidx, tlen;
+    for (int32_t i = 0; i < nq; ++i) {
+      text += queries[i]; off.push_back((int64_t)text.size());
+      for (size_t c = 0; c < candidates[(size_t)i].size(); ++c) {
+        const Window& w = candidates[(size_t)i][c];
+        if (w.reference < 0 || w.reference >= n_targets_) throw std::runtime_error("BatchAligner::AlignWindowsTopK: no such reference sequence");
+        qidx.push_back(i); tidx.push_back(w.reference); tbeg.push_back(w.begin); tlen.push_back(w.length);
+      }
+      cand_off.push_back((int64_t)qidx.size());
+    }
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nq, table_.data());
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<ssw_gpu_result> res((size_t)nq * (size_t)k);
+    std::vector<int32_t> pos((size_t)nq * (size_t)k);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_align_windows_topk(ctx_, Q, targets_, cand_off.data(), nq, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), &p, k, min_score,
+                                              max_drop, pos.data(), eligible->data(), res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_windows_topk: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t i = 0; i < nq; ++i)
+      for (int32_t r = 0; r < k; ++r) {
+        const size_t o = (size_t)i * (size_t)k + (size_t)r;
+        if (pos[o] < 0) break;
+        const ssw_gpu_result& rec = res[o];
+        const size_t c = (size_t)(cand_off[(size_t)i] + pos[o]);
+        Alignment a;
+        a.sw_score = rec.score1; a.sw_score_next_best = rec.score2; a.ref_begin = rec.ref_begin1; a.ref_end = rec.ref_end1;
+        a.query_begin = rec.read_begin1; a.query_end = rec.read_end1; a.ref_end_next_best = rec.ref_end2;
+        Expand(a, rec.cigarLen > 0 ? pool + rec.cigar_off : 0, rec.cigarLen, ref_codes_.data() + ref_off_[(size_t)tidx[c]] + tbeg[c], text.data() + off[(size_t)i],
+               (int)queries[(size_t)i].size());
+        if (rebase) {
+          const int32_t sh = (int32_t)tbeg[c];
+          if (a.ref_begin >= 0) a.ref_begin += sh;
+          if (a.ref_end >= 0) a.ref_end += sh;
+          if (a.ref_end_next_best >= 0) a.ref_end_next_best += sh;
+        }
+        WindowHit h; h.candidate = pos[o]; h.flag = rec.flag;
+        (*alignments)[(size_t)i].push_back(a); (*hits)[(size_t)i].push_back(h);
+      }
+    free(pool);
+  }
+
   // A database search kept to its best hits (ssw_gpu_search_topk): (*hits)[i] holds, in rank order (sw_score descending, then reference
   // index ascending), up to k references of the set whose alignment with queries[i] scores > 0 and >= min_score -- each with the Alignment
   // and flag that AlignPairs gives for that pair.  maskLen < 15 is raised to 15 like there.
