@@ -135,6 +135,14 @@ def load(path=None):
         L.ssw_gpu_pool_search_topk.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32,
                                                C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_pool_search_topk.restype = C.c_int
+    if hasattr(L, "ssw_gpu_pool_align_windows"):
+        L.ssw_gpu_pool_align_windows.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int64, C.c_int64, C.POINTER(Params), C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_pool_align_windows.restype = C.c_int
+        L.ssw_gpu_pool_align_windows_topk.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_pool_align_windows_topk.restype = C.c_int
     L.ssw_gpu_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ssw_gpu_last_timing.restype = C.c_int
     L.ssw_gpu_last_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -655,6 +663,101 @@ class Pool(object):
         if want_cigar and pool:
             C.CDLL(None).free(pool)
         return ti, res, cig
+
+    def align_windows(self, reads, qidx, tidx, tbeg, tlen, mat, n, with_revcomp=False, rebase=False, block=0, gapO=3, gapE=1, flag=0, filters=0,
+                      filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None, packed=None):
+        """Context.align_windows over the pool (ssw_gpu_pool_align_windows): windows of the pool's targets, reads from the host (a list of
+        code arrays, or packed=(codes int8, offsets int64)).  with_revcomp: qidx = nq + i names the reverse complement of read i.  block:
+        pairs per block (0: a few blocks per worker) -- the output does not depend on it
+        -> (numpy record array [npairs] of RESULT_DTYPE, numpy uint32 CIGAR pool in pair order); rebase and out as Context.align_windows."""
+        codes, off = packed if packed is not None else _pack(reads)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        npairs = int(qi.shape[0])
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            res = np.zeros(npairs, dtype=RESULT_DTYPE)
+        else:
+            res = out
+            if res.dtype != RESULT_DTYPE or res.shape != (npairs,) or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a C-contiguous [npairs] array of RESULT_DTYPE")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_pool_align_windows(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1, 1 if with_revcomp else 0,
+                                                 qi.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p),
+                                                 tl.ctypes.data_as(C.c_void_p), npairs, int(block), C.byref(p), res.ctypes.data_as(C.c_void_p),
+                                                 C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_pool_align_windows: " + self.error())
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase:
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                v = res[f]
+                res[f] = np.where(v >= 0, v + tb, v).astype(np.int32)
+        return res, cig
+
+    def align_windows_topk(self, reads, cand_off, qidx, tidx, tbeg, tlen, mat, n, k, min_score=0, max_drop=-1, with_revcomp=False, rebase=False,
+                           block=0, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False,
+                           out=None, packed=None):
+        """Context.align_windows_topk over the pool (ssw_gpu_pool_align_windows_topk): reads from the host, windows of the pool's targets;
+        with_revcomp: qidx = nq + i names the reverse complement of read i.  block: candidates per block of whole groups (0: a few blocks
+        per worker) -- the output does not depend on it
+        -> (pos int32 [ngroups, k], n_eligible int32 [ngroups], records [ngroups, k], uint32 CIGAR pool in (group, rank) order); rebase
+        and out as Context.align_windows_topk.  k = 1 answers align_windows_best; k = 2 with max_drop < 0 adds its runner-up."""
+        codes, off = packed if packed is not None else _pack(reads)
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1:
+            raise ValueError("cand_off must be a 1-D array of ngroups + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        ng = int(co.shape[0]) - 1
+        if ng > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[ngroups] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        k = int(k)
+        kk = max(k, 0)                                # (the library refuses k < 1; the arrays only have to exist)
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            pos = np.zeros((ng, kk), dtype=np.int32)
+            nel = np.zeros(ng, dtype=np.int32)
+            res = np.zeros((ng, kk), dtype=RESULT_DTYPE)
+        else:
+            pos, nel, res = out
+            if pos.dtype != np.int32 or nel.dtype != np.int32 or res.dtype != RESULT_DTYPE or pos.shape != (ng, kk) or nel.shape != (ng,) or \
+                    res.shape != (ng, kk) or not pos.flags["C_CONTIGUOUS"] or not nel.flags["C_CONTIGUOUS"] or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be C-contiguous arrays: int32 [ngroups, k], int32 [ngroups], RESULT_DTYPE [ngroups, k]")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_pool_align_windows_topk(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1,
+                                                      1 if with_revcomp else 0, co.ctypes.data_as(C.c_void_p), ng, qi.ctypes.data_as(C.c_void_p),
+                                                      ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                      int(block), C.byref(p), k, int(min_score), int(max_drop), pos.ctypes.data_as(C.c_void_p),
+                                                      nel.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                                      C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_pool_align_windows_topk: " + self.error())
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase and ng > 0:
+            hit = pos >= 0
+            wb = np.zeros((ng, kk), dtype=np.int64)
+            wb[hit] = tb[(co[:-1, None] + pos)[hit]]
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                v = res[f]
+                res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
+        return pos, nel, res, cig
 
     def stats(self):
         out = []

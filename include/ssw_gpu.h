@@ -175,7 +175,8 @@ int ssw_gpu_align_pairs(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw
  * windows, empty ones, gapO <= gapE, wider alphabets, larger scores of short reads -- is answered exactly and may be slow: those windows
  * are gathered on the device into temporary sets (identical windows once) and handed to ssw_gpu_align_pairs' path;
  * ssw_gpu_timing.win_copied counts their residues.
- * Not provided (yet): a multi-device pool variant, a CLI option, a strand flag per pair (both strands: ssw_gpu_seqs_with_revcomp on the
+ * Several devices, or several workers on one: ssw_gpu_pool_align_windows.
+ * Not provided (yet): a CLI option, a strand flag per pair (both strands: ssw_gpu_seqs_with_revcomp on the
  * reads and qidx = count + i), a wider envelope (queries of 641..768 residues, windows over 65 000 columns on the fast path).
  */
 int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
@@ -213,9 +214,10 @@ int ssw_gpu_align_windows(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const s
  * decreasing cand_off, more than 0x7fffff00 candidates, an index or window out of range (ssw_gpu_align_windows' text), sequences of
  * another context.  ngroups == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for ssw_gpu_align_windows.
  * ssw_gpu_last_timing: reduce_ms is the device time of k_groupbest; best_flagged the winners handed to the reverse pass / traceback.
- * Not provided (yet): a multi-device pool variant, a CLI option, building the survivor list of the
+ * Not provided (yet): a CLI option, building the survivor list of the
  * flagged stage on the device (the winners' records make one round trip to the host), a fast path for reads of 641..768 residues.
- * More than the best two per group: ssw_gpu_align_windows_topk.
+ * More than the best two per group: ssw_gpu_align_windows_topk.  Several devices: ssw_gpu_pool_align_windows_topk with k = 2 (no pool
+ * variant of this entry point: see there).
  */
 typedef struct {
 	int32_t best;          /* position in the candidate list of the group's best eligible candidate; -1: none */
@@ -259,7 +261,8 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * context lock as for ssw_gpu_align_windows.
  * ssw_gpu_last_timing: reduce_ms is the device time of k_grouptopk; best_flagged the reported slots that pass src/ssw.c:916 (all of them
  * unless flag == 2 and score1 < filters) -- the pairs handed to the reverse pass / traceback, never more than ngroups * k, 0 at flag 0.
- * Not provided (yet): a multi-device pool variant, a CLI option, a strand flag per pair, building the survivor list on the device.
+ * Several devices, or several workers on one: ssw_gpu_pool_align_windows_topk.
+ * Not provided (yet): a CLI option, a strand flag per pair, building the survivor list on the device.
  */
 #define SSW_GPU_GROUP_TOPK_MAX 64
 int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
@@ -370,7 +373,44 @@ int ssw_gpu_pool_align(ssw_gpu_pool* pool, const int8_t* qcodes, const int64_t* 
 int ssw_gpu_pool_search_topk(ssw_gpu_pool* pool, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int32_t block,
                              const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t* tidx, ssw_gpu_result* results,
                              uint32_t** cigar_pool, int64_t* cigar_words);
-/* per worker, accumulated over the last ssw_gpu_pool_align: blocks taken, DP cells (readLen x refLen), device milliseconds */
+/*
+ * The window entry points over the pool: ssw_gpu_align_windows and ssw_gpu_align_windows_topk with the pool's resident target set
+ * (ssw_gpu_pool_set_targets, replicated once per worker; tidx / tbeg / tlen index it) and reads that stay on the host, as for
+ * ssw_gpu_pool_align.  with_revcomp != 0: qidx in [nq, 2 nq) names the reverse complement of read qidx - nq, the convention of
+ * ssw_gpu_seqs_with_revcomp -- a worker builds the reverse complements it needs on its device, the caller never does.
+ * Output: bit for bit what ONE context gives for ssw_gpu_align_windows / ssw_gpu_align_windows_topk over all the reads (with_revcomp:
+ * over ssw_gpu_seqs_with_revcomp of them) -- results, pos, n_eligible, cigar_off and the words of the CIGAR pool -- whatever the number
+ * of workers, whichever worker took which block, and whatever `block` is.
+ * Blocks: contiguous ranges, in order, of pairs (align_windows: `block` pairs each) or of WHOLE groups (topk: a block takes groups until
+ * it holds at least `block` candidates; always at least one group; empty groups belong to the block they fall into).  block <= 0: a few
+ * blocks per worker by candidate count, ceil(candidates / (4 x workers)), but at least 16 384 candidates per block -- below that the
+ * host planning of a window call outweighs its kernels.  A worker uploads only the distinct forward reads its block names, in ascending read
+ * index, renumbers the block's qidx to them (forward read j of m is j, its reverse complement m + j; ssw_gpu_seqs_with_revcomp only if
+ * the block names a reverse strand), rebases cand_off to the block and passes the slices of tidx / tbeg / tlen / pos / n_eligible /
+ * results in place.  The blocks' CIGAR pools are concatenated in block order, cigar_off rebased: pair order, or (group, rank) order.
+ * Errors (-1, text in ssw_gpu_pool_last_error; before any worker starts and before any output is written; the pair or group is named
+ * by its index in the CALLER's arrays): a NULL array, no target set, k outside 1..SSW_GPU_GROUP_TOPK_MAX, cand_off[0] != 0 or a
+ * decreasing cand_off, qidx outside [0, nq) -- [0, 2 nq) with with_revcomp --, tidx out of range, tbeg < 0, tlen < 0, a window past the
+ * end of its target.  npairs == 0 / ngroups == 0 return 0 with *cigar_words = 0.  A failure inside a worker stops the hand-out and
+ * reports worker, device and the block's range of pairs or groups.  ssw_gpu_pool_stats: blocks taken, `queries` = distinct reads
+ * uploaded (summed over the blocks), cells, busy milliseconds.
+ * There is no pool variant of ssw_gpu_align_windows_best: ssw_gpu_pool_align_windows_topk answers it -- k = 1 gives `best` and its
+ * record; k = 2 with max_drop < 0 gives `second` in pos[2 g + 1] and second_score1 in results[2 g + 1].score1; n_eligible is returned
+ * as it is.
+ */
+int ssw_gpu_pool_align_windows(ssw_gpu_pool* pool,
+        const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int64_t npairs,
+        int64_t block, const ssw_gpu_params* params,
+        ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
+int ssw_gpu_pool_align_windows_topk(ssw_gpu_pool* pool,
+        const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+        const int64_t* cand_off, int64_t ngroups,
+        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+        int64_t block, const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t max_drop,
+        int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results,
+        uint32_t** cigar_pool, int64_t* cigar_words);
+/* per worker, accumulated over the last pool call: blocks taken, reads uploaded, DP cells (readLen x refLen), device milliseconds */
 typedef struct { int32_t device; int64_t blocks; int64_t queries; int64_t cells; double busy_ms; } ssw_gpu_pool_stat;
 int ssw_gpu_pool_stats(const ssw_gpu_pool* pool, int worker, ssw_gpu_pool_stat* out);
 
