@@ -290,7 +290,24 @@ typedef struct {
 	int32_t* counters;       /* optional: [0] alignments decided under 16-bit rules, [1] under 8-bit rules */
 	int32_t mark_word;       /* records decided under 16-bit rules carry SSW_OUT_WORD in their status */
 	int32_t* err;            /* error word of the call (as ssw_chainx_args.err): raised when the tracked best cell is not the first column of the maximum */
+	/* database mode (res_nt > 0; the jobs hold whole targets, `win` unset): the record of (query q, target t) goes to row q, column t - tfirst
+	   of ONE of three matrices with res_nt columns -- the ones k_filldb fills for the short rows of the same chunk (ssw_filldb_args) */
+	int32_t res_nt, tfirst;
+	struct ssw_hit_rec* db_hits;   /* compact records of the streamed search (ref_end2 = -2 where the reference returns NULL), or ... */
+	struct ssw_out_rec* db_out;    /* ... final-layout records (with mark_word: SSW_OUT_WORD for k_select), or ... */
+	ssw_dres* db_res;              /* ... the records the host converts per sub-batch of targets */
 } ssw_reduce_pairs_args;
+
+/* The job list of the database path's long class, built on the device (k_dbjobs): job g of the launch pairs long query qlist[(first + g) / hp]
+   with itself against the two neighbours tlist[2 p], tlist[2 p + 1] (p = (first + g) % hp, hp = (ntl + 1) / 2) of the chunk's non-empty
+   targets in length order; an odd ntl leaves the last job of a row with an idle high half (qb = -1). */
+typedef struct {
+	const int32_t* qlist;    /* the long queries of one bucket */
+	const int32_t* tlist;    /* non-empty targets of the chunk, sorted by length */
+	int32_t ntl;
+	int64_t first, count;    /* jobs [first, first + count) of the bucket's nq x hp */
+	ssw_pjob* jobs;          /* count entries */
+} ssw_dbjobs_args;
 
 /*
  * literal lane model (k_literal): for gap penalties with gapO <= gapE the reference's answer depends on its striped
@@ -524,6 +541,7 @@ int64_t ssw_shim_capture_lds_need(int R, int n);   /* dynamic LDS of one k_captu
 int ssw_shim_launch_chainx(int R, int capture, const ssw_chainx_args* a, void* stream);
 int ssw_shim_launch_chainq(int R, int capture, const ssw_chainx_args* a, int max_workgroups, void* stream);   /* 64-lane chains behind a work queue; capture 0: fill, 1: window pass, 2: pair mode of the fill */
 int ssw_shim_launch_reduce_pairs(const ssw_reduce_pairs_args* a, void* stream);
+int ssw_shim_launch_dbjobs(const ssw_dbjobs_args* a, void* stream);
 int ssw_shim_chainq_resident(int R, int capture, int n);   /* wavefronts of k_chainq<R> the device holds at once (0: unknown) */
 int ssw_shim_launch_literal(const ssw_literal_args* a, void* stream);
 int ssw_shim_launch_trace(const ssw_trace_args* a, void* stream);

@@ -98,7 +98,7 @@ struct ssw_gpu_ctx {
 	char err[512];
 	pthread_mutex_t mu;                 /* guards the lazily created streams and the error text: ONE other thread may upload sequences while a batch call runs */
 	ssw_gpu_timing tm;
-	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab, wtab, brec, bmap;
+	dbuf mat, pairs, pairs2, qlist, res, cm16, cm8, cm16b, cm8b, scratch, cigar, cigar2, need, goff, gpool, bnd, tlist, cand, tresume, queue, cands, sg16, sg8, qerr, fmtab, wtab, brec, bmap, dbjobs;
 	dbuf sres, svq, svt, scnt;          /* flagged database search: survivor records, their (query, target) maps, counters */
 	dbuf scratch0, need0, list0;        /* traceback: round 0 of the narrow alignments while the wide ones' teams already run (trace_phase "early") */
 	dbuf tk_hits0, tk_hits1, tk_lst;    /* top-K search: the two chunk record buffers, the per-query lists + their state */
@@ -341,7 +341,7 @@ void ssw_gpu_close(ssw_gpu_ctx* c)
 	if (c->stream) ssw_shim_stream_sync(c->stream);
 	for (int i = 0; i < 2; ++i) { ssw_shim_free(c->hits_d[i]); ssw_shim_host_free(c->hits_h[i]); }
 	dbuf_free(&c->mat); dbuf_free(&c->pairs); dbuf_free(&c->qlist); dbuf_free(&c->res); dbuf_free(&c->cm16);
-	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab); dbuf_free(&c->wtab); dbuf_free(&c->brec); dbuf_free(&c->bmap);
+	dbuf_free(&c->cm8); dbuf_free(&c->cm16b); dbuf_free(&c->cm8b); dbuf_free(&c->cigar2); dbuf_free(&c->scratch); dbuf_free(&c->cigar); dbuf_free(&c->need); dbuf_free(&c->goff); dbuf_free(&c->gpool); dbuf_free(&c->bnd); dbuf_free(&c->tlist); dbuf_free(&c->pairs2); dbuf_free(&c->cand); dbuf_free(&c->tresume); dbuf_free(&c->queue); dbuf_free(&c->cands); dbuf_free(&c->sg16); dbuf_free(&c->sg8); dbuf_free(&c->qerr); dbuf_free(&c->fmtab); dbuf_free(&c->wtab); dbuf_free(&c->brec); dbuf_free(&c->bmap); dbuf_free(&c->dbjobs);
 	dbuf_free(&c->sres); dbuf_free(&c->svq); dbuf_free(&c->svt); dbuf_free(&c->scnt);
 	dbuf_free(&c->scratch0); dbuf_free(&c->need0); dbuf_free(&c->list0);
 	dbuf_free(&c->tk_hits0); dbuf_free(&c->tk_hits1); dbuf_free(&c->tk_lst);
@@ -657,6 +657,7 @@ static void timing_add(call_acc* acc, const ssw_gpu_timing* t)
 	a->fill_ms += t->fill_ms; a->fill_launches += t->fill_launches; a->fill_cells += t->fill_cells; a->cells += t->cells;
 	a->reduce_ms += t->reduce_ms; a->locate_ms += t->locate_ms; a->trace_ms += t->trace_ms; a->n_word += t->n_word; a->n_byte += t->n_byte;
 	a->db_repeats += t->db_repeats; a->fill_pipelined += t->fill_pipelined; a->win_copied += t->win_copied;
+	a->db_long_pairs += t->db_long_pairs;
 	if (t->fill_cells > acc->best_cells) {
 		acc->best_cells = t->fill_cells;
 		memcpy(a->fill_kernel, t->fill_kernel, sizeof a->fill_kernel);
@@ -887,9 +888,90 @@ typedef struct {
 static int dbx_chunk(ssw_gpu_ctx* c, dbx_state* dx, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm, const bucket* bk, int nb,
                      const int8_t* d_mat, struct ssw_out_rec* d_out, int32_t tbase, int32_t nt);
 
+/* scratch of ONE job of the strip kernel's pair mode against a target of tl columns: two rows of column maxima, the boundary records of the
+   strip hand-off, queue flag + best-cell record per strip, the job's best cells and its two records */
+static int64_t plong_cm_stride(int64_t tl) { return (tl + 15) / 16 * 16 + 16; }
+static int64_t plong_bnd_cols(int64_t tl) { return (tl + 31) / 16 * 16; }
+static int64_t plong_job_bytes(int64_t tl, int32_t strips)
+{
+	return 8 * plong_cm_stride(tl) + 16 * plong_bnd_cols(tl) + 36 * (int64_t)strips + 32 + 2 * (int64_t)sizeof(ssw_gpu_result);
+}
+
+/* The long class of the database path: queries above k_filldb's classes (641 residues and more; 385 and more where the alphabet keeps the
+   classes of 25..40 rows per lane out) on the strip kernel's pair mode.  A job is (q, ta, q, tb): BOTH halves of a register hold the same
+   query, against two neighbours of the chunk's length-sorted targets -- the partner of identical padded length that jobs of several strips
+   need is the query itself.  k_dbjobs writes the jobs of a launch on the device, k_reduce_pairs (database mode) stores the records in the
+   chunk's matrix beside k_filldb's.  qdone[q] == 2 marks the class's queries. */
+#define PJ_LONG_MAX 65535      /* longest query of the pair mode, here and on the pair path */
+typedef struct {
+	int nlb;
+	bucket* b;                            /* [nlb] strip shapes (win_bucket_shape); first_q / nq: the bucket's slice of the call's bucket-ordered query list */
+	int64_t* cells;                       /* [nlb] cells evaluated, summed over the chunks */
+	int* form;                            /* [nlb] 3: column frame, 0: plain int16 */
+	const int32_t* d_order;               /* that list on the device */
+	int32_t maxmat, minmat;
+} dbl_class;
+
+/* one chunk's launches of the long class, on the main stream: nz non-empty targets d_tl (host copy tl) in length order */
+static int dbl_chunk(ssw_gpu_ctx* c, dbl_class* dl, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const ssw_gpu_params* prm, const int8_t* d_mat, int32_t bias,
+                     int32_t maxtlen, const int32_t* d_tl, const int32_t* tl, int32_t nz, int32_t tfirst, int32_t res_nt,
+                     ssw_dres* d_res, struct ssw_out_rec* d_out, struct ssw_hit_rec* d_hits, int32_t* d_cnt, int mark_word)
+{
+	const int32_t n = prm->n;
+	const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
+	const int64_t hp = ((int64_t)nz + 1) / 2;
+	const int64_t stride = plong_cm_stride(maxtlen), bcols = plong_bnd_cols(maxtlen);
+	int64_t colsum = 0;      /* columns a row of jobs walks: the longer target of every job (sorted: the second one) */
+	for (int64_t p = 0; p < hp; ++p) { const int32_t t = tl[2 * p + 1 < nz ? 2 * p + 1 : 2 * p]; colsum += T->h_off[t + 1] - T->h_off[t]; }
+	for (int b = 0; b < dl->nlb; ++b) {
+		const bucket* B = &dl->b[b];
+		const int64_t total = (int64_t)B->nq * hp;
+		int64_t jpl = (int64_t)(c->cm_budget / 2) / plong_job_bytes(maxtlen, B->strips);      /* (>= 1: the class's gate) */
+		if (jpl < 1) jpl = 1;
+		if (jpl > total) jpl = total;
+		if (jpl * B->strips > 0x7ffffff0 / 2) jpl = 0x7ffffff0 / 2 / B->strips;
+		uint32_t* d_cm16 = (uint32_t*)ensure(c, &c->cm16, (size_t)(4 * stride * jpl));
+		uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
+		uint32_t* d_bnd = (uint32_t*)ensure(c, &c->bnd, (size_t)(16 * bcols * jpl));
+		int32_t* d_cand = (int32_t*)ensure(c, &c->cand, (size_t)(32 * jpl));
+		ssw_pjob* d_jobs = (ssw_pjob*)ensure(c, &c->dbjobs, sizeof(ssw_pjob) * (size_t)jpl);
+		if (!d_cm16 || !d_cm8 || !d_bnd || !d_cand || !d_jobs) return -1;
+		int32_t fr_base = 0, fr_kmask = 0;
+		const int xform = !c->kn.fill_plain && !c->kn.db_plain &&
+		                  ssw_frame_params(&c->kn, (int64_t)B->P16 * (dl->maxmat > 0 ? dl->maxmat : 0), prm->gapO, prm->gapE, dl->minmat, 64, &fr_base, &fr_kmask) ? 3 : 0;
+		dl->form[b] = xform;
+		const int qgrid = chainq_grid(c, B->R, 1, n);      /* (the window pass's occupancy, as the pair path's long class: the same LDS footprint) */
+		for (int64_t a0 = 0; a0 < total; a0 += jpl) {
+			const int64_t nl = total - a0 < jpl ? total - a0 : jpl;
+			ssw_dbjobs_args ja; memset(&ja, 0, sizeof ja);
+			ja.qlist = dl->d_order + B->first_q; ja.tlist = d_tl; ja.ntl = nz; ja.first = a0; ja.count = nl; ja.jobs = d_jobs;
+			if (ssw_shim_launch_dbjobs(&ja, c->stream)) return fail(c, "job list launch failed: %s", ssw_shim_last_error());
+			ssw_chainx_args xa; memset(&xa, 0, sizeof xa);
+			xa.qcodes = Q->d_codes; xa.qoff = Q->d_off; xa.mat = d_mat; xa.n = n; xa.gapO2 = gapO2; xa.gapE2 = gapE2; xa.gapE = prm->gapE; xa.maxmat = dl->maxmat;
+			xa.njobs = (int32_t)nl; xa.pjobs = d_jobs; xa.vm.tcodes = T->d_codes; xa.vm.toff = T->d_off;
+			xa.ntiles = 1; xa.cm16 = d_cm16; xa.cm8 = d_cm8; xa.cm_stride = stride; xa.bnd = d_bnd; xa.bnd_stride = bcols; xa.cand = d_cand; xa.lanes = 64;
+			if (chainq_prepare(c, &xa, B->strips, nl, qgrid)) return -1;
+			xa.form = xform; xa.fr_base = fr_base; xa.fr_kmask = fr_kmask; xa.tail_R = B->tailR;
+			if (c->kn.debug) fprintf(stderr, "[ssw_gpu] database search, long class: R %d (last strip %d), %lld jobs x %d strips, %d wavefronts, %s tickets, form %d\n",
+			                                     B->R, B->tailR ? B->tailR : B->R, (long long)nl, B->strips, qgrid, xa.whole_jobs ? "job" : "strip", xa.form);
+			if (ssw_shim_launch_chainq(B->R, 2, &xa, qgrid, c->stream)) return fail(c, "fill launch failed: %s", ssw_shim_last_error());
+			ssw_reduce_pairs_args ra; memset(&ra, 0, sizeof ra);
+			ra.jobs = d_jobs; ra.njobs = xa.njobs; ra.qoff = Q->d_off; ra.toff = T->d_off; ra.cm16 = d_cm16; ra.cm8 = d_cm8; ra.cm_stride = stride;
+			ra.cand = d_cand; ra.maskLen = prm->maskLen; ra.bias = bias; ra.score_size = prm->score_size; ra.counters = d_cnt; ra.mark_word = mark_word; ra.err = xa.err;
+			ra.res_nt = res_nt; ra.tfirst = tfirst; ra.db_hits = d_hits; ra.db_out = d_hits ? 0 : d_out; ra.db_res = d_hits || d_out ? 0 : d_res;
+			if (ssw_shim_launch_reduce_pairs(&ra, c->stream)) return fail(c, "reduce launch failed: %s", ssw_shim_last_error());
+		}
+		const int64_t rows = (int64_t)64 * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips);
+		const int64_t bcells = rows * 2 * colsum * B->nq;
+		c->tm.fill_cells += bcells; dl->cells[b] += bcells;
+		c->tm.db_long_pairs += (int64_t)B->nq * nz;
+	}
+	return 0;
+}
+
 static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, int32_t tfirst, int32_t tcount,
                     const ssw_gpu_params* prm, ssw_gpu_result* results, const bucket* bk, int nb, const ssw_pair* d_pairs,
-                    const int8_t* d_mat, int32_t bias, int32_t maxtlen, const uint8_t* qdone, db_stream* ds, dbx_state* dx)
+                    const int8_t* d_mat, int32_t bias, int32_t maxtlen, const uint8_t* qdone, db_stream* ds, dbx_state* dx, dbl_class* dl)
 {
 	const int32_t nq = Q->count, n = prm->n;
 	const uint32_t gapO2 = (uint32_t)prm->gapO * 0x10001u, gapE2 = (uint32_t)prm->gapE * 0x10001u;
@@ -906,13 +988,13 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 	ssw_pair* midpairs = 0; const ssw_pair* d_midpairs = 0;
 	{
 		int32_t nm = 0;
-		for (int32_t q = 0; q < nq; ++q) if (qdone[q]) { const int64_t L = Q->h_off[q + 1] - Q->h_off[q]; if (L > 16 * SSW_RMAX && L <= 640) ++nm; }
+		for (int32_t q = 0; q < nq; ++q) if (qdone[q] == 1) { const int64_t L = Q->h_off[q + 1] - Q->h_off[q]; if (L > 16 * SSW_RMAX && L <= 640) ++nm; }
 		if (nm > 0) {
 			keyed* mk = (keyed*)malloc(sizeof(keyed) * (size_t)nm);
 			midpairs = (ssw_pair*)malloc(sizeof(ssw_pair) * (size_t)nm);
 			if (!mk || !midpairs) { free(mk); free(midpairs); free(tk); free(tl_all); return fail(c, "out of host memory%s", ""); }
 			int32_t k = 0, np = 0;
-			for (int32_t q = 0; q < nq; ++q) if (qdone[q]) { const int64_t L = Q->h_off[q + 1] - Q->h_off[q]; if (L > 16 * SSW_RMAX && L <= 640) { mk[k].key = (int32_t)L; mk[k].sub = 0; mk[k].q = q; ++k; } }
+			for (int32_t q = 0; q < nq; ++q) if (qdone[q] == 1) { const int64_t L = Q->h_off[q + 1] - Q->h_off[q]; if (L > 16 * SSW_RMAX && L <= 640) { mk[k].key = (int32_t)L; mk[k].sub = 0; mk[k].q = q; ++k; } }
 			qsort(mk, (size_t)nm, sizeof(keyed), keyed_cmp);
 			for (int cls = SSW_RMAX + 1; cls <= 40; ++cls) {
 				bucket b; b.tailR = 0; b.R = cls; b.strips = 1; b.P16 = 16 * cls; b.lanes = 16; b.use_x = 0; b.first_pair = np; b.first_q = 0; b.nq = 0;
@@ -1058,8 +1140,11 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 					fail(c, "stream join failed: %s", ssw_shim_last_error()); goto done;
 				}
 		}
+		/* the long class follows on the main stream (its scratch is k_filldb's, free again after the join above): records into the same matrix */
+		const int has_long = dl && dl->nlb > 0;
+		if (nz > 0 && has_long && dbl_chunk(c, dl, Q, T, prm, d_mat, bias, maxtlen, d_tl, tl, nz, tfirst + t0, nt, d_res, d_out, d_hits, d_cnt, dx != 0)) goto done;
 		ssw_shim_event_record(e1, c->stream);
-		c->tm.fill_launches++;      /* one launch group: all size classes of this chunk of targets */
+		c->tm.fill_launches++;      /* one launch group: all size classes of this chunk of targets, the long class's launches among them */
 		if (ds && ds->sel) {      /* select mode: k_topk on the second stream after this chunk's fill, while the next chunk is computed */
 			topk_sel* s = ds->sel;
 			s->a.hits = d_hits; s->a.nt = nt; s->a.tfirst = tfirst + t0;
@@ -1147,6 +1232,14 @@ static int align_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T
 			char nm[48];
 			snprintf(nm, sizeof nm, "k_filldb<%d,%s>", B->R, db_form[b] ? "frame" : "int16+max3");
 			note_fill_kernel(c, db_cells[b], &bestc, nm, db_form[b] ? 6.5 : 8.5, B->R, 1);
+		}
+		for (int b = 0; dl && b < dl->nlb; ++b) {      /* (named as the pair path names its long class) */
+			const bucket* B = &dl->b[b];
+			char nm[48];
+			const int nlen = B->tailR ? snprintf(nm, sizeof nm, "k_chainq<%d,pairs,%s> x %d strips + 1 of %d", B->R, dl->form[b] == 3 ? "frame" : "int16", B->strips - 1, B->tailR)
+			                          : snprintf(nm, sizeof nm, "k_chainq<%d,pairs,%s> x %d strips", B->R, dl->form[b] == 3 ? "frame" : "int16", B->strips);
+			if (nlen >= (int)sizeof nm && c->kn.debug) fprintf(stderr, "[ssw_gpu] fill kernel name cut to %d characters\n", (int)sizeof nm - 1);
+			note_fill_kernel(c, dl->cells[b], &bestc, nm, dl->form[b] == 3 ? 6.5 : 9.0, B->R, B->strips);
 		}
 	}
 	if (ds && prev_t0 >= 0) {     /* the last chunk */
@@ -1937,18 +2030,36 @@ static void batch_totals(ssw_gpu_ctx* c, batch_call* bc, uint32_t** cigar_pool, 
 	if (cigar_words) *cigar_words = bc->pool.n;
 }
 
-/* database search: several short targets -> fused kernel for the short-query buckets (scores only, or flagged: db_gate).
+/* database search: several short targets -> fused kernel for the short-query buckets (scores only, or flagged: db_gate), the strip
+   kernel's pair mode for the buckets above them (dbl_class).
    Returns 0: go on with the generic path (for the queries not marked in qdone), 1: the call is answered, SSW_NOT_STREAMABLE, -1: error. */
 static int batch_try_db(ssw_gpu_ctx* c, batch_call* bc, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words, db_stream* ds)
 {
 	const ssw_gpu_seqs* Q = bc->Q;
 	const int32_t n = bc->n;
 	const int mid_ok = (int64_t)n * 10 * 256 <= 65535;     /* 40 rows per lane: 10 chunks of 256 bytes per residue; n x that must stay a 16-bit offset */
+	/* buckets above k_filldb's classes: the long class (dbl_class) takes those whose job fits the scratch rule of the pair path's long class;
+	   the others (any_long) stay on the per-target loop */
+	dbl_class* dl = 0;
+	const int dbl_ok = !bc->literal && bc->may_db && bc->geom.xlanes == 64 && bc->geom.xrmax <= 16;
 	int any_short = 0, any_long = 0;
-	for (int b = 0; b < bc->nb; ++b) { if (bc->bk[b].use_x && (bc->bk[b].P16 > 640 || !mid_ok)) any_long = 1; else any_short = 1; }
-	const int db_ok = !bc->literal && any_short && bc->may_db;
-	if (ds && (!db_ok || any_long)) return SSW_NOT_STREAMABLE;
-	if (!db_ok) return 0;
+	for (int b = 0; b < bc->nb; ++b) {
+		const bucket* B = &bc->bk[b];
+		if (!(B->use_x && (B->P16 > 640 || !mid_ok))) { any_short = 1; continue; }
+		int32_t lmax = 0;
+		for (int32_t k = 0; k < B->nq; ++k) { const int32_t qq = bc->order[B->first_q + k]; const int64_t L = Q->h_off[qq + 1] - Q->h_off[qq]; if (L > lmax) lmax = (int32_t)(L > 0x7fffffff ? 0x7fffffff : L); }
+		if (!dbl_ok || lmax > PJ_LONG_MAX || B->R > 16 || plong_job_bytes(bc->maxt, B->strips) > (int64_t)(c->cm_budget / 2)) { any_long = 1; continue; }
+		if (!dl) {      /* one block: the record, then room for every bucket of the call (queries of several strips: a bucket per padded length) */
+			dl = (dbl_class*)calloc(1, sizeof *dl + (sizeof(bucket) + sizeof(int64_t) + sizeof(int)) * (size_t)bc->nb);
+			if (!dl) return fail(c, "out of host memory%s", "");
+			dl->cells = (int64_t*)(dl + 1); dl->b = (bucket*)(dl->cells + bc->nb); dl->form = (int*)(dl->b + bc->nb);
+		}
+		dl->b[dl->nlb++] = *B;
+	}
+	const int db_ok = !bc->literal && (any_short || dl) && bc->may_db;
+	if (ds && (!db_ok || any_long)) { free(dl); return SSW_NOT_STREAMABLE; }
+	if (!db_ok) { free(dl); return 0; }
+	if (dl) { dl->d_order = bc->d_qlist; dl->maxmat = bc->maxmat; dl->minmat = bc->minmat; }
 	dbx_state dxs; memset(&dxs, 0, sizeof dxs);
 	if (bc->use_dbx) {
 		dxs.order = bc->order; dxs.nqa = bc->nqa; dxs.d_order = bc->d_qlist; dxs.maxmat = bc->maxmat; dxs.minmat = bc->minmat; dxs.maxt = (int32_t)bc->maxt;
@@ -1959,10 +2070,17 @@ static int batch_try_db(ssw_gpu_ctx* c, batch_call* bc, ssw_gpu_result* results,
 		bc->qdone[qq] = 1;
 		if (Q->h_off[qq + 1] - Q->h_off[qq] > dxs.maxlen) dxs.maxlen = (int32_t)(Q->h_off[qq + 1] - Q->h_off[qq]);
 	}
+	for (int b = 0; dl && b < dl->nlb; ++b) for (int32_t k = 0; k < dl->b[b].nq; ++k) {
+		const int32_t qq = bc->order[dl->b[b].first_q + k];
+		bc->qdone[qq] = 2;
+		if (Q->h_off[qq + 1] - Q->h_off[qq] > dxs.maxlen) dxs.maxlen = (int32_t)(Q->h_off[qq + 1] - Q->h_off[qq]);
+	}
 	for (int32_t q = 0; q < bc->nq; ++q) if (Q->h_off[q + 1] == Q->h_off[q]) bc->qdone[q] = 1;     /* empty queries: empty records, written there */
-	const int db_rc = align_db(c, Q, bc->T, bc->tfirst, bc->tcount, bc->prm, results, bc->bk, bc->nb, bc->d_pairs, bc->d_mat, bc->bias, (int32_t)bc->maxt, bc->qdone, ds,
-	                           bc->use_dbx ? &dxs : 0);
+	int db_rc = align_db(c, Q, bc->T, bc->tfirst, bc->tcount, bc->prm, results, bc->bk, bc->nb, bc->d_pairs, bc->d_mat, bc->bias, (int32_t)bc->maxt, bc->qdone, ds,
+	                     bc->use_dbx ? &dxs : 0, dl);
 	free(dxs.hs); free(dxs.hvq); free(dxs.hvt); free(dxs.hpo);      /* (the survivors' host copies were patched into the records inside) */
+	if (!db_rc && dl && !(ds && ds->fn_rc)) db_rc = chainq_check(c);      /* (the long class ran behind the work queue) */
+	free(dl);
 	if (db_rc) return -1;
 	bc->d_res = (ssw_dres*)ensure(c, &c->res, sizeof(ssw_dres) * (size_t)bc->nq);   /* align_db may have regrown the record buffer */
 	if (!bc->d_res) return -1;
@@ -2728,8 +2846,8 @@ int ssw_gpu_search_db(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (c->hits_cap < bytes) rc = fail(c, "search_db: buffer allocation failed: %s", ssw_shim_last_error());
 		else rc = align_batch_locked(c, Q, T, 0, nt_all, prm, 0, 0, 0, &ds);
 		if (rc == SSW_NOT_STREAMABLE) {
-			/* generic path (queries above 640 residues, matrices with entries above 49, gapO <= gapE, ...): full records per chunk,
-			   converted on the host -- same values, no overlap */
+			/* generic path (matrices with entries above 49, gapO <= gapE, wide alphabets, targets over 65 000 columns, a long query whose job
+			   does not fit the scratch rule of the long class): full records per chunk, converted on the host -- same values, no overlap */
 			ssw_gpu_result* full = (ssw_gpu_result*)ssw_shim_host_alloc(sizeof(ssw_gpu_result) * (size_t)nq * (size_t)chunk);
 			rc = full ? 0 : fail(c, "search_db: buffer allocation failed: %s", ssw_shim_last_error());
 			for (int32_t t0 = 0; rc == 0 && t0 < nt_all; t0 += (int32_t)chunk) {
@@ -2778,7 +2896,6 @@ static inline int32_t ps_tid(const pair_src* s, int64_t i) { return s->tbeg ? (i
 #define PJ_KEY_FALLBACK 0xffffffffu
 #define PJ_KEY_LONG 0xfffffffeu      /* the strip kernel's pair mode (queries of 769 residues and more) */
 #define PJ_LONG_MIN 769
-#define PJ_LONG_MAX 65535
 
 /* a pair of the long class on its way into jobs: sorted by bucket key, then query length, then target length (the two halves of a job and
    the jobs of a launch finish together), then position */
@@ -2793,14 +2910,7 @@ static int plong_cmp(const void* a, const void* b)
 }
 /* jobs [j0, j0 + jn) of the long class share the strip shape b; maxt: their longest target */
 typedef struct { bucket b; int64_t j0, jn, maxt; } plong_bucket;
-/* scratch of ONE job of the pair mode against a target of tl columns: two rows of column maxima, the boundary records of the strip
-   hand-off, queue flag + best-cell record per strip, the job's best cells and its two records */
-static int64_t plong_cm_stride(int64_t tl) { return (tl + 15) / 16 * 16 + 16; }
-static int64_t plong_bnd_cols(int64_t tl) { return (tl + 31) / 16 * 16; }
-static int64_t plong_job_bytes(int64_t tl, int32_t strips)
-{
-	return 8 * plong_cm_stride(tl) + 16 * plong_bnd_cols(tl) + 36 * (int64_t)strips + 32 + 2 * (int64_t)sizeof(ssw_gpu_result);
-}
+/* (scratch of one job: plong_job_bytes, above the database path, which cuts its long class by the same rule) */
 
 static double wall_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 

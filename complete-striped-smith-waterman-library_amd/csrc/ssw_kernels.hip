@@ -1663,9 +1663,39 @@ __global__ void __launch_bounds__(256) k_reduce_pairs(ssw_reduce_pairs_args a)
 		if (tid == 0) {
 			const int32_t* cd = a.cand + ((int64_t)job * 2 + h) * 4;
 			if (bv > 0 && (cd[0] != bv || cd[1] != bc)) atomicAdd(a.err, 1);      /* one tile, no halo: the tracked cell IS the first column of the maximum */
-			pj_emit(a.out + 2 * (int64_t)job + h, a.counters, a.mark_word, pr.status, pr.word, bv, bc, cd[2], len, pr.maskLen, s2, i2);
+			if (a.res_nt <= 0) { pj_emit(a.out + 2 * (int64_t)job + h, a.counters, a.mark_word, pr.status, pr.word, bv, bc, cd[2], len, pr.maskLen, s2, i2); continue; }
+			/* database mode: the same record, stored at (q, t) of the chunk's matrix in the layout the call asked for */
+			const int64_t at = (int64_t)q * a.res_nt + (t - a.tfirst);
+			if (a.db_out) { pj_emit(a.db_out + at, a.counters, a.mark_word, pr.status, pr.word, bv, bc, cd[2], len, pr.maskLen, s2, i2); continue; }
+			ssw_out_rec o;
+			pj_emit(&o, a.counters, 0, pr.status, pr.word, bv, bc, cd[2], len, pr.maskLen, s2, i2);
+			if (a.db_hits) {
+				ssw_hit_rec hr;
+				hr.score1 = o.score1; hr.score2 = o.score2; hr.ref_end1 = o.ref_end1; hr.read_end1 = o.read_end1; hr.ref_end2 = o.status == 1 ? -2 : o.ref_end2;
+				a.db_hits[at] = hr;
+			} else {
+				ssw_dres r;
+				r.score1 = o.score1; r.score2 = o.score2; r.ref_begin1 = -1; r.ref_end1 = o.ref_end1; r.read_begin1 = -1; r.read_end1 = o.read_end1;
+				r.ref_end2 = o.ref_end2; r.cigarLen = 0; r.flag = 0; r.status = o.status; r.word = pr.word; r.want_begin = 0; r.want_cigar = 0;
+				r.rev_score = 0; r.loc_done = 0; r.nm = 0; r.cigar_off = 0;
+				a.db_res[at] = r;
+			}
 		}
 	}
+}
+
+/* k_dbjobs (ssw_dbjobs_args): the pair-mode jobs of the database path's long class -- one thread per job, one 16-byte store; the host
+   uploads the bucket's queries and the chunk's sorted targets and nothing per pair */
+__global__ void __launch_bounds__(256) k_dbjobs(ssw_dbjobs_args a)
+{
+	const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (g >= a.count) return;
+	const int64_t hp = ((int64_t)a.ntl + 1) / 2, lin = a.first + g, k = lin / hp, p = lin - k * hp;
+	const bool both = 2 * p + 1 < a.ntl;
+	ssw_pjob j;
+	j.qa = a.qlist[k]; j.ta = a.tlist[2 * p];
+	j.qb = both ? j.qa : -1; j.tb = both ? a.tlist[2 * p + 1] : j.ta;
+	a.jobs[g] = j;
 }
 
 /* ================================================================================================
@@ -4596,7 +4626,17 @@ extern "C" int ssw_shim_launch_reduce_pairs(const ssw_reduce_pairs_args* a, void
 {
 	ssw_reduce_pairs_args args = *a;
 	if (args.njobs <= 0) return 0;
+	if (args.res_nt > 0 && (args.win || !args.toff || !(args.db_hits || args.db_out || args.db_res))) return -2;
 	SSW_LAUNCH(k_reduce_pairs, ssw_reduce_pairs_args, args, args.njobs, 256, 256 * 8, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_dbjobs(const ssw_dbjobs_args* a, void* stream)
+{
+	ssw_dbjobs_args args = *a;
+	if (args.count <= 0) return 0;
+	if (args.ntl <= 0 || args.first < 0) return -2;
+	SSW_LAUNCH(k_dbjobs, ssw_dbjobs_args, args, (args.count + 255) / 256, 256, 0, stream);
 	return SSW_LAUNCH_OK();
 }
 

@@ -90,6 +90,9 @@ typedef struct {
 	int64_t best_flagged;  /* ssw_gpu_align_windows_best: pairs the call handed to the reverse pass and the traceback -- the winners, never more than ngroups
 	                          (ssw_gpu_align_windows_topk: the reported slots that pass src/ssw.c:916, never more than ngroups * k);
 	                          0 with flag 0 and for the other entry points */
+	int64_t db_long_pairs; /* database search (ssw_gpu_align_batch against four or more targets, ssw_gpu_search_db, ssw_gpu_search_topk): the (query, target)
+	                          pairs answered by the long class of the database path -- queries above k_filldb's 640 residues on the strip kernel's pair
+	                          mode, two targets per job; 0 when there are none and for the other entry points */
 	/* new fields are only ever appended here; ssw_gpu_last_timing_sized lets a caller built against an older header keep its layout */
 } ssw_gpu_timing;
 
@@ -123,6 +126,11 @@ int32_t ssw_gpu_seqs_count(const ssw_gpu_seqs* s);
  * fused kernel; with flag != 0 the pairs that pass the reference's gates (src/ssw.c:916: not when flag == 2 and score1 < filters) go
  * through one batched reverse pass and traceback -- the loop of src/main.c:493-506 without a per-target iteration.  Queries of mixed
  * lengths run side by side.  A call with one query and one target is what ssw_align is made of.
+ * Envelope of the database search: gapO > gapE, n <= 32, max(mat) <= 49, targets of at most 65 000 columns.  Queries of 1..640 residues
+ * (1..384 where n x 10 x 256 > 65 535, i.e. n >= 26) run on k_filldb; longer ones, up to 65 535 residues, on the strip kernel's pair mode
+ * (both halves of a register hold the same query, against two targets of neighbouring length; ssw_gpu_timing.db_long_pairs counts these
+ * pairs), as long as one job's scratch -- about 24 bytes per column of the longest target -- fits half of ssw_gpu_get_budget.  Rows
+ * outside the envelope are answered exactly by a loop over the targets: one round trip per target.
  */
 int ssw_gpu_align_batch(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
                         int32_t target_first, int32_t target_count, const ssw_gpu_params* params,
@@ -302,6 +310,11 @@ size_t ssw_gpu_get_budget(const ssw_gpu_ctx* ctx);
  * chunk `fn` receives the compact records hits[q * target_count + t] of targets [target_first, target_first + target_count)
  * (valid only during the call) while the device already works on the next chunk.  fn returns 0 to go on, non-zero to stop
  * (ssw_gpu_search_db then returns that value).  params->flag must be 0.
+ * Streamed (chunk i + 1 is filled while chunk i is downloaded and handed to fn) inside the database search's envelope as described at
+ * ssw_gpu_align_batch: short queries on k_filldb and queries of up to 65 535 residues on the strip kernel's pair mode write one chunk
+ * matrix.  NOT streamed -- every chunk then produces full records that are converted on the host, same values, no overlap -- with
+ * gapO <= gapE, more than 32 letters, max(mat) > 49, a target over 65 000 columns, or a query above 640 residues (384 for n >= 26) whose
+ * job does not fit half of ssw_gpu_get_budget (a longest target of roughly budget / 48 columns and more).
  */
 typedef struct {
 	uint16_t score1;     /* as s_align */
@@ -326,9 +339,11 @@ int ssw_gpu_search_db(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_g
  * targets_per_chunk: 0 = 2048, as ssw_gpu_search_db (the answer does not depend on it).  k outside 1..SSW_GPU_TOPK_MAX, a NULL tidx /
  * results / params or sequences of another context return -1 with a message before anything is launched or written; nq == 0 returns 0;
  * nt == 0 fills every slot with padding.  Every phase stays within ssw_gpu_get_budget(ctx).
- * Inside the fused database search's envelope (queries up to 640 residues, n <= 32, max(mat) <= 49, gapO > gapE) the selection runs on the
- * device (k_topk, one launch per chunk of targets, beside the next chunk's fill), and the lists come to the host once; elsewhere the chunks'
- * full records are selected on the host -- exact, slower.  With flag != 0 the selected pairs then go through the ssw_gpu_align_pairs path.
+ * Inside the database search's envelope (n <= 32, max(mat) <= 49, gapO > gapE, targets up to 65 000 columns; queries of any length up to
+ * 65 535 residues -- those above 640, or above 384 for n >= 26, on the strip kernel's pair mode as described at ssw_gpu_align_batch) the
+ * selection runs on the device (k_topk, one launch per chunk of targets, beside the next chunk's fill), and the lists come to the host
+ * once; elsewhere the chunks' full records are selected on the host -- exact, slower.  With flag != 0 the selected pairs then go through
+ * the ssw_gpu_align_pairs path (whose own fast paths leave queries of 641..768 residues out).
  * ssw_gpu_last_timing: reduce_ms is the device time of the k_topk selection launches (the other fields as for the search and the pairs).
  */
 #define SSW_GPU_TOPK_MAX 1024
