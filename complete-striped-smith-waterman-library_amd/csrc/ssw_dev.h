@@ -456,6 +456,34 @@ typedef struct {
 	struct ssw_out_rec* out;     /* [ngroups][k]: the ranked candidates' records as the fill wrote them (SSW_OUT_WORD kept) */
 } ssw_grouptopk_args;
 
+/* Best candidate pair per read pair (ssw_gpu_align_windows_mates): k_groupbest's inputs and eligibility over 2 * nfrag groups -- group 2 f
+   holds the candidates of mate 1 of fragment f, group 2 f + 1 those of mate 2 -- and a side table per candidate, uploaded by the host:
+   the window's first column, its target, and the read's length with the strand in bit 31.  From these and the fill record a candidate has
+   E = tbeg + ref_end1 (last column, target coordinates) and B = E - len + 1 (estimated first column, never clamped), both 64-bit.
+   A combination (a of mate 1, b of mate 2) is PROPER when both lie on one target, on opposite strands, and the plus-strand one's B and the
+   minus-strand one's E span min_insert .. max_insert columns; its score is score1(a) + score1(b), less unpaired_penalty unless proper.
+   Order: that score descending, then position of a, then position of b ascending. */
+struct ssw_mate_rec {        /* byte-for-byte the layout of ssw_gpu_mates (include/ssw_gpu.h) */
+	int32_t pos1, pos2, n_eligible1, n_eligible2, score, second_score, n_proper;
+	uint16_t proper, pad;
+};
+#define SSW_MATES_GROUP_MAX 4096      /* SSW_GPU_MATES_GROUP_MAX: pos1 * n2 + pos2 stays below 2^24 */
+typedef struct {
+	const struct ssw_out_rec* rec;
+	const int32_t* slot;         /* candidate -> index into rec */
+	const int64_t* cand_off;     /* 2 * nfrag + 1 */
+	const int64_t* tbeg;         /* per candidate: first column of its window */
+	const int32_t* tidx;         /* ... the target of the window */
+	const uint32_t* len_strand;  /* ... length of its query | minus strand << 31 */
+	int64_t nfrag;
+	int32_t min_score;
+	int32_t min_insert, max_insert;
+	int32_t unpaired_penalty;    /* 0 .. 65535 */
+	struct ssw_mate_rec* sel;    /* [nfrag] */
+	struct ssw_out_rec* out;     /* [2 * nfrag]: the chosen candidates' records as the fill wrote them (SSW_OUT_WORD kept), the record of an
+	                                empty target where a mate has none */
+} ssw_matebest_args;
+
 /* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
 typedef struct {
 	const int8_t* src;
@@ -557,6 +585,7 @@ int ssw_shim_launch_wintab(const ssw_wintab_args* a, void* stream);
 int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefront per query */
 int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream);   /* one DPP row of 16 lanes per group */
 int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stream);   /* the same geometry, k ranks per group */
+int ssw_shim_launch_matebest(const ssw_matebest_args* a, void* stream);     /* one DPP row of 16 lanes per fragment (two groups) */
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

@@ -27,6 +27,8 @@
 #include "ssw_dev.h"
 
 _Static_assert(sizeof(struct ssw_out_rec) == sizeof(ssw_gpu_result), "device record layout must equal ssw_gpu_result");
+_Static_assert(sizeof(struct ssw_mate_rec) == sizeof(ssw_gpu_mates) && sizeof(ssw_gpu_mates) == 32, "device selection layout must equal ssw_gpu_mates");
+_Static_assert(SSW_MATES_GROUP_MAX == SSW_GPU_MATES_GROUP_MAX, "the kernel's group limit is the header's");
 _Static_assert(sizeof(struct ssw_best_rec) == sizeof(ssw_gpu_best) && sizeof(ssw_gpu_best) == 16, "device record layout must equal ssw_gpu_best");
 
 struct _profile {
@@ -3085,12 +3087,15 @@ static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu
 
 /* select mode of the pair list: the pairs are candidates in groups.  ssw_gpu_align_windows_best (k == 0): `results` has one record per
    GROUP, `sel` the selections.  ssw_gpu_align_windows_topk (k >= 1): `results` has k records per group, slot g * k + r for rank r, `pos`
-   their positions in the group and `n_eligible` one count per group */
+   their positions in the group and `n_eligible` one count per group.  ssw_gpu_align_windows_mates (`mates`, k == 0): groups 2 f and 2 f + 1
+   are the two mates of fragment f, `results` has one record per group, `mates` one selection per FRAGMENT */
 typedef struct {
 	const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel;
 	int32_t k, max_drop; int32_t* pos; int32_t* n_eligible;
+	ssw_gpu_mates* mates; int32_t nfwd, min_insert, max_insert, unpaired_penalty;
 } best_mode;
-/* device bytes of the per-group output behind the call-long record array: record + selection (64) / k records, k positions and a count */
+/* device bytes of the per-group output behind the call-long record array: record + selection (64; mates: 48 + half of the fragment's 32) /
+   k records, k positions and a count */
 static size_t best_out_bytes(const best_mode* bm)
 {
 	return bm->k ? (size_t)bm->ngroups * ((sizeof(struct ssw_out_rec) + 4) * (size_t)bm->k + 4) : 64 * (size_t)bm->ngroups;
@@ -3398,12 +3403,13 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		}
 	}
 	if (bm) {
-		/* ---- select: candidate -> record slot, k_groupbest (k_grouptopk), one selection + one record (k positions + k records) per group to the host */
+		/* ---- select: candidate -> record slot, k_groupbest (k_grouptopk, k_matebest), one selection + one record (k positions + k records) per group to the host */
 		const int64_t ng = bm->ngroups;
 		const size_t rec_bytes = sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb);
 		if (!d_brec && !(d_brec = (unsigned char*)ensure(c, &c->brec, rec_bytes + best_out_bytes(bm)))) goto done;
-		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + 4 * (size_t)np);      /* (4 bytes per candidate, 8 per group) */
-		slot = (int32_t*)malloc(sizeof(int32_t) * (size_t)np);
+		/* (4 bytes per candidate, 8 per group; mates: 16 more per candidate for the side table -- tbeg, tidx, length | strand) */
+		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + (bm->mates ? 20 : 4) * (size_t)np);
+		slot = (int32_t*)malloc(sizeof(int32_t) * (bm->mates ? 2 : 1) * (size_t)np);
 		if (!d_map) goto done;
 		if (!slot) { fail(c, "out of host memory%s", ""); goto done; }
 		for (int64_t j = 0; j < nj; ++j)
@@ -3411,14 +3417,33 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		for (int64_t f = 0; f < nfb; ++f) slot[fb[f]] = (int32_t)(2 * nj + f);
 		const int32_t K = bm->k;
 		const struct ssw_out_rec* d_rec = (const struct ssw_out_rec*)d_brec;
-		const int64_t* d_off = (const int64_t*)d_map; const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1));
+		const int64_t* d_off = (const int64_t*)d_map; const int64_t* d_tbeg = (const int64_t*)(d_map + 8 * ((size_t)ng + 1));      /* (mates only) */
+		const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1) + (bm->mates ? 8 * (size_t)np : 0));
 		unsigned char* d_sel = d_brec + rec_bytes;      /* best: [ng] records, [ng] selections; top-k: [nout] records, [nout] positions, [ng] counts */
 		if ((nfb > 0 && ssw_shim_h2d((void*)(d_rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
 		    ssw_shim_h2d((void*)d_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)d_slot, slot, 4 * (size_t)np, c->stream)) {
 			fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
 		}
+		if (bm->mates) {      /* the side table behind the slot map: [np] targets, [np] query length | minus strand << 31 */
+			uint32_t* ls = (uint32_t*)slot + np;
+			for (int64_t i = 0; i < np; ++i) ls[i] = (uint32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) | (qidx[i] >= bm->nfwd ? 0x80000000u : 0u);
+			if (ssw_shim_h2d((void*)d_tbeg, src->tbeg, 8 * (size_t)np, c->stream) || ssw_shim_h2d((void*)(d_slot + np), tidx, 4 * (size_t)np, c->stream) ||
+			    ssw_shim_h2d((void*)(d_slot + 2 * np), ls, 4 * (size_t)np, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+		}
 		ssw_shim_event_record(c->ev_a, c->stream);
-		if (K) {
+		if (bm->mates) {
+			ssw_matebest_args ma; memset(&ma, 0, sizeof ma);
+			ma.rec = d_rec; ma.cand_off = d_off; ma.slot = d_slot; ma.tbeg = d_tbeg; ma.tidx = d_slot + np; ma.len_strand = (const uint32_t*)(d_slot + 2 * np);
+			ma.nfrag = ng / 2; ma.min_score = bm->min_score; ma.min_insert = bm->min_insert; ma.max_insert = bm->max_insert;
+			ma.unpaired_penalty = bm->unpaired_penalty;
+			ma.out = (struct ssw_out_rec*)d_sel; ma.sel = (struct ssw_mate_rec*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)ng);
+			if (ssw_shim_launch_matebest(&ma, c->stream)) { fail(c, "matebest launch failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(c->ev_b, c->stream);
+			if (ssw_shim_d2h(results, ma.out, sizeof(ssw_gpu_result) * (size_t)ng, c->stream) ||
+			    ssw_shim_d2h(bm->mates, ma.sel, sizeof(ssw_gpu_mates) * (size_t)(ng / 2), c->stream) || ssw_shim_stream_sync(c->stream)) {
+				fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
+			}
+		} else if (K) {
 			ssw_grouptopk_args ta; memset(&ta, 0, sizeof ta);
 			ta.rec = d_rec; ta.cand_off = d_off; ta.slot = d_slot; ta.ngroups = ng; ta.min_score = bm->min_score; ta.k = K; ta.max_drop = bm->max_drop;
 			ta.out = (struct ssw_out_rec*)d_sel; ta.pos = (int32_t*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)nout); ta.n_eligible = ta.pos + nout;
@@ -3449,7 +3474,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			wg = wlist + nout;      /* wlist: the fused path's winners from the front, the fallback's from the back; wg: their output slots */
 			for (int64_t g = 0; g < ng; ++g)
 				for (int64_t o = g * per; o < (g + 1) * per; ++o) {
-					const int32_t p = K ? bm->pos[o] : bm->sel[g].best;
+					const int32_t p = K ? bm->pos[o] : bm->mates ? (g & 1 ? bm->mates[g >> 1].pos2 : bm->mates[g >> 1].pos1) : bm->sel[g].best;
 					if (p < 0) break;
 					const int64_t i = bm->cand_off[g] + p;
 					if (!(prm->flag == 2 && (int)results[o].score1 < prm->filters)) ++ngate;      /* ssw.c:916 */
@@ -3682,6 +3707,82 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
 	if (!c) return fail(0, "align_windows_best: NULL context%s", "");
 	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
 	return ctx_leave(c, align_windows_best_locked(c, Q, T, cand_off, ngroups, qidx, tidx, tbeg, tlen, prm, min_score, sel, results, cigar_pool, cigar_words));
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Best candidate pair per read pair (ssw_gpu_align_windows_mates): the same select mode over 2 * nfrag groups, the selection per FRAGMENT
+ * (k_matebest).  Device state that outlives a fill launch, an input / output of the call like the window table: per candidate 48 bytes of
+ * record, 4 of slot map and 16 of side table (tbeg, tidx, read length | strand), per fragment 128 bytes of output (two records, one
+ * selection) and 16 of offsets.
+ * ------------------------------------------------------------------------------------------------ */
+static void mates_pad(ssw_gpu_mates* m) { memset(m, 0, sizeof *m); m->pos1 = m->pos2 = -1; }
+
+static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                      const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
+                                      ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	char msg[200];
+	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
+	if (cigar_words) *cigar_words = 0;
+	if (nf < 0 || (nf > 0 && (!cand_off || !sel || !results))) return fail(c, "align_windows_mates: NULL argument%s", "");
+	if (check_common(c, "align_windows_mates", Q, T, prm)) return -1;
+	if (nf == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }
+	if (nf > 0x7fffff00 / 2) {
+		snprintf(msg, sizeof msg, "%lld fragments", (long long)nf);
+		return fail(c, "align_windows_mates: more than 2^31 output slots in one call (%s)", msg);
+	}
+	if (min_insert < 0 || min_insert > max_insert) {
+		snprintf(msg, sizeof msg, "min_insert = %d, max_insert = %d", min_insert, max_insert);
+		return fail(c, "align_windows_mates: 0 <= min_insert <= max_insert required (%s)", msg);
+	}
+	if (unpaired_penalty < 0 || unpaired_penalty > 65535) {
+		snprintf(msg, sizeof msg, "unpaired_penalty = %d", unpaired_penalty);
+		return fail(c, "align_windows_mates: unpaired_penalty must be 0 .. 65535 (%s)", msg);
+	}
+	if (nfwd < 0 || nfwd > Q->count) {
+		snprintf(msg, sizeof msg, "nfwd = %d, %d queries", nfwd, Q->count);
+		return fail(c, "align_windows_mates: nfwd outside the query set (%s)", msg);
+	}
+	if (cand_off[0] != 0) {
+		snprintf(msg, sizeof msg, "fragment 0 starts at candidate %lld", (long long)cand_off[0]);
+		return fail(c, "align_windows_mates: cand_off[0] must be 0 (%s)", msg);
+	}
+	const int64_t ng = 2 * nf;
+	for (int64_t g = 0; g < ng; ++g) {
+		const int64_t sz = cand_off[g + 1] - cand_off[g];
+		if (sz >= 0 && sz <= SSW_GPU_MATES_GROUP_MAX) continue;
+		snprintf(msg, sizeof msg, "fragment %lld, mate %d: candidates [%lld, %lld)", (long long)(g >> 1), (int)(g & 1) + 1, (long long)cand_off[g], (long long)cand_off[g + 1]);
+		return sz < 0 ? fail(c, "align_windows_mates: cand_off decreases (%s)", msg)
+		              : fail(c, "align_windows_mates: more than 4096 candidates in a group (%s)", msg);
+	}
+	const int64_t np = cand_off[ng];
+	if (np > 0x7fffff00) return fail(c, "align_windows_mates: %s", "more than 2^31 candidates in one call");
+	if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) return fail(c, "align_windows_mates: NULL argument%s", "");
+	if (windows_check(c, "align_windows_mates", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
+	if (np == 0) {      /* empty groups only */
+		memset(&c->tm, 0, sizeof c->tm);
+		for (int64_t g = 0; g < ng; ++g) topk_pad(&results[g]);
+		for (int64_t f = 0; f < nf; ++f) mates_pad(&sel[f]);
+		return 0;
+	}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows_mates";
+	best_mode bm; memset(&bm, 0, sizeof bm);
+	bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.mates = sel;
+	bm.nfwd = nfwd; bm.min_insert = min_insert; bm.max_insert = max_insert; bm.unpaired_penalty = unpaired_penalty;
+	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
+}
+
+int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                                const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
+                                ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows_mates: NULL context%s", "");
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_mates_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
+	                                               unpaired_penalty, sel, results, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -4385,6 +4385,147 @@ __global__ void __launch_bounds__(256) k_grouptopk(ssw_grouptopk_args a)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * k_matebest (ssw_matebest_args): the best two combinations (candidate of mate 1, candidate of mate 2) of every fragment
+ * (ssw_gpu_align_windows_mates), on k_groupbest's geometry -- one DPP row of 16 lanes per FRAGMENT, four per wavefront, sixteen per
+ * workgroup -- in two steps.
+ *   1. The lanes stride over the fragment's n1 + n2 candidates and form one DIGEST per candidate, 24 bytes: score1 (0: not eligible),
+ *      target | strand << 31, E = tbeg + ref_end1 and E - len (64-bit both): one load of the slot map, three of the record (score1,
+ *      ref_end1, flag | status, as k_groupbest reads them) and three of the side table.  Fragments of up to MB_LDS_CAND candidates keep
+ *      their digests in LDS; larger ones form them again whenever they are needed (rare: a mapper hands over a few candidates per mate).
+ *      MB_LDS_CAND = 48: 16 fragments x 48 x 24 bytes = 18 KiB per workgroup, so that the eight workgroups that fill a CU's 32 wavefront
+ *      slots take 144 of its 160 KiB -- the LDS does not lower residency.  The step also counts the eligible candidates of either mate
+ *      and keeps k_groupbest's key pair over the candidates themselves, for fragments in which only one mate has any.
+ *   2. The lanes stride over the combinations c = pos1 * n2 + pos2 (c < 2^24: the host's group limit).  Eligible x eligible gives the key
+ *        (S + 65536) << 32 | ~c,   S = score1(a) + score1(b) - (proper ? 0 : unpaired_penalty) >= -65533
+ *      so that a plain maximum is the ranking and 0 means none; a lane keeps its best two and counts the proper ones.  (pos1, pos2) advance
+ *      by 16 combinations without a division; the digest of pos1 is fetched again only when pos1 changes.
+ * Both steps end in gb_merge's four row rotations, outside every loop: trip counts may differ between the rows of a wavefront.  Lane 0
+ * writes the 32-byte selection, lanes 0..2 copy the record chosen for mate 1 (or the padding record) and lanes 3..5 that of mate 2,
+ * 16 bytes each.  No atomics, no waiting; the LDS hand-off stays inside a wavefront (wave_lds_fence).
+ * ------------------------------------------------------------------------------------------------ */
+#define MB_LDS_CAND 48
+#define MB_DIGEST 24
+#define MB_LDS_BYTES (16 * MB_LDS_CAND * MB_DIGEST)
+struct mb_dig { u32 s, ts; long long E, EL; };
+SSW_DEV mb_dig mb_form(const ssw_matebest_args& a, int64_t i, int lo)      /* candidate i of the call */
+{
+	const u32* r = (const u32*)(a.rec + a.slot[i]);
+	const u32 s = r[0] & 0xffffu, st = (r[10] >> 16) & ~(u32)SSW_OUT_WORD;      /* as k_groupbest reads them; word 2: ref_end1 */
+	const u32 ls = a.len_strand[i];
+	mb_dig d;
+	d.s = st == 0 && (int)s >= lo ? s : 0u;
+	d.ts = (u32)a.tidx[i] | (ls & 0x80000000u);
+	d.E = (long long)a.tbeg[i] + (int32_t)r[2];
+	d.EL = d.E - (long long)(ls & 0x7fffffffu);
+	return d;
+}
+SSW_DEV mb_dig mb_get(const ssw_matebest_args& a, const unsigned char* lds, u32 base, bool in_lds, int64_t c0, int p, int lo)
+{
+	if (!in_lds) return mb_form(a, c0 + p, lo);
+	const u32 off = base + (u32)p * MB_DIGEST;
+	const u32x2 w0 = lds_ld64(lds, off), w1 = lds_ld64(lds, off + 8), w2 = lds_ld64(lds, off + 16);
+	mb_dig d;
+	d.s = w0.x; d.ts = w0.y;
+	d.E = (long long)((unsigned long long)w1.x | ((unsigned long long)w1.y << 32));
+	d.EL = (long long)((unsigned long long)w2.x | ((unsigned long long)w2.y << 32));
+	return d;
+}
+/* one target, opposite strands, and min_insert <= E(minus) - B(plus) + 1 <= max_insert with B = E - len + 1 */
+SSW_DEV bool mb_proper(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y)
+{
+	if ((x.ts ^ y.ts) != 0x80000000u) return false;
+	const long long ins = (x.ts >> 31) ? x.E - y.EL : y.E - x.EL;
+	return ins >= (long long)a.min_insert && ins <= (long long)a.max_insert;
+}
+
+__global__ void __launch_bounds__(256) k_matebest(ssw_matebest_args a)
+{
+	SSW_DYN_LDS(lds);
+	const int64_t f = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;      /* (a row is inside the list or outside it as a whole) */
+	const int l = (int)threadIdx.x & 15;
+	const u32 base = ((u32)threadIdx.x >> 4) * (u32)(MB_LDS_CAND * MB_DIGEST);
+	const bool live = f < a.nfrag;
+	const int lo = a.min_score > 1 ? a.min_score : 1;
+	unsigned long long k1 = 0, k2 = 0;
+	u32 ne1 = 0, ne2 = 0;
+	int64_t c0 = 0;
+	int n1 = 0, n2 = 0;
+	bool in_lds = false;
+	if (live) {
+		c0 = a.cand_off[2 * f];
+		const int64_t c1 = a.cand_off[2 * f + 1];
+		n1 = (int)(c1 - c0); n2 = (int)(a.cand_off[2 * f + 2] - c1);      /* (each at most SSW_MATES_GROUP_MAX: the host's check) */
+		in_lds = n1 + n2 <= MB_LDS_CAND;
+		for (int p = l; p < n1 + n2; p += 16) {
+			const mb_dig d = mb_form(a, c0 + p, lo);
+			if (in_lds) {
+				const u32 off = base + (u32)p * MB_DIGEST;
+				lds_st32(lds, off, d.s); lds_st32(lds, off + 4, d.ts);
+				lds_st32(lds, off + 8, (u32)(unsigned long long)d.E); lds_st32(lds, off + 12, (u32)((unsigned long long)d.E >> 32));
+				lds_st32(lds, off + 16, (u32)(unsigned long long)d.EL); lds_st32(lds, off + 20, (u32)((unsigned long long)d.EL >> 32));
+			}
+			if (d.s) {
+				const unsigned long long k = ((unsigned long long)d.s << 32) | (u32)~(u32)(p < n1 ? p : p - n1);
+				if (k > k1) { k2 = k1; k1 = k; } else if (k > k2) k2 = k;
+				if (p < n1) ++ne1; else ++ne2;
+			}
+		}
+	}
+	gb_merge<8>(k1, k2, ne1); gb_merge<4>(k1, k2, ne1); gb_merge<2>(k1, k2, ne1); gb_merge<1>(k1, k2, ne1);
+	ne2 += xl_row_ror<8>(ne2); ne2 += xl_row_ror<4>(ne2); ne2 += xl_row_ror<2>(ne2); ne2 += xl_row_ror<1>(ne2);
+	wave_lds_fence();      /* the row's digests are in LDS before any of its lanes reads another lane's */
+	const bool both = ne1 != 0 && ne2 != 0;
+	unsigned long long m1 = 0, m2 = 0;
+	u32 npr = 0;
+	if (both) {
+		const u32 nc = (u32)n1 * (u32)n2, q16 = 16u / (u32)n2, r16 = 16u % (u32)n2;
+		u32 p1 = (u32)l / (u32)n2, p2 = (u32)l % (u32)n2, have = 0xffffffffu;
+		mb_dig da; da.s = 0; da.ts = 0; da.E = 0; da.EL = 0;
+		for (u32 c = (u32)l; c < nc; c += 16) {
+			if (p1 != have) { da = mb_get(a, lds, base, in_lds, c0, (int)p1, lo); have = p1; }
+			if (da.s) {
+				const mb_dig db = mb_get(a, lds, base, in_lds, c0, n1 + (int)p2, lo);
+				if (db.s) {
+					const bool pr = mb_proper(a, da, db);
+					const unsigned long long k = ((unsigned long long)(da.s + db.s + 65536u - (pr ? 0u : (u32)a.unpaired_penalty)) << 32) | (u32)~c;
+					if (k > m1) { m2 = m1; m1 = k; } else if (k > m2) m2 = k;
+					npr += pr;
+				}
+			}
+			p1 += q16; p2 += r16;
+			if (p2 >= (u32)n2) { p2 -= (u32)n2; ++p1; }
+		}
+	}
+	gb_merge<8>(m1, m2, npr); gb_merge<4>(m1, m2, npr); gb_merge<2>(m1, m2, npr); gb_merge<1>(m1, m2, npr);
+	if (!live) return;
+	int pos1 = -1, pos2 = -1, score = 0, second = 0;
+	u32 proper = 0;
+	if (both) {
+		const u32 c = ~(u32)m1;
+		pos1 = (int)(c / (u32)n2); pos2 = (int)(c % (u32)n2);
+		score = (int)(u32)(m1 >> 32) - 65536;
+		second = m2 ? (int)(u32)(m2 >> 32) - 65536 : 0;
+		proper = mb_proper(a, mb_get(a, lds, base, in_lds, c0, pos1, lo), mb_get(a, lds, base, in_lds, c0, n1 + pos2, lo)) ? 1u : 0u;
+	} else if (k1) {      /* one mate alone: k_groupbest's rule over its candidates */
+		if (ne1) pos1 = (int)~(u32)k1; else pos2 = (int)~(u32)k1;
+		score = (int)(u32)(k1 >> 32);
+		second = (int)((u32)(k2 >> 32) & 0xffffu);
+	}
+	if (l == 0) {
+		const u32x4 v0 = { (u32)pos1, (u32)pos2, ne1, ne2 }, v1 = { (u32)score, (u32)second, npr, proper };
+		((u32x4*)(a.sel + f))[0] = v0; ((u32x4*)(a.sel + f))[1] = v1;
+	}
+	if (l < 6) {
+		const int h = l >= 3, piece = l - 3 * h, pos = h ? pos2 : pos1;
+		u32x4 v = { 0u, 0u, 0u, 0u };
+		if (pos >= 0) v = ((const u32x4*)(a.rec + a.slot[c0 + (h ? n1 : 0) + pos]))[piece];
+		else if (piece == 0) { v.y = 0xffffffffu; v.w = 0xffffffffu; }      /* ref_begin1, read_begin1 */
+		else if (piece == 2) { v.x = 0xffffffffu; v.y = 0xffffffffu; }      /* cigar_off */
+		((u32x4*)(a.out + 2 * f + h))[piece] = v;
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------
  * k_selftest: (a) the cross-lane primitives applied to the lane id, so that tests can pin the DPP semantics the
  * chains rely on (and that the CPU emulator assumes) on real hardware; (b) a packed-int16 VALU issue-rate probe
  * (8 independent v_pk_add_i16/v_pk_max_i16/v_pk_sub_u16 chains) whose measured rate is the roofline's "peak".
@@ -4578,6 +4719,14 @@ extern "C" int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stre
 	if (args.ngroups <= 0) return 0;
 	if (args.k < 1) return -2;
 	SSW_LAUNCH(k_grouptopk, ssw_grouptopk_args, args, (args.ngroups + 15) / 16, 256, 0, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_matebest(const ssw_matebest_args* a, void* stream)
+{
+	ssw_matebest_args args = *a;
+	if (args.nfrag <= 0) return 0;
+	SSW_LAUNCH(k_matebest, ssw_matebest_args, args, (args.nfrag + 15) / 16, 256, MB_LDS_BYTES, stream);
 	return SSW_LAUNCH_OK();
 }
 

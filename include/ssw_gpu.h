@@ -280,6 +280,74 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
                                int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results,
                                uint32_t** cigar_pool, int64_t* cigar_words);
 
+/*
+ * Best candidate pair per read pair: the step of a paired-end mapper between seeding and SAM output.  A fragment has two mates, each with
+ * its own candidate windows; wanted is not the best window of either mate but the best COMBINATION -- one candidate of mate 1 and one of
+ * mate 2 on the same target, on opposite strands, a plausible insert apart -- and how far the next-best combination is.
+ * cand_off has 2 * nfrag + 1 offsets: group 2 f holds the candidates of mate 1 of fragment f, group 2 f + 1 those of mate 2.  Candidates,
+ * their four arrays and eligibility (status 0, score1 > 0, score1 >= min_score) are exactly ssw_gpu_align_windows_best's; a group holds at
+ * most SSW_GPU_MATES_GROUP_MAX candidates.  Candidate i is on the minus strand iff qidx[i] >= nfwd (ssw_gpu_seqs_with_revcomp's
+ * convention: nfwd = the number of forward reads; nfwd = queries->count: everything on the plus strand).
+ * Per eligible candidate i, from its flag-0 record `rec`, in 64-bit arithmetic and target coordinates:
+ *   E = tbeg[i] + rec.ref_end1          the last column of the alignment;
+ *   B = E - len(query qidx[i]) + 1      the ESTIMATED first column, signed and never clamped (a read hanging over column 0 has B < 0).
+ * B is an estimate by design -- begin positions do not exist before the reverse pass, which runs over the winners only; an alignment
+ * with gaps or clipping begins elsewhere.  It decides which combinations count as proper, nothing else: the caller computes TLEN from the
+ * winners' real ref_begin1 / ref_end1.
+ * A combination (a of mate 1, b of mate 2) is PROPER (FR library) iff tidx[a] == tidx[b], the strands differ, and, with p the plus-strand
+ * and m the minus-strand one, min_insert <= E(m) - B(p) + 1 <= max_insert.  Its score is
+ *   S(a, b) = score1(a) + score1(b) - (proper ? 0 : unpaired_penalty)            (signed)
+ * Ranking over eligible x eligible: S descending, then position of a, then position of b ascending -- one total order; a proper and an
+ * improper combination of equal S tie-break by position only.
+ *   sel[f]          pos1 / pos2: the first combination of that order, positions relative to the groups' cand_off; score: its S;
+ *                   second_score: S of the second combination (0 when there is none: n_eligible1 * n_eligible2 < 2); n_proper: proper
+ *                   combinations among eligible x eligible; proper: whether the chosen one is.  When only ONE mate has an eligible
+ *                   candidate it is chosen by ssw_gpu_align_windows_best's rule (score1 descending, position ascending): the other pos is
+ *                   -1, score its score1, second_score the group's runner-up score1, proper = n_proper = 0.  Neither: both -1, the rest 0.
+ *                   sel does not depend on params->flag.  With unpaired_penalty == 0, pos1 / pos2 equal ssw_gpu_align_windows_best's
+ *                   `best` of groups 2 f and 2 f + 1.
+ *   results[2 f + h]  bit for bit the record ssw_gpu_align_windows gives for the chosen candidate of mate h + 1 with the caller's flag,
+ *                   filters, filterd, maskLen, score_size and mark_mismatch (window-relative positions); the padding record (zeros,
+ *                   ref_begin1 = read_begin1 = -1, cigar_off = -1) where pos is -1;
+ *   cigar_pool      (optional, malloc()ed, caller frees) the winners' CIGARs in (fragment, mate) order.
+ * The forward fill runs once over all candidates as for ssw_gpu_align_windows_best; the selection runs on the device (k_matebest: one
+ * 16-lane row per fragment); 32 bytes of selection and two records per fragment come to the host; the reverse pass, the traceback and
+ * mark_mismatch run over the winners only, their fill records reused.  Candidates outside the fast-path envelopes are exact in any mix,
+ * inside one fragment too, by ssw_gpu_align_windows_best's route: the fallback at flag 0 first, their records uploaded beside the fill's,
+ * the fallback once more for those that win.
+ * Memory (inputs / outputs of the call like the window table, not scratch under ssw_gpu_get_budget): per candidate 48 bytes of record, 4
+ * of slot map and a side table of 16 (tbeg, tidx, read length | strand); per fragment 128 bytes of output (two records, one selection)
+ * and 16 of offsets.  Fill launches are cut to the budget as for ssw_gpu_align_windows.
+ * Errors (-1 with a message that names the fragment or the pair, before anything is launched or written): a NULL array, cand_off[0] != 0,
+ * a decreasing cand_off, a group of more than SSW_GPU_MATES_GROUP_MAX candidates (pos1 * n2 + pos2 has to fit the 32-bit half of a
+ * selection key with room to spare), 2 * nfrag or the candidate count beyond 0x7fffff00, nfwd outside [0, queries->count], min_insert < 0
+ * or min_insert > max_insert, unpaired_penalty outside 0 .. 65535, an index or window out of range (ssw_gpu_align_windows' text),
+ * sequences of another context.  nfrag == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for
+ * ssw_gpu_align_windows.
+ * ssw_gpu_last_timing: reduce_ms is the device time of k_matebest; best_flagged the winners handed to the reverse pass / traceback (at
+ * most 2 * nfrag; 0 at flag 0).
+ * Not provided (yet): a pool variant (it follows in a change of its own, cutting blocks at fragment borders); the C++ BatchAligner (its
+ * window methods are forward-strand only); RF and FF library orientations; more than the best two combinations; a CLI option.
+ */
+#define SSW_GPU_MATES_GROUP_MAX 4096
+typedef struct {
+	int32_t pos1, pos2;          /* chosen candidate of mate 1 / mate 2, relative to its group's cand_off; -1: none */
+	int32_t n_eligible1, n_eligible2;
+	int32_t score;               /* pair score S of the chosen combination; with one mate only: its score1; 0: nothing chosen */
+	int32_t second_score;        /* S of the second combination in the ranking (one mate only: second best score1 of that group); 0 when there is none */
+	int32_t n_proper;            /* proper combinations among eligible x eligible */
+	uint16_t proper;             /* 1: the chosen combination is proper */
+	uint16_t pad;                /* 0 */
+} ssw_gpu_mates;                 /* 32 bytes */
+int ssw_gpu_align_windows_mates(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                                const int64_t* cand_off, int64_t nfrag,
+                                const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                int32_t nfwd,
+                                const ssw_gpu_params* params, int32_t min_score,
+                                int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
+                                ssw_gpu_mates* sel, ssw_gpu_result* results,
+                                uint32_t** cigar_pool, int64_t* cigar_words);
+
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
    an earlier, shorter ssw_gpu_timing passes ITS sizeof and is not written past it */
