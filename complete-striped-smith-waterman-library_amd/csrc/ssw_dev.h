@@ -460,13 +460,17 @@ typedef struct {
    holds the candidates of mate 1 of fragment f, group 2 f + 1 those of mate 2 -- and a side table per candidate, uploaded by the host:
    the window's first column, its target, and the read's length with the strand in bit 31.  From these and the fill record a candidate has
    E = tbeg + ref_end1 (last column, target coordinates) and B = E - len + 1 (estimated first column, never clamped), both 64-bit.
-   A combination (a of mate 1, b of mate 2) is PROPER when both lie on one target, on opposite strands, and the plus-strand one's B and the
-   minus-strand one's E span min_insert .. max_insert columns; its score is score1(a) + score1(b), less unpaired_penalty unless proper.
+   A combination (a of mate 1, b of mate 2) is PROPER when both lie on one target, on the strands of the library `orientation` -- opposite
+   for FR and RF, equal for FF -- and the upstream one's B and the downstream one's E span min_insert .. max_insert columns (upstream: the
+   plus-strand one for FR, the minus-strand one for RF, mate 1 on the plus and mate 2 on the minus strand for FF); its score is score1(a) + score1(b), less unpaired_penalty unless proper.
    Order: that score descending, then position of a, then position of b ascending. */
 struct ssw_mate_rec {        /* byte-for-byte the layout of ssw_gpu_mates (include/ssw_gpu.h) */
 	int32_t pos1, pos2, n_eligible1, n_eligible2, score, second_score, n_proper;
 	uint16_t proper, pad;
 };
+#define SSW_MATES_FR 0                /* SSW_GPU_MATES_FR / _RF / _FF */
+#define SSW_MATES_RF 1
+#define SSW_MATES_FF 2
 #define SSW_MATES_GROUP_MAX 4096      /* SSW_GPU_MATES_GROUP_MAX: pos1 * n2 + pos2 stays below 2^24 */
 typedef struct {
 	const struct ssw_out_rec* rec;
@@ -479,6 +483,7 @@ typedef struct {
 	int32_t min_score;
 	int32_t min_insert, max_insert;
 	int32_t unpaired_penalty;    /* 0 .. 65535 */
+	int32_t orientation;         /* SSW_MATES_FR / RF / FF: which strands and which order make a combination proper */
 	struct ssw_mate_rec* sel;    /* [nfrag] */
 	struct ssw_out_rec* out;     /* [2 * nfrag]: the chosen candidates' records as the fill wrote them (SSW_OUT_WORD kept), the record of an
 	                                empty target where a mate has none */

@@ -29,6 +29,7 @@
 _Static_assert(sizeof(struct ssw_out_rec) == sizeof(ssw_gpu_result), "device record layout must equal ssw_gpu_result");
 _Static_assert(sizeof(struct ssw_mate_rec) == sizeof(ssw_gpu_mates) && sizeof(ssw_gpu_mates) == 32, "device selection layout must equal ssw_gpu_mates");
 _Static_assert(SSW_MATES_GROUP_MAX == SSW_GPU_MATES_GROUP_MAX, "the kernel's group limit is the header's");
+_Static_assert(SSW_MATES_FR == SSW_GPU_MATES_FR && SSW_MATES_RF == SSW_GPU_MATES_RF && SSW_MATES_FF == SSW_GPU_MATES_FF, "the kernel's orientations are the header's");
 _Static_assert(sizeof(struct ssw_best_rec) == sizeof(ssw_gpu_best) && sizeof(ssw_gpu_best) == 16, "device record layout must equal ssw_gpu_best");
 
 struct _profile {
@@ -3092,7 +3093,7 @@ static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu
 typedef struct {
 	const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel;
 	int32_t k, max_drop; int32_t* pos; int32_t* n_eligible;
-	ssw_gpu_mates* mates; int32_t nfwd, min_insert, max_insert, unpaired_penalty;
+	ssw_gpu_mates* mates; int32_t nfwd, min_insert, max_insert, unpaired_penalty, orientation;
 } best_mode;
 /* device bytes of the per-group output behind the call-long record array: record + selection (64; mates: 48 + half of the fragment's 32) /
    k records, k positions and a count */
@@ -3435,7 +3436,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			ssw_matebest_args ma; memset(&ma, 0, sizeof ma);
 			ma.rec = d_rec; ma.cand_off = d_off; ma.slot = d_slot; ma.tbeg = d_tbeg; ma.tidx = d_slot + np; ma.len_strand = (const uint32_t*)(d_slot + 2 * np);
 			ma.nfrag = ng / 2; ma.min_score = bm->min_score; ma.min_insert = bm->min_insert; ma.max_insert = bm->max_insert;
-			ma.unpaired_penalty = bm->unpaired_penalty;
+			ma.unpaired_penalty = bm->unpaired_penalty; ma.orientation = bm->orientation;
 			ma.out = (struct ssw_out_rec*)d_sel; ma.sel = (struct ssw_mate_rec*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)ng);
 			if (ssw_shim_launch_matebest(&ma, c->stream)) { fail(c, "matebest launch failed: %s", ssw_shim_last_error()); goto done; }
 			ssw_shim_event_record(c->ev_b, c->stream);
@@ -3720,7 +3721,7 @@ static void mates_pad(ssw_gpu_mates* m) { memset(m, 0, sizeof *m); m->pos1 = m->
 static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
                                       const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
                                       const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
-                                      ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+                                      int32_t orientation, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
 	char msg[200];
 	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
@@ -3739,6 +3740,10 @@ static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, con
 	if (unpaired_penalty < 0 || unpaired_penalty > 65535) {
 		snprintf(msg, sizeof msg, "unpaired_penalty = %d", unpaired_penalty);
 		return fail(c, "align_windows_mates: unpaired_penalty must be 0 .. 65535 (%s)", msg);
+	}
+	if (orientation < SSW_GPU_MATES_FR || orientation > SSW_GPU_MATES_FF) {
+		snprintf(msg, sizeof msg, "orientation = %d", orientation);
+		return fail(c, "align_windows_mates: orientation must be SSW_GPU_MATES_FR, _RF or _FF (%s)", msg);
 	}
 	if (nfwd < 0 || nfwd > Q->count) {
 		snprintf(msg, sizeof msg, "nfwd = %d, %d queries", nfwd, Q->count);
@@ -3771,7 +3776,19 @@ static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, con
 	best_mode bm; memset(&bm, 0, sizeof bm);
 	bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.mates = sel;
 	bm.nfwd = nfwd; bm.min_insert = min_insert; bm.max_insert = max_insert; bm.unpaired_penalty = unpaired_penalty;
+	bm.orientation = orientation;
 	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
+}
+
+int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                                    const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                    const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
+                                    int32_t orientation, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows_mates: NULL context%s", "");
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_mates_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
+	                                               unpaired_penalty, orientation, sel, results, cigar_pool, cigar_words));
 }
 
 int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
@@ -3779,10 +3796,8 @@ int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
                                 const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
                                 ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	if (!c) return fail(0, "align_windows_mates: NULL context%s", "");
-	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
-	return ctx_leave(c, align_windows_mates_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
-	                                               unpaired_penalty, sel, results, cigar_pool, cigar_words));
+	return ssw_gpu_align_windows_mates_lib(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
+	                                       unpaired_penalty, SSW_GPU_MATES_FR, sel, results, cigar_pool, cigar_words);
 }
 
 /* ------------------------------------------------------------------------------------------------

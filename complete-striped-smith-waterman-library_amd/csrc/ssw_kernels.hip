@@ -4430,11 +4430,14 @@ SSW_DEV mb_dig mb_get(const ssw_matebest_args& a, const unsigned char* lds, u32 
 	d.EL = (long long)((unsigned long long)w2.x | ((unsigned long long)w2.y << 32));
 	return d;
 }
-/* one target, opposite strands, and min_insert <= E(minus) - B(plus) + 1 <= max_insert with B = E - len + 1 */
+/* x of mate 1, y of mate 2: one target, the strands the library orientation asks for -- opposite (FR, RF) or equal (FF) --, and
+   min_insert <= E(downstream) - B(upstream) + 1 <= max_insert with B = E - len + 1.  Downstream is the minus-strand one (FR), the
+   plus-strand one (RF), mate 2 on the plus and mate 1 on the minus strand (FF): x exactly when x's strand bit differs from "RF".
+   a.orientation is a kernel argument: both tests are wave-uniform selects, no branch. */
 SSW_DEV bool mb_proper(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y)
 {
-	if ((x.ts ^ y.ts) != 0x80000000u) return false;
-	const long long ins = (x.ts >> 31) ? x.E - y.EL : y.E - x.EL;
+	if ((x.ts ^ y.ts) != (a.orientation == SSW_MATES_FF ? 0u : 0x80000000u)) return false;
+	const long long ins = ((x.ts >> 31) ^ (u32)(a.orientation == SSW_MATES_RF)) ? x.E - y.EL : y.E - x.EL;
 	return ins >= (long long)a.min_insert && ins <= (long long)a.max_insert;
 }
 

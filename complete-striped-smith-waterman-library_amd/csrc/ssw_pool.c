@@ -6,8 +6,8 @@
  * on one core).  Here a pool owns one worker per device -- a context (its own streams and workspaces, include/ssw_gpu.h)
  * plus one host thread for the duration of a call -- the target set is uploaded once to every device, and blocks of work
  * are handed out through one atomic counter.  A block is a contiguous range of UNITS -- reads (ssw_gpu_pool_align,
- * ssw_gpu_pool_search_topk), pairs (ssw_gpu_pool_align_windows) or groups (ssw_gpu_pool_align_windows_topk) --, a unit owns
- * `width` consecutive record slots, CIGAR pools are concatenated in block order afterwards, so the output is identical to
+ * ssw_gpu_pool_search_topk), pairs (ssw_gpu_pool_align_windows), groups (ssw_gpu_pool_align_windows_topk) or fragments
+ * (ssw_gpu_pool_align_windows_mates) --, a unit owns `width` consecutive record slots, CIGAR pools are concatenated in block order afterwards, so the output is identical to
  * the single-context call over the whole list.
  * Uses only the public batch ABI; host code, plain C.
  */
@@ -56,7 +56,7 @@ struct pool_call {
 	   [bstart[b], bstart[b + 1]) --; a unit owns `width` records */
 	int64_t nunits, block, nblocks, width;
 	int64_t* bstart;
-	const char* unit;            /* "reads", "pairs", "groups": how a failure names its block */
+	const char* unit;            /* "reads", "pairs", "groups", "fragments": how a failure names its block */
 	/* one block on one worker: 0, or -1 with the reason in the worker's context (or in *why, a host-side failure); *uploaded: reads sent */
 	int (*run)(pool_call* k, pool_worker* w, win_scratch* ws, int64_t b, int64_t u0, int64_t cnt, int64_t* uploaded, const char** why);
 	block_cigars* cig;           /* per block */
@@ -66,10 +66,13 @@ struct pool_call {
 	int32_t topk, min_score;     /* topk > 0: ssw_gpu_search_topk per block, rows of topk slots (tidx + results) */
 	int32_t* tidx;
 	/* window lists */
-	const int64_t* cand_off;     /* groups (ssw_gpu_align_windows_topk) or NULL (ssw_gpu_align_windows: a unit is a pair) */
+	const int64_t* cand_off;     /* groups (ssw_gpu_align_windows_topk, _mates) or NULL (ssw_gpu_align_windows: a unit is a pair) */
+	int64_t gpu;                 /* groups per unit: 1, or 2 for ssw_gpu_align_windows_mates (a unit is a fragment: its two mates' groups) */
 	const int32_t* wq; const int32_t* wt; const int64_t* wbeg; const int32_t* wlen;
 	int32_t wk, max_drop;
 	int32_t* pos; int32_t* n_eligible;
+	ssw_gpu_mates* mates;        /* ssw_gpu_align_windows_mates: one selection per fragment, and the rule's arguments */
+	int32_t min_insert, max_insert, unpaired_penalty, orientation;
 	int64_t next;                /* next block index (atomic) */
 	int failed;                  /* first failure stops the hand-out (atomic) */
 	pthread_mutex_t err_lock;
@@ -118,13 +121,15 @@ static int grow(void** p, int64_t* cap, int64_t need, size_t elem)
 	return 0;
 }
 
-/* a block of a window list: pairs [u0, u0 + cnt), or groups [u0, u0 + cnt) with their candidates.  The block's candidates name arbitrary
-   reads on either strand: the worker uploads the DISTINCT forward reads among them in ascending read index (m of them), builds their
+/* a block of a window list: pairs [u0, u0 + cnt), or groups [u0, u0 + cnt) with their candidates, or fragments [u0, u0 + cnt) with the
+   candidates of their 2 cnt groups.  The block's candidates name arbitrary reads on either strand: the worker uploads the DISTINCT forward reads among them in ascending read index (m of them), builds their
    reverse complements on its device only if the block names one, and renumbers qidx to that set -- forward read j is j, its reverse
-   complement m + j.  tidx / tbeg / tlen and the output slices are the caller's arrays in place. */
+   complement m + j -- so that a candidate is on the minus strand iff its local index is >= m, the nfwd a block of fragments is called
+   with.  tidx / tbeg / tlen and the output slices are the caller's arrays in place. */
 static int run_windows(pool_call* k, pool_worker* w, win_scratch* ws, int64_t b, int64_t u0, int64_t cnt, int64_t* uploaded, const char** why)
 {
-	const int64_t p0 = k->cand_off ? k->cand_off[u0] : u0, p1 = k->cand_off ? k->cand_off[u0 + cnt] : u0 + cnt, np = p1 - p0;
+	const int64_t g0 = u0 * k->gpu, ng = cnt * k->gpu;      /* (the block's groups; gpu is 1 without cand_off) */
+	const int64_t p0 = k->cand_off ? k->cand_off[g0] : u0, p1 = k->cand_off ? k->cand_off[g0 + ng] : u0 + cnt, np = p1 - p0;
 	const int32_t nq = k->nq;
 	*why = "out of host memory (window block)";
 	if (!ws->map) {
@@ -150,7 +155,7 @@ static int run_windows(pool_call* k, pool_worker* w, win_scratch* ws, int64_t b,
 	int rc = -1;
 	ssw_gpu_seqs* F = 0; ssw_gpu_seqs* Q = 0;
 	if (grow((void**)&ws->loff, &ws->cap_loff, (int64_t)m + 1, sizeof(int64_t)) || grow((void**)&ws->codes, &ws->cap_codes, total + 1, 1) ||
-	    (k->cand_off && grow((void**)&ws->lco, &ws->cap_groups, cnt + 1, sizeof(int64_t)))) {
+	    (k->cand_off && grow((void**)&ws->lco, &ws->cap_groups, ng + 1, sizeof(int64_t)))) {
 		for (int32_t j = 0; j < m; ++j) ws->map[ws->reads[j]] = -1;
 		return -1;
 	}
@@ -179,9 +184,14 @@ static int run_windows(pool_call* k, pool_worker* w, win_scratch* ws, int64_t b,
 	uint32_t** const cw = k->want_cigars ? &k->cig[b].words : 0;
 	int64_t* const cn = k->want_cigars ? &k->cig[b].n : 0;
 	if (k->cand_off) {
-		for (int64_t g = 0; g <= cnt; ++g) ws->lco[g] = k->cand_off[u0 + g] - p0;
-		rc = ssw_gpu_align_windows_topk(w->ctx, Q, w->targets, ws->lco, cnt, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, k->prm, k->wk,
-		                                k->min_score, k->max_drop, k->pos + u0 * k->wk, k->n_eligible + u0, k->results + u0 * k->wk, cw, cn);
+		for (int64_t g = 0; g <= ng; ++g) ws->lco[g] = k->cand_off[g0 + g] - p0;
+		if (k->mates)
+			rc = ssw_gpu_align_windows_mates_lib(w->ctx, Q, w->targets, ws->lco, cnt, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, m, k->prm,
+			                                     k->min_score, k->min_insert, k->max_insert, k->unpaired_penalty, k->orientation, k->mates + u0,
+			                                     k->results + 2 * u0, cw, cn);
+		else
+			rc = ssw_gpu_align_windows_topk(w->ctx, Q, w->targets, ws->lco, cnt, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, k->prm, k->wk,
+			                                k->min_score, k->max_drop, k->pos + u0 * k->wk, k->n_eligible + u0, k->results + u0 * k->wk, cw, cn);
 	} else
 		rc = ssw_gpu_align_windows(w->ctx, Q, w->targets, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, np, k->prm, k->results + u0, cw, cn);
 	ssw_gpu_seqs_free(Q);
@@ -411,23 +421,24 @@ int ssw_gpu_pool_align_windows(ssw_gpu_pool* p, const int8_t* qcodes, const int6
 	k.wq = qidx; k.wt = tidx; k.wbeg = tbeg; k.wlen = tlen;
 	k.nunits = npairs; k.block = block > 0 ? block : windows_auto_block(p, npairs);
 	if (k.block > npairs) k.block = npairs;
-	 k.width = 1; k.run = run_windows; k.unit = "pairs";
+	k.gpu = 1; k.width = 1; k.run = run_windows; k.unit = "pairs";
 	return pool_run(p, &k, cigar_pool, cigar_words);
 }
 
-/* groups in blocks: a block takes whole groups, in order, until it holds at least `block` candidates -- at least one group, empty groups
-   included.  Writes the first group of every block and ngroups at the end into bstart (when given) -> the number of blocks */
-static int64_t cut_groups(const int64_t* cand_off, int64_t ng, int64_t block, int64_t* bstart)
+/* groups in blocks: a block takes whole units of `gpu` groups each (a group, or the two groups of a fragment), in order, until it holds at
+   least `block` candidates -- at least one unit, empty ones included.  Writes the first unit of every block and nu at the end into
+   bstart (when given) -> the number of blocks */
+static int64_t cut_groups(const int64_t* cand_off, int64_t nu, int64_t gpu, int64_t block, int64_t* bstart)
 {
-	int64_t nb = 0, g = 0;
-	while (g < ng) {
-		if (bstart) bstart[nb] = g;
-		const int64_t c0 = cand_off[g];
-		++g;
-		while (g < ng && cand_off[g] - c0 < block) ++g;
+	int64_t nb = 0, u = 0;
+	while (u < nu) {
+		if (bstart) bstart[nb] = u;
+		const int64_t c0 = cand_off[u * gpu];
+		++u;
+		while (u < nu && cand_off[u * gpu] - c0 < block) ++u;
 		++nb;
 	}
-	if (bstart) bstart[nb] = ng;
+	if (bstart) bstart[nb] = nu;
 	return nb;
 }
 
@@ -467,11 +478,81 @@ int ssw_gpu_pool_align_windows_topk(ssw_gpu_pool* p, const int8_t* qcodes, const
 	c.cand_off = cand_off; c.wq = qidx; c.wt = tidx; c.wbeg = tbeg; c.wlen = tlen;
 	c.wk = k; c.min_score = min_score; c.max_drop = max_drop; c.pos = pos; c.n_eligible = n_eligible;
 	if (block <= 0) block = windows_auto_block(p, cand_off[ngroups]);
-	c.nblocks = cut_groups(cand_off, ngroups, block, 0);
+	c.nblocks = cut_groups(cand_off, ngroups, 1, block, 0);
 	c.bstart = (int64_t*)malloc(sizeof(int64_t) * ((size_t)c.nblocks + 1));
 	if (!c.bstart) { snprintf(p->err, sizeof p->err, "out of host memory (block list)"); return -1; }
-	cut_groups(cand_off, ngroups, block, c.bstart);
-	c.nunits = ngroups; c.width = k; c.run = run_windows; c.unit = "groups";
+	cut_groups(cand_off, ngroups, 1, block, c.bstart);
+	c.nunits = ngroups; c.gpu = 1; c.width = k; c.run = run_windows; c.unit = "groups";
+	const int rc = pool_run(p, &c, cigar_pool, cigar_words);
+	free(c.bstart);
+	return rc;
+}
+
+/* ssw_gpu_align_windows_mates_lib over the pool: a unit is a fragment -- two groups, two records, one selection.  Every check of the
+   single-context call is made here over the whole list, so that the message names the caller's fragment, mate or pair and nothing is
+   written before it */
+int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+                                     const int64_t* cand_off, int64_t nfrag,
+                                     const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                     int64_t block, const ssw_gpu_params* prm, int32_t min_score,
+                                     int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+                                     ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	const char* const who = "pool_align_windows_mates";
+	if (!p) return -1;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	if (!qoffsets || nq < 0 || nfrag < 0 || !prm || !prm->mat || (nfrag > 0 && (!cand_off || !sel || !results))) {
+		snprintf(p->err, sizeof p->err, "%s: NULL argument", who);
+		return -1;
+	}
+	if (!p->w[0].targets || !p->toff) { snprintf(p->err, sizeof p->err, "%s: no target set (ssw_gpu_pool_set_targets)", who); return -1; }
+	if (min_insert < 0 || min_insert > max_insert) {
+		snprintf(p->err, sizeof p->err, "%s: 0 <= min_insert <= max_insert required (min_insert = %d, max_insert = %d)", who, min_insert, max_insert);
+		return -1;
+	}
+	if (unpaired_penalty < 0 || unpaired_penalty > 65535) {
+		snprintf(p->err, sizeof p->err, "%s: unpaired_penalty must be 0 .. 65535 (unpaired_penalty = %d)", who, unpaired_penalty);
+		return -1;
+	}
+	if (orientation < SSW_GPU_MATES_FR || orientation > SSW_GPU_MATES_FF) {
+		snprintf(p->err, sizeof p->err, "%s: orientation must be SSW_GPU_MATES_FR, _RF or _FF (orientation = %d)", who, orientation);
+		return -1;
+	}
+	if (nfrag > 0x7fffff00 / 2) {
+		snprintf(p->err, sizeof p->err, "%s: more than 2^31 output slots in one call (%lld fragments)", who, (long long)nfrag);
+		return -1;
+	}
+	if (nfrag > 0) {
+		if (cand_off[0] != 0) {
+			snprintf(p->err, sizeof p->err, "%s: cand_off[0] must be 0 (fragment 0 starts at candidate %lld)", who, (long long)cand_off[0]);
+			return -1;
+		}
+		for (int64_t g = 0; g < 2 * nfrag; ++g) {
+			const int64_t sz = cand_off[g + 1] - cand_off[g];
+			if (sz >= 0 && sz <= SSW_GPU_MATES_GROUP_MAX) continue;
+			snprintf(p->err, sizeof p->err, "%s: %s (fragment %lld, mate %d: candidates [%lld, %lld))", who,
+			         sz < 0 ? "cand_off decreases" : "more than 4096 candidates in a group", (long long)(g >> 1), (int)(g & 1) + 1,
+			         (long long)cand_off[g], (long long)cand_off[g + 1]);
+			return -1;
+		}
+		const int64_t np = cand_off[2 * nfrag];
+		if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) { snprintf(p->err, sizeof p->err, "%s: NULL argument", who); return -1; }
+		if (pool_windows_check(p, who, nq, with_revcomp, qidx, tidx, tbeg, tlen, np)) return -1;
+	}
+	pool_reset_stats(p);
+	if (nfrag == 0) return 0;
+	pool_call c; memset(&c, 0, sizeof c);
+	c.qcodes = qcodes; c.qoff = qoffsets; c.nq = nq; c.prm = prm; c.results = results;
+	c.cand_off = cand_off; c.wq = qidx; c.wt = tidx; c.wbeg = tbeg; c.wlen = tlen;
+	c.min_score = min_score; c.mates = sel;
+	c.min_insert = min_insert; c.max_insert = max_insert; c.unpaired_penalty = unpaired_penalty; c.orientation = orientation;
+	if (block <= 0) block = windows_auto_block(p, cand_off[2 * nfrag]);
+	c.nblocks = cut_groups(cand_off, nfrag, 2, block, 0);
+	c.bstart = (int64_t*)malloc(sizeof(int64_t) * ((size_t)c.nblocks + 1));
+	if (!c.bstart) { snprintf(p->err, sizeof p->err, "out of host memory (block list)"); return -1; }
+	cut_groups(cand_off, nfrag, 2, block, c.bstart);
+	c.nunits = nfrag; c.gpu = 2; c.width = 2; c.run = run_windows; c.unit = "fragments";
 	const int rc = pool_run(p, &c, cigar_pool, cigar_words);
 	free(c.bstart);
 	return rc;

@@ -74,6 +74,29 @@ assert BEST_DTYPE.itemsize == 16
 MATES_DTYPE = np.dtype([("pos1", "<i4"), ("pos2", "<i4"), ("n_eligible1", "<i4"), ("n_eligible2", "<i4"), ("score", "<i4"),
                         ("second_score", "<i4"), ("n_proper", "<i4"), ("proper", "<u2"), ("pad", "<u2")], align=True)
 assert MATES_DTYPE.itemsize == 32
+# SSW_GPU_MATES_FR / _RF / _FF (include/ssw_gpu.h): the library orientation of the proper-pair rule
+MATES_ORIENTATION = {"fr": 0, "rf": 1, "ff": 2}
+
+
+def _orientation(o):
+    """"fr" | "rf" | "ff" (any case) -> 0 .. 2; an integer goes to the library as it is (which refuses what it does not know)"""
+    if isinstance(o, str):
+        if o.lower() not in MATES_ORIENTATION:
+            raise ValueError("orientation must be 'fr', 'rf', 'ff' or 0 .. 2")
+        return MATES_ORIENTATION[o.lower()]
+    return int(o)
+
+
+def _mates_rebase(sel, res, co, tb):
+    """adds the chosen candidate's tbeg to ref_begin1, ref_end1 and ref_end2 where they are >= 0"""
+    nf = sel.shape[0]
+    pos = np.stack([sel["pos1"], sel["pos2"]], axis=1)
+    hit = pos >= 0
+    wb = np.zeros((nf, 2), dtype=np.int64)
+    wb[hit] = tb[(co[:-1].reshape(nf, 2) + pos)[hit]]
+    for f in ("ref_begin1", "ref_end1", "ref_end2"):
+        v = res[f]
+        res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
 
 
 def load(path=None):
@@ -137,6 +160,16 @@ def load(path=None):
                                                   C.c_void_p, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_windows_mates.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows_mates_lib"):
+        L.ssw_gpu_align_windows_mates_lib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_mates_lib.restype = C.c_int
+    if hasattr(L, "ssw_gpu_pool_align_windows_mates"):
+        L.ssw_gpu_pool_align_windows_mates.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
+                                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_pool_align_windows_mates.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -504,12 +537,14 @@ class Context(object):
 
     def align_windows_mates(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mat, n, min_insert, max_insert, unpaired_penalty,
                             min_score=0, rebase=False, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True,
-                            mark_mismatch=False, out=None):
-        """best candidate pair per read pair (ssw_gpu_align_windows_mates): cand_off has 2 nfrag + 1 offsets, group 2 f the candidates of
+                            mark_mismatch=False, out=None, orientation="fr"):
+        """best candidate pair per read pair (ssw_gpu_align_windows_mates_lib): cand_off has 2 nfrag + 1 offsets, group 2 f the candidates of
         mate 1 of fragment f and group 2 f + 1 those of mate 2; candidate i is on the minus strand iff qidx[i] >= nfwd
         -> (sel [nfrag] of MATES_DTYPE, records [nfrag, 2] of RESULT_DTYPE -- the chosen candidates', or the empty record where pos1 / pos2
         is -1 --, uint32 CIGAR pool in (fragment, mate) order).  rebase=True adds the chosen candidate's tbeg to ref_begin1, ref_end1 and
-        ref_end2 where they are >= 0.  `out`: (sel, records) to fill."""
+        ref_end2 where they are >= 0.  `out`: (sel, records) to fill.  orientation: "fr" (default), "rf", "ff" or 0 .. 2 -- the
+        library orientation of the proper-pair rule (SSW_GPU_MATES_*)."""
+        orient = _orientation(orientation)
         co = np.ascontiguousarray(cand_off, dtype=np.int64)
         qi = np.ascontiguousarray(qidx, dtype=np.int32)
         ti = np.ascontiguousarray(tidx, dtype=np.int32)
@@ -534,24 +569,18 @@ class Context(object):
                 raise ValueError("out must be C-contiguous arrays: MATES_DTYPE [nfrag], RESULT_DTYPE [nfrag, 2]")
         pool = _u32p()
         words = C.c_int64(0)
-        rc = self.lib.ssw_gpu_align_windows_mates(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
-                                                  ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
-                                                  int(nfwd), C.byref(p), int(min_score), int(min_insert), int(max_insert), int(unpaired_penalty),
-                                                  sel.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
-                                                  C.byref(pool) if want_cigar else None, C.byref(words))
+        rc = self.lib.ssw_gpu_align_windows_mates_lib(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
+                                                      ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                      int(nfwd), C.byref(p), int(min_score), int(min_insert), int(max_insert),
+                                                      int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
+                                                      res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
         if rc != 0:
             raise RuntimeError("ssw_gpu_align_windows_mates: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
         cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
         if want_cigar and pool:
             C.CDLL(None).free(pool)
         if rebase and nf > 0:
-            pos = np.stack([sel["pos1"], sel["pos2"]], axis=1)
-            hit = pos >= 0
-            wb = np.zeros((nf, 2), dtype=np.int64)
-            wb[hit] = tb[(co[:-1].reshape(nf, 2) + pos)[hit]]
-            for f in ("ref_begin1", "ref_end1", "ref_end2"):
-                v = res[f]
-                res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
+            _mates_rebase(sel, res, co, tb)
         return sel, res, cig
 
     def search_db(self, queries, targets, mat, n, gapO=3, gapE=1, maskLen=-1, score_size=2, chunk=0, on_chunk=None):
@@ -820,6 +849,56 @@ class Pool(object):
                 v = res[f]
                 res[f] = np.where(v >= 0, v + wb, v).astype(np.int32)
         return pos, nel, res, cig
+
+    def align_windows_mates(self, reads, cand_off, qidx, tidx, tbeg, tlen, mat, n, min_insert, max_insert, unpaired_penalty, min_score=0,
+                            orientation="fr", with_revcomp=False, rebase=False, block=0, gapO=3, gapE=1, flag=0, filters=0, filterd=0,
+                            maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None, packed=None):
+        """Context.align_windows_mates over the pool (ssw_gpu_pool_align_windows_mates): reads from the host, windows of the pool's targets;
+        cand_off has 2 nfrag + 1 offsets.  with_revcomp: qidx = nq + i names the reverse complement of read i -- the minus strand;
+        without it everything is on the plus strand.  block: candidates per block of whole fragments (0: a few blocks per worker) -- the
+        output does not depend on it
+        -> (sel [nfrag] of MATES_DTYPE, records [nfrag, 2], uint32 CIGAR pool in (fragment, mate) order); orientation, rebase and out as
+        Context.align_windows_mates."""
+        orient = _orientation(orientation)
+        codes, off = packed if packed is not None else _pack(reads)
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1 or co.shape[0] % 2 != 1:
+            raise ValueError("cand_off must be a 1-D array of 2 nfrag + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        nf = (int(co.shape[0]) - 1) // 2
+        if nf > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[2 nfrag] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        if out is None:
+            sel = np.zeros(nf, dtype=MATES_DTYPE)
+            res = np.zeros((nf, 2), dtype=RESULT_DTYPE)
+        else:
+            sel, res = out
+            if sel.dtype != MATES_DTYPE or res.dtype != RESULT_DTYPE or sel.shape != (nf,) or res.shape != (nf, 2) or \
+                    not sel.flags["C_CONTIGUOUS"] or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be C-contiguous arrays: MATES_DTYPE [nfrag], RESULT_DTYPE [nfrag, 2]")
+        pool = _u32p()
+        words = C.c_int64(0)
+        rc = self.lib.ssw_gpu_pool_align_windows_mates(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1,
+                                                       1 if with_revcomp else 0, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
+                                                       ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                       int(block), C.byref(p), int(min_score), int(min_insert), int(max_insert),
+                                                       int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
+                                                       res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_pool_align_windows_mates: " + self.error())
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase and nf > 0:
+            _mates_rebase(sel, res, co, tb)
+        return sel, res, cig
 
     def stats(self):
         out = []

@@ -321,15 +321,26 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * Errors (-1 with a message that names the fragment or the pair, before anything is launched or written): a NULL array, cand_off[0] != 0,
  * a decreasing cand_off, a group of more than SSW_GPU_MATES_GROUP_MAX candidates (pos1 * n2 + pos2 has to fit the 32-bit half of a
  * selection key with room to spare), 2 * nfrag or the candidate count beyond 0x7fffff00, nfwd outside [0, queries->count], min_insert < 0
- * or min_insert > max_insert, unpaired_penalty outside 0 .. 65535, an index or window out of range (ssw_gpu_align_windows' text),
+ * or min_insert > max_insert, unpaired_penalty outside 0 .. 65535, an orientation outside 0 .. 2, an index or window out of range (ssw_gpu_align_windows' text),
  * sequences of another context.  nfrag == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for
  * ssw_gpu_align_windows.
  * ssw_gpu_last_timing: reduce_ms is the device time of k_matebest; best_flagged the winners handed to the reverse pass / traceback (at
  * most 2 * nfrag; 0 at flag 0).
- * Not provided (yet): a pool variant (it follows in a change of its own, cutting blocks at fragment borders); the C++ BatchAligner (its
- * window methods are forward-strand only); RF and FF library orientations; more than the best two combinations; a CLI option.
+ * Library orientation (ssw_gpu_align_windows_mates_lib; ssw_gpu_align_windows_mates is that call with SSW_GPU_MATES_FR): which strands
+ * and which order make a combination of a (mate 1) and b (mate 2) on one target proper.  D is the span that has to lie in
+ * min_insert .. max_insert:
+ *   SSW_GPU_MATES_FR   strands differ; p the plus-strand, m the minus-strand candidate:  D = E(m) - B(p) + 1   (reads point at each other)
+ *   SSW_GPU_MATES_RF   strands differ;                                                    D = E(p) - B(m) + 1   (the minus-strand mate upstream)
+ *   SSW_GPU_MATES_FF   strands equal;  both plus:  D = E(b) - B(a) + 1 (mate 1 upstream);  both minus:  D = E(a) - B(b) + 1 (mate 2 upstream)
+ * Nothing else depends on it: S, the ranking, n_proper's meaning, the one-mate case, the records and the CIGAR order.  In k_matebest it
+ * is one wave-uniform argument.  An orientation outside 0 .. 2 returns -1 with a message before anything is launched or written.
+ * Over several contexts or devices: ssw_gpu_pool_align_windows_mates below.  C++: BatchAligner::AlignWindowsMates (ssw_gpu_cpp.h).
+ * Not provided: more than the best two combinations; an insert-size likelihood; mate rescue; a CLI option.
  */
 #define SSW_GPU_MATES_GROUP_MAX 4096
+#define SSW_GPU_MATES_FR 0
+#define SSW_GPU_MATES_RF 1
+#define SSW_GPU_MATES_FF 2
 typedef struct {
 	int32_t pos1, pos2;          /* chosen candidate of mate 1 / mate 2, relative to its group's cand_off; -1: none */
 	int32_t n_eligible1, n_eligible2;
@@ -347,6 +358,14 @@ int ssw_gpu_align_windows_mates(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, c
                                 int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
                                 ssw_gpu_mates* sel, ssw_gpu_result* results,
                                 uint32_t** cigar_pool, int64_t* cigar_words);
+int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                                    const int64_t* cand_off, int64_t nfrag,
+                                    const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                    int32_t nfwd,
+                                    const ssw_gpu_params* params, int32_t min_score,
+                                    int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+                                    ssw_gpu_mates* sel, ssw_gpu_result* results,
+                                    uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
@@ -493,6 +512,28 @@ int ssw_gpu_pool_align_windows_topk(ssw_gpu_pool* pool,
         int64_t block, const ssw_gpu_params* params, int32_t k, int32_t min_score, int32_t max_drop,
         int32_t* pos, int32_t* n_eligible, ssw_gpu_result* results,
         uint32_t** cigar_pool, int64_t* cigar_words);
+/*
+ * ssw_gpu_align_windows_mates_lib over the pool, on the conventions above: the pool's target set, reads on the host, with_revcomp.
+ * Output: bit for bit what ONE context gives for ssw_gpu_align_windows_mates_lib over all the reads with nfwd = nq (with_revcomp: over
+ * ssw_gpu_seqs_with_revcomp of them; without it everything is on the plus strand) -- sel, both records per fragment, cigar_off and the
+ * words of the CIGAR pool, in (fragment, mate) order -- whatever the workers, whichever took which block, and whatever `block` is.
+ * Blocks: contiguous runs of WHOLE fragments; a block takes fragments until it holds at least `block` candidates, always at least one,
+ * empty fragments stay in the block they fall into; block <= 0 as for the other window calls, by candidate count.  A worker uploads the
+ * distinct forward reads of its block (m of them), renumbers qidx, rebases the block's 2 cnt + 1 offsets and calls the single-context
+ * entry point with nfwd = m; sel + f0 and results + 2 f0 are written in place.
+ * Errors (-1, text in ssw_gpu_pool_last_error, before any worker starts and before any output is written, naming the CALLER's fragment,
+ * mate or pair): every check of ssw_gpu_align_windows_mates_lib over the whole list -- a NULL array, no target set, cand_off[0] != 0, a
+ * decreasing cand_off, a group over SSW_GPU_MATES_GROUP_MAX, min_insert < 0 or > max_insert, unpaired_penalty outside 0 .. 65535, an
+ * orientation outside 0 .. 2 -- and the index and window checks of the other pool window calls.  nfrag == 0 returns 0 with
+ * *cigar_words = 0.  A failure inside a worker names worker, device and the block's range of fragments.  ssw_gpu_pool_stats as above.
+ */
+int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* pool,
+        const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+        const int64_t* cand_off, int64_t nfrag,
+        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+        int64_t block, const ssw_gpu_params* params, int32_t min_score,
+        int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+        ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
 /* per worker, accumulated over the last pool call: blocks taken, reads uploaded, DP cells (readLen x refLen), device milliseconds */
 typedef struct { int32_t device; int64_t blocks; int64_t queries; int64_t cells; double busy_ms; } ssw_gpu_pool_stat;
 int ssw_gpu_pool_stats(const ssw_gpu_pool* pool, int worker, ssw_gpu_pool_stat* out);

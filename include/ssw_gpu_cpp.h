@@ -367,6 +367,98 @@ class BatchAligner {
     free(pool);
   }
 
+  // The best candidate pair of every read pair (ssw_gpu_align_windows_mates_lib): reads holds 2 * nfrag strings, mate 1 of fragment f at
+  // 2 f and mate 2 at 2 f + 1, as the sequencer gives them; candidates[r] are the windows a mapper holds for reads[r], each on the strand
+  // it says (reverse: the read's reverse complement is what is aligned -- the minus strand).  The reads are uploaded once and their
+  // reverse complements built on the device (ssw_gpu_seqs_with_revcomp).  (*pairs)[f] is the selection of fragment f -- the candidate
+  // indices in candidates[2 f] / candidates[2 f + 1] (-1: none), how many were eligible, the pair score S, the second combination's S, the
+  // number of proper combinations and whether the chosen one is proper under `orientation` (SSW_GPU_MATES_FR / _RF / _FF) and
+  // min_insert .. max_insert; (*alignments)[r] is what AlignWindows gives for the aligned sequence against the chosen window (a default
+  // Alignment where nothing was chosen).  For a winner on the reverse strand the aligned sequence is the reverse complement of reads[r]:
+  // query_begin / query_end and the '=' / 'X' runs of cigar_string refer to it (DNA tables: codes 0 .. 3 are complemented, every other
+  // character is kept, as the device does).  rebase = true adds the chosen window's begin to the three reference positions.
+  struct MateWindow {
+    int32_t reference;
+    int64_t begin;
+    int32_t length;
+    bool reverse;
+  };
+  struct MatePair {
+    int32_t candidate1, candidate2;      // -1: none
+    int32_t eligible1, eligible2;
+    int32_t score, second_score;
+    int32_t proper_count;
+    bool proper;
+    uint16_t flag1, flag2;               // s_align flag of the two alignments
+  };
+  void AlignWindowsMates(const std::vector<std::string>& reads, const std::vector<std::vector<MateWindow> >& candidates, const Filter& filter,
+                         std::vector<Alignment>* alignments, std::vector<MatePair>* pairs, int32_t maskLen, int32_t min_insert, int32_t max_insert,
+                         int32_t unpaired_penalty, int32_t min_score = 0, int32_t orientation = SSW_GPU_MATES_FR, bool rebase = false) const {
+    if (!targets_) throw std::runtime_error("BatchAligner::AlignWindowsMates: no reference sequences");
+    if (reads.size() % 2 != 0) throw std::runtime_error("BatchAligner::AlignWindowsMates: two reads per fragment");
+    if (candidates.size() != reads.size()) throw std::runtime_error("BatchAligner::AlignWindowsMates: one candidate list per read");
+    const int32_t nr = (int32_t)reads.size(), nf = nr / 2;
+    alignments->assign(reads.size(), Alignment());
+    MatePair none; none.candidate1 = none.candidate2 = -1; none.eligible1 = none.eligible2 = 0; none.score = none.second_score = 0;
+    none.proper_count = 0; none.proper = false; none.flag1 = none.flag2 = 0;
+    pairs->assign((size_t)nf, none);
+    if (nf == 0) return;
+    std::string text; std::vector<int64_t> off(1, 0), cand_off(1, 0), tbeg;
+    std::vector<int32_t> qidx, tidx, tlen;
+    for (int32_t i = 0; i < nr; ++i) {
+      text += reads[(size_t)i]; off.push_back((int64_t)text.size());
+      for (size_t k = 0; k < candidates[(size_t)i].size(); ++k) {
+        const MateWindow& w = candidates[(size_t)i][k];
+        if (w.reference < 0 || w.reference >= n_targets_) throw std::runtime_error("BatchAligner::AlignWindowsMates: no such reference sequence");
+        qidx.push_back(w.reverse ? nr + i : i); tidx.push_back(w.reference); tbeg.push_back(w.begin); tlen.push_back(w.length);
+      }
+      cand_off.push_back((int64_t)qidx.size());
+    }
+    ssw_gpu_seqs* F = ssw_gpu_seqs_upload_ascii(ctx_, text.data(), off.data(), nr, table_.data());
+    if (!F) throw std::runtime_error(std::string("ssw_gpu_seqs_upload_ascii: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_seqs* Q = ssw_gpu_seqs_with_revcomp(ctx_, F);
+    ssw_gpu_seqs_free(F);
+    if (!Q) throw std::runtime_error(std::string("ssw_gpu_seqs_with_revcomp: ") + ssw_gpu_last_error(ctx_));
+    ssw_gpu_params p; memset(&p, 0, sizeof p);
+    p.mat = matrix_.data(); p.n = matrix_size_; p.gapO = gap_open_; p.gapE = gap_extend_;
+    p.flag = (uint8_t)((filter.report_begin_position ? 0x08 : 0) | (filter.report_cigar ? 0x0f : 0));
+    p.filters = filter.score_filter; p.filterd = filter.distance_filter; p.maskLen = std::max(maskLen, 15); p.score_size = 2;
+    std::vector<ssw_gpu_result> res((size_t)nr);
+    std::vector<ssw_gpu_mates> sel((size_t)nf);
+    uint32_t* pool = 0; int64_t words = 0;
+    const int rc = ssw_gpu_align_windows_mates_lib(ctx_, Q, targets_, cand_off.data(), nf, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), nr, &p,
+                                                   min_score, min_insert, max_insert, unpaired_penalty, orientation, sel.data(), res.data(), &pool, &words);
+    ssw_gpu_seqs_free(Q);
+    if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_windows_mates: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
+    for (int32_t f = 0; f < nf; ++f) {
+      const ssw_gpu_mates& s = sel[(size_t)f];
+      MatePair& m = (*pairs)[(size_t)f];
+      m.candidate1 = s.pos1; m.candidate2 = s.pos2; m.eligible1 = s.n_eligible1; m.eligible2 = s.n_eligible2;
+      m.score = s.score; m.second_score = s.second_score; m.proper_count = s.n_proper; m.proper = s.proper != 0;
+      for (int h = 0; h < 2; ++h) {
+        const int32_t pos = h ? s.pos2 : s.pos1, i = 2 * f + h;
+        if (pos < 0) continue;
+        const ssw_gpu_result& r = res[(size_t)i];
+        const size_t c = (size_t)(cand_off[(size_t)i] + pos);
+        Alignment& a = (*alignments)[(size_t)i];
+        a.sw_score = r.score1; a.sw_score_next_best = r.score2; a.ref_begin = r.ref_begin1; a.ref_end = r.ref_end1;
+        a.query_begin = r.read_begin1; a.query_end = r.read_end1; a.ref_end_next_best = r.ref_end2;
+        (h ? m.flag2 : m.flag1) = r.flag;
+        const int qlen = (int)reads[(size_t)i].size();
+        const std::string rcq = qidx[c] >= nr ? ReverseComplement(reads[(size_t)i]) : std::string();
+        Expand(a, r.cigarLen > 0 ? pool + r.cigar_off : 0, r.cigarLen, ref_codes_.data() + ref_off_[(size_t)tidx[c]] + tbeg[c],
+               qidx[c] >= nr ? rcq.data() : text.data() + off[(size_t)i], qlen);
+        if (rebase) {
+          const int32_t sh = (int32_t)tbeg[c];
+          if (a.ref_begin >= 0) a.ref_begin += sh;
+          if (a.ref_end >= 0) a.ref_end += sh;
+          if (a.ref_end_next_best >= 0) a.ref_end_next_best += sh;
+        }
+      }
+    }
+    free(pool);
+  }
+
   // A database search kept to its best hits (ssw_gpu_search_topk): (*hits)[i] holds, in rank order (sw_score descending, then reference
   // index ascending), up to k references of the set whose alignment with queries[i] scores > 0 and >= min_score -- each with the Alignment
   // and flag that AlignPairs gives for that pair.  maskLen < 15 is raised to 15 like there.
@@ -444,6 +536,22 @@ class BatchAligner {
     if (run > 0) Push(a, run, run_op);
     const int end = qlen - a.query_end - 1;
     if (end > 0) Push(a, (uint32_t)end, 'S');
+  }
+  // what the device's reverse complement of a read looks like as text: reversed, a character of code c in 0 .. 3 replaced by one of
+  // code 3 - c (A, C, G or T where the table knows them), every other character kept
+  std::string ReverseComplement(const std::string& s) const {
+    char comp[4];
+    for (int c = 0; c < 4; ++c) {
+      comp[c] = 0;
+      for (const char* k = "ACGT"; *k && !comp[c]; ++k) if (table_[(unsigned char)*k] == 3 - c) comp[c] = *k;
+      for (int k = 1; k < 128 && !comp[c]; ++k) if (table_[(size_t)k] == 3 - c) comp[c] = (char)k;
+    }
+    std::string out(s.rbegin(), s.rend());
+    for (size_t i = 0; i < out.size(); ++i) {
+      const int8_t c = table_[(unsigned char)out[i] & 127];
+      if (c >= 0 && c < 4 && comp[c]) out[i] = comp[c];
+    }
+    return out;
   }
   static void Push(Alignment& a, uint32_t len, char op) {
     a.cigar.push_back(to_cigar_int(len, op));
