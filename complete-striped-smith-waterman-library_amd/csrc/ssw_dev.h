@@ -489,6 +489,41 @@ typedef struct {
 	                                empty target where a mate has none */
 } ssw_matebest_args;
 
+/* Mate rescue (ssw_gpu_align_windows_mates_rescue): the groups of `m` are AUGMENTED -- the caller's candidates of a mate followed by
+   max_anchors rescue slots, which hold nothing yet.  For mate h of fragment f the kernel ranks the caller's candidates of the OTHER mate
+   (eligible, score1 >= anchor_min_score; score1 descending, position ascending), and for anchor r = 0 .. max_anchors - 1 that has no
+   proper partner among the caller's eligible candidates of mate h it writes the window a proper partner can occupy, clipped to the
+   anchor's target, into slot (2 f + h) * max_anchors + r; every other slot is written empty (tlen 0).  A non-empty slot is also entered
+   at its candidate position i = cand_off[2 f + h + 1] - max_anchors + r into k_matebest's side table and, where the call has one, into
+   the window table (as k_wintab would). */
+struct ssw_rescue_slot {     /* byte-for-byte the layout of ssw_gpu_rescued (include/ssw_gpu.h) */
+	int64_t tbeg;
+	int32_t tlen, tidx, qidx, anchor;
+};
+typedef struct {
+	ssw_matebest_args m;         /* k_matebest's inputs over the augmented list (sel / out unused) */
+	const int32_t* mate_q;       /* [2 nfrag]: forward read of mate h of fragment f at 2 f + h */
+	const int64_t* qoff;         /* offsets of the resident reads (lengths) */
+	const int64_t* toff;         /* offsets of the resident targets (clipping) */
+	int32_t nfwd;
+	int32_t max_anchors;         /* 1 .. SSW_RESCUE_ANCHORS_MAX */
+	int32_t anchor_min_score;
+	int32_t rescue_pad;
+	struct ssw_rescue_slot* slots;   /* [2 nfrag][max_anchors] */
+	int64_t* side_tbeg;          /* m.tbeg / m.tidx / m.len_strand, writable */
+	int32_t* side_tidx;
+	uint32_t* side_ls;
+	ssw_win* win;                /* optional: the call's window table (k_wintab's entry, written here for the slot) */
+} ssw_materescue_args;
+#define SSW_RESCUE_ANCHORS_MAX 8      /* SSW_GPU_RESCUE_ANCHORS_MAX */
+
+/* n 16-byte pieces from src to dst (the call-long record array of a select-mode call moving into a larger allocation) */
+typedef struct {
+	const void* src;
+	void* dst;
+	int64_t n16;
+} ssw_copy16_args;
+
 /* a subset of a sequence set, in any order and with repeats, gathered into a new set (dst offsets computed on the host) */
 typedef struct {
 	const int8_t* src;
@@ -591,6 +626,8 @@ int ssw_shim_launch_topk(const ssw_topk_args* a, void* stream);   /* one wavefro
 int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream);   /* one DPP row of 16 lanes per group */
 int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stream);   /* the same geometry, k ranks per group */
 int ssw_shim_launch_matebest(const ssw_matebest_args* a, void* stream);     /* one DPP row of 16 lanes per fragment (two groups) */
+int ssw_shim_launch_materescue(const ssw_materescue_args* a, void* stream); /* k_matebest's geometry */
+int ssw_shim_launch_copy16(const ssw_copy16_args* a, void* stream);
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 
 #ifdef __cplusplus

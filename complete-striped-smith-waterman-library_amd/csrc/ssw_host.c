@@ -28,6 +28,7 @@
 
 _Static_assert(sizeof(struct ssw_out_rec) == sizeof(ssw_gpu_result), "device record layout must equal ssw_gpu_result");
 _Static_assert(sizeof(struct ssw_mate_rec) == sizeof(ssw_gpu_mates) && sizeof(ssw_gpu_mates) == 32, "device selection layout must equal ssw_gpu_mates");
+_Static_assert(sizeof(struct ssw_rescue_slot) == sizeof(ssw_gpu_rescued) && sizeof(ssw_gpu_rescued) == 24, "device rescue slot layout must equal ssw_gpu_rescued");
 _Static_assert(SSW_MATES_GROUP_MAX == SSW_GPU_MATES_GROUP_MAX, "the kernel's group limit is the header's");
 _Static_assert(SSW_MATES_FR == SSW_GPU_MATES_FR && SSW_MATES_RF == SSW_GPU_MATES_RF && SSW_MATES_FF == SSW_GPU_MATES_FF, "the kernel's orientations are the header's");
 _Static_assert(sizeof(struct ssw_best_rec) == sizeof(ssw_gpu_best) && sizeof(ssw_gpu_best) == 16, "device record layout must equal ssw_gpu_best");
@@ -3094,6 +3095,10 @@ typedef struct {
 	const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel;
 	int32_t k, max_drop; int32_t* pos; int32_t* n_eligible;
 	ssw_gpu_mates* mates; int32_t nfwd, min_insert, max_insert, unpaired_penalty, orientation;
+	/* mate rescue (ssw_gpu_align_windows_mates_rescue; rescue_anchors == 0: none): the list is the augmented one, its four arrays are the
+	   entry point's own (r_*: the same memory, writable -- pairs_core enters the non-empty rescue slots), r_slots receives the slot table */
+	int32_t rescue_anchors, anchor_min_score, rescue_pad; const int32_t* mate_q;
+	int32_t* r_qidx; int32_t* r_tidx; int64_t* r_tbeg; int32_t* r_tlen; ssw_gpu_rescued* r_slots;
 } best_mode;
 /* device bytes of the per-group output behind the call-long record array: record + selection (64; mates: 48 + half of the fragment's 32) /
    k records, k positions and a count */
@@ -3121,53 +3126,70 @@ out:
 	return rc;
 }
 
-/* The pair list of the entry points, arguments checked by the caller: planning, launch loop, flagged phases, fallback and pool assembly.
-   They differ only in where a pair's target starts and how long it is (pair_src) -- and, with `bm` (select mode), in what happens to the
-   fill's records: they stay on the device in one call-long array, k_groupbest (k_grouptopk: the best k) selects per group after the last
-   fill launch, one record and one selection per group (k records and positions) come to the host, and only the winners go on to the
-   flagged phases.  The candidates outside the envelope take
-   the fallback at flag 0 FIRST (their records join the device array, so that the selection happens in one place) and, where they win and
-   flag != 0, once more with the caller's flag. */
-static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src,
-                      int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words,
-                      const best_mode* bm)
+/* the call-long record array of a select-mode call with room for `bytes`, its first `keep` bytes preserved (a rescue stage appends the
+   records of its windows behind those the selection of anchors has read: k_copy16 moves them when the allocation has to grow) */
+static unsigned char* brec_reserve(ssw_gpu_ctx* c, size_t keep, size_t bytes)
 {
-	const int32_t* const tidx = src->tidx;
-	if (cigar_pool) *cigar_pool = 0;
-	if (cigar_words) *cigar_words = 0;
-	memset(&c->tm, 0, sizeof c->tm);
-	if (np == 0) return 0;
-	const double t_start = wall_ms();
-	ssw_shim_set_device(c->device);
-	knobs_load(&c->kn);
+	dbuf* b = &c->brec;
+	if (keep == 0 || !b->p || b->cap >= bytes) return (unsigned char*)ensure(c, b, bytes);
+	const size_t want = bytes + bytes / 8 + 256;
+	void* p = ssw_shim_malloc(want);
+	if (!p) { fail(c, "device allocation failed: %s", ssw_shim_last_error()); return 0; }
+	ssw_copy16_args ca; memset(&ca, 0, sizeof ca);
+	ca.src = b->p; ca.dst = p; ca.n16 = (int64_t)((keep + 15) / 16);      /* (keep <= the old capacity, which ensure() rounds up by 256) */
+	if (ssw_shim_launch_copy16(&ca, c->stream) || ssw_shim_stream_sync(c->stream)) {
+		fail(c, "record array copy failed: %s", ssw_shim_last_error()); ssw_shim_free(p); return 0;
+	}
+	ssw_shim_free(b->p);
+	b->p = p; b->cap = want;
+	return (unsigned char*)p;
+}
 
-	int32_t minmat, maxmat, bias;
-	mat_range(prm, &minmat, &maxmat, &bias);
-	const int32_t n = prm->n;
-	/* (flagged pairs: the window kernels reach a job's target through a 64-bit base and keep their column indices relative to it, so the size
-	   of the resident set does not matter -- unlike the flagged database search's survivors) */
-	const int kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db;
-	/* the strip kernel's pair mode (k_chainq<R,pairs,..>): no max(mat) gate -- ssw_frame_params picks the form per bucket */
-	win_geom geom;
-	win_geom_fill(&geom, &c->kn, n);
-	const int long_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && !c->kn.no_db && geom.xlanes == 64 && geom.xrmax <= 16;
+/* what does not change between the sublists of one call: the scores' range and which fast paths the parameters allow */
+typedef struct { int32_t minmat, maxmat, bias; int kern_ok, long_ok; win_geom geom; } pair_env;
 
+/* what the plan + fill of a sublist leaves behind for the rest of the call (pairs_core) */
+typedef struct {
+	int64_t* perm; int64_t nk;          /* its pairs of k_fillpairs, by (R, target-length class) */
+	int64_t* fb; int64_t nfb;           /* ... outside both envelopes */
+	plong* lk; int64_t nlong;           /* ... of the strip kernel's pair mode */
+	int64_t* jix; int64_t nj;           /* the pair of either half of every job (-1: idle) */
+	ssw_gpu_result* stage;              /* (no select mode) the fill's records, two per job */
+	ssw_gpu_result* fbrec;              /* (select mode) the flag-0 records of `fb`, from the fallback */
+	unsigned char* d_brec; int8_t* d_mat;
+} pair_fill;
+static void pair_fill_free(pair_fill* pf)
+{
+	free(pf->perm); free(pf->fb); free(pf->lk); free(pf->jix); free(pf->stage); free(pf->fbrec);
+	memset(pf, 0, sizeof *pf);
+}
+
+/* Plan + fill of the sublist list[0 .. nl) of a pair list of np pairs (list == NULL: all of them): the classes go to key[] (the call's
+   array, one entry per pair of the LIST), the jobs are launched, and in select mode the records stay on the device from record rec0 of
+   the call-long array on -- two per job, then room for the fallback's, which come back in pf->fbrec --, records [0, rec0) preserved;
+   `rec_extra` more records and the per-group output fit behind them.  The window table covers all np pairs: it is built here unless
+   the call has one already (src->d_win). */
+static int pairs_fill(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src, int64_t np,
+                      const int64_t* list, int64_t nl, const ssw_gpu_params* prm, const pair_env* env, const best_mode* bm, uint32_t* key,
+                      int64_t rec0, int64_t rec_extra, pair_fill* pf, cigar_stage* st, call_acc* acc)
+{
+	const int32_t minmat = env->minmat, maxmat = env->maxmat, bias = env->bias, n = prm->n;
+	const int kern_ok = env->kern_ok, long_ok = env->long_ok;
+	const win_geom geom = env->geom;
 	/* ---- plan: counting sort of the kernel's pairs by (R, target-length class); the rest to the fallback list */
 	const int64_t nkeys = (int64_t)40 * PJ_TCLS;
 	int64_t* kcount = (int64_t*)calloc((size_t)nkeys + 1, sizeof(int64_t));
-	uint32_t* key = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)np);
-	int64_t* perm = (int64_t*)malloc(sizeof(int64_t) * (size_t)np);
+	int64_t* perm = (int64_t*)malloc(sizeof(int64_t) * (size_t)(nl > 0 ? nl : 1));
 	int64_t* fb = 0; int64_t nfb = 0;
 	plong* lk = 0; plong_bucket* lb = 0; int64_t nlong = 0; int nlb = 0;
 	ssw_pjob* jobs = 0; int64_t* jix = 0; ssw_gpu_result* stage = 0;
-	ssw_gpu_result* fbrec = 0; int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0;      /* select mode */
+	ssw_gpu_result* fbrec = 0;      /* select mode */
 	unsigned char* d_brec = 0; int8_t* d_mat = 0; int64_t nj = 0;
-	const int64_t nout = bm ? bm->ngroups * (bm->k ? bm->k : 1) : np;
-	cigar_stage st; memset(&st, 0, sizeof st);
-	call_acc acc; memset(&acc, 0, sizeof acc);
 	int rc = -1;
-	if (!kcount || !key || !perm) { fail(c, "out of host memory%s", ""); goto done; }
-	for (int64_t i = 0; i < np; ++i) {
+	memset(pf, 0, sizeof *pf);
+	if (!kcount || !perm) { fail(c, "out of host memory%s", ""); goto done; }
+	for (int64_t li = 0; li < nl; ++li) {
+		const int64_t i = list ? list[li] : li;
 		const int64_t ql = Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]], tl = ps_tlen(src, T, i);
 		const int R = (int)((ql + 15) / 16);
 		if (long_ok && ql >= PJ_LONG_MIN && ql <= PJ_LONG_MAX && tl >= 1 && tl <= 65000) {
@@ -3186,7 +3208,8 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 	if (nfb > 0) { fb = (int64_t*)malloc(sizeof(int64_t) * (size_t)nfb); if (!fb) { fail(c, "out of host memory%s", ""); goto done; } }
 	{
 		int64_t f = 0;
-		for (int64_t i = 0; i < np; ++i) {
+		for (int64_t li = 0; li < nl; ++li) {
+			const int64_t i = list ? list[li] : li;
 			if (key[i] == PJ_KEY_FALLBACK) fb[f++] = i;
 			else if (key[i] != PJ_KEY_LONG) perm[kcount[key[i]]++] = i;      /* kcount[k] ends as the end of class k */
 		}
@@ -3195,7 +3218,8 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		lk = (plong*)malloc(sizeof(plong) * (size_t)nlong); lb = (plong_bucket*)malloc(sizeof(plong_bucket) * (size_t)nlong);
 		if (!lk || !lb) { fail(c, "out of host memory%s", ""); goto done; }
 		int64_t f = 0;
-		for (int64_t i = 0; i < np; ++i) {
+		for (int64_t li = 0; li < nl; ++li) {
+			const int64_t i = list ? list[li] : li;
 			if (key[i] != PJ_KEY_LONG) continue;
 			int32_t P16q;
 			lk[f].len = (int32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]); lk[f].key = win_bucket_key(&geom, lk[f].len, &P16q);
@@ -3208,7 +3232,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		ssw_gpu_params p0 = *prm; p0.flag = 0;
 		fbrec = (ssw_gpu_result*)malloc(sizeof(ssw_gpu_result) * (size_t)nfb);
 		if (!fbrec) { fail(c, "out of host memory%s", ""); goto done; }
-		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, &st, &acc)) goto done;
+		if (best_fallback(c, Q, T, qidx, src, fb, nfb, &p0, fbrec, st, acc)) goto done;
 		memset(&c->tm, 0, sizeof c->tm);
 	}
 	if (nk + nlong > 0) {
@@ -3264,14 +3288,15 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		/* select mode: the records of ALL fill launches stay on the device (two per job, then the fallback's), followed by the per-group output.
 		   An input / output of the call like the window table, not scratch under the budget: 48 bytes per candidate; 64 per group, or with
 		   k ranks (ssw_gpu_align_windows_topk) 52 k + 4 per group */
-		if (bm && !(d_brec = (unsigned char*)ensure(c, &c->brec, sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb) + best_out_bytes(bm)))) goto done;
+		if (bm && !(d_brec = brec_reserve(c, sizeof(struct ssw_out_rec) * (size_t)rec0,
+		                                  sizeof(struct ssw_out_rec) * (size_t)(rec0 + 2 * nj + nfb + rec_extra) + best_out_bytes(bm)))) goto done;
 		d_mat = (int8_t*)d_hdr;
 		ssw_pjob* d_jobs = (ssw_pjob*)(d_hdr + hdr_mat);
 		c->nev = 0;
 		ssw_shim_event_record(c->ev_t0, c->stream);
 		if (ssw_shim_h2d(d_mat, prm->mat, (size_t)n * n, c->stream) || ssw_shim_h2d(d_jobs, jobs, sizeof(ssw_pjob) * (size_t)nj, c->stream) ||
 		    ssw_shim_memset(d_cnt, 0, DB_COUNTERS * sizeof(int32_t), c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
-		if (src->tbeg) {
+		if (src->tbeg && !src->d_win) {
 			/* the window table: the caller's three arrays go up as they are (16 bytes per pair), k_wintab adds the resident offsets */
 			unsigned char* d_w = (unsigned char*)ensure(c, &c->wtab, 32 * (size_t)np);
 			if (!d_w) goto done;
@@ -3301,7 +3326,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			if (jpl > jn) jpl = jn;
 			uint32_t* d_cm16 = (uint32_t*)ensure(c, &c->cm16, (size_t)(4 * stride * jpl));
 			uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
-			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
+			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec + rec0 : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
 			if (!d_cm16 || !d_cm8 || !d_out) goto done;
 			int32_t fr_base = 0, fr_kmask = 0;
 			const int fr = !c->kn.db_plain && ssw_frame_params(&c->kn, (int64_t)16 * R * maxmat, prm->gapO, prm->gapE, minmat, 16, &fr_base, &fr_kmask);
@@ -3343,7 +3368,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			uint32_t* d_cm8 = (uint32_t*)ensure(c, &c->cm8, (size_t)(4 * stride * jpl));
 			uint32_t* d_bnd = (uint32_t*)ensure(c, &c->bnd, (size_t)(16 * bcols * jpl));
 			int32_t* d_cand = (int32_t*)ensure(c, &c->cand, (size_t)(32 * jpl));
-			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
+			struct ssw_out_rec* d_out = bm ? (struct ssw_out_rec*)d_brec + rec0 : (struct ssw_out_rec*)ensure(c, &c->res, sizeof(struct ssw_out_rec) * 2 * (size_t)jpl);
 			if (!d_cm16 || !d_cm8 || !d_bnd || !d_cand || !d_out) goto done;
 			int32_t fr_base = 0, fr_kmask = 0;
 			const int xform = !c->kn.fill_plain && ssw_frame_params(&c->kn, (int64_t)B->P16 * (maxmat > 0 ? maxmat : 0), prm->gapO, prm->gapE, minmat, 64, &fr_base, &fr_kmask) ? 3 : 0;
@@ -3393,26 +3418,102 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (chainq_check(c)) goto done;      /* (the long class: a strip that gave up waiting, or a best cell that is not the maximum's first column) */
 		for (int e = 0; e + 1 < c->nev; e += 2) c->tm.fill_ms += ssw_shim_event_elapsed_ms(c->ev[e], c->ev[e + 1]);
 		c->tm.fill_cells = kcells; c->tm.n_word = cnt[0]; c->tm.n_byte = cnt[1];      /* (the reduction is fused into the fill: reduce_ms stays 0) */
-		if (!bm) {
-			/* the records of the pairs in job order (stage holds two per job; an idle high half is dropped) */
-			int64_t nrec = 0;
-			for (int64_t j = 0; j < nj; ++j)
-				for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
-			if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &st)) goto done;
-			for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
-			timing_add(&acc, &c->tm);
+	}
+	/* (select mode: a sublist without a fill launch still has its place in the record array) */
+	if (bm && !d_brec && !(d_brec = brec_reserve(c, sizeof(struct ssw_out_rec) * (size_t)rec0,
+	                                             sizeof(struct ssw_out_rec) * (size_t)(rec0 + nfb + rec_extra) + best_out_bytes(bm)))) goto done;
+	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
+		const int64_t i = perm[k]; acc->t.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
+	for (int64_t k = 0; k < nlong; ++k) acc->t.cells += (int64_t)lk[k].len * lk[k].tl;
+	pf->perm = perm; pf->nk = nk; pf->fb = fb; pf->nfb = nfb; pf->lk = lk; pf->nlong = nlong; pf->jix = jix; pf->nj = nj;
+	pf->stage = stage; pf->fbrec = fbrec; pf->d_brec = d_brec; pf->d_mat = d_mat;
+	perm = 0; fb = 0; lk = 0; jix = 0; stage = 0; fbrec = 0;
+	rc = 0;
+done:
+	free(kcount); free(perm); free(fb); free(lk); free(lb); free(jobs); free(jix); free(stage); free(fbrec);
+	return rc;
+}
+
+/* The pair list of the entry points, arguments checked by the caller: planning and launch loop (pairs_fill), flagged phases, fallback and
+   pool assembly.
+   They differ only in where a pair's target starts and how long it is (pair_src) -- and, with `bm` (select mode), in what happens to the
+   fill's records: they stay on the device in one call-long array, k_groupbest (k_grouptopk: the best k) selects per group after the last
+   fill launch, one record and one selection per group (k records and positions) come to the host, and only the winners go on to the
+   flagged phases.  The candidates outside the envelope take
+   the fallback at flag 0 FIRST (their records join the device array, so that the selection happens in one place) and, where they win and
+   flag != 0, once more with the caller's flag.
+   Mate rescue (bm->rescue_anchors = A > 0): the list is the AUGMENTED one -- the last A candidates of every group are rescue slots, empty
+   (tlen 0) on entry.  The first plan + fill covers the caller's candidates; k_materescue writes the slots; the non-empty ones are entered
+   into the list (the caller of pairs_core owns the four arrays) and take a second plan + fill, their records appended to the device
+   array; the empty ones share one all-zero record (score 0: never eligible); k_matebest and the flagged tail then see one list. */
+static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int32_t* qidx, pair_src* src,
+                      int64_t np, const ssw_gpu_params* prm, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words,
+                      const best_mode* bm)
+{
+	const int32_t* const tidx = src->tidx;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	memset(&c->tm, 0, sizeof c->tm);
+	if (np == 0) return 0;
+	const double t_start = wall_ms();
+	ssw_shim_set_device(c->device);
+	knobs_load(&c->kn);
+
+	pair_env env; memset(&env, 0, sizeof env);
+	mat_range(prm, &env.minmat, &env.maxmat, &env.bias);
+	const int32_t n = prm->n, minmat = env.minmat, maxmat = env.maxmat;
+	/* (flagged pairs: the window kernels reach a job's target through a 64-bit base and keep their column indices relative to it, so the size
+	   of the resident set does not matter -- unlike the flagged database search's survivors) */
+	env.kern_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && maxmat <= 49 && !c->kn.no_db;
+	/* the strip kernel's pair mode (k_chainq<R,pairs,..>): no max(mat) gate -- ssw_frame_params picks the form per bucket */
+	win_geom_fill(&env.geom, &c->kn, n);
+	env.long_ok = prm->gapO > prm->gapE && n <= SSW_MAX_N && !c->kn.no_db && env.geom.xlanes == 64 && env.geom.xrmax <= 16;
+
+	uint32_t* key = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)np);
+	pair_fill pf, pf2; memset(&pf, 0, sizeof pf); memset(&pf2, 0, sizeof pf2);
+	int32_t* slot = 0; int64_t* wlist = 0; ssw_gpu_result* wrec = 0; int64_t* rlist = 0;      /* select mode */
+	unsigned char* d_brec = 0; int8_t* d_mat = 0;
+	const int64_t nout = bm ? bm->ngroups * (bm->k ? bm->k : 1) : np;
+	const int32_t RA = bm ? bm->rescue_anchors : 0;
+	cigar_stage st; memset(&st, 0, sizeof st);
+	call_acc acc; memset(&acc, 0, sizeof acc);
+	int64_t nresc = 0; double rescue_ms = 0;
+	int rc = -1;
+	if (!key) { fail(c, "out of host memory%s", ""); goto done; }
+	int64_t nl1 = np;
+	if (RA) {      /* the caller's candidates; a rescue slot that stays empty never wins, its class does not matter */
+		rlist = (int64_t*)malloc(sizeof(int64_t) * (size_t)np);
+		if (!rlist) { fail(c, "out of host memory%s", ""); goto done; }
+		nl1 = 0;
+		for (int64_t g = 0; g < bm->ngroups; ++g) {
+			const int64_t e = bm->cand_off[g + 1] - RA;
+			for (int64_t i = bm->cand_off[g]; i < e; ++i) rlist[nl1++] = i;
+			for (int64_t i = e; i < e + RA; ++i) key[i] = PJ_KEY_FALLBACK;
 		}
+	}
+	if (pairs_fill(c, Q, T, qidx, src, np, RA ? rlist : 0, nl1, prm, &env, bm, key, 0, RA ? 1 : 0, &pf, &st, &acc)) goto done;
+	d_brec = pf.d_brec; d_mat = pf.d_mat;
+	const int64_t nj = pf.nj, nfb = pf.nfb;
+	int64_t* const jix = pf.jix; int64_t* const fb = pf.fb; ssw_gpu_result* const stage = pf.stage;
+	if (!bm && nj > 0) {
+		/* the records of the pairs in job order (stage holds two per job; an idle high half is dropped) */
+		int64_t nrec = 0;
+		for (int64_t j = 0; j < nj; ++j)
+			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) { stage[nrec] = stage[2 * j + h]; jix[nrec] = jix[2 * j + h]; ++nrec; }
+		if (prm->flag != 0 && pairs_flagged(c, Q, T, qidx, src, jix, stage, nrec, prm, d_mat, maxmat, minmat, &st)) goto done;
+		for (int64_t k = 0; k < nrec; ++k) results[jix[k]] = stage[k];
+		timing_add(&acc, &c->tm);
 	}
 	if (bm) {
 		/* ---- select: candidate -> record slot, k_groupbest (k_grouptopk, k_matebest), one selection + one record (k positions + k records) per group to the host */
 		const int64_t ng = bm->ngroups;
-		const size_t rec_bytes = sizeof(struct ssw_out_rec) * (size_t)(2 * nj + nfb);
-		if (!d_brec && !(d_brec = (unsigned char*)ensure(c, &c->brec, rec_bytes + best_out_bytes(bm)))) goto done;
+		int64_t nrecs = 2 * nj + nfb + (RA ? 1 : 0);      /* records of the call on the device (rescue: the last one is the empty slots') */
 		/* (4 bytes per candidate, 8 per group; mates: 16 more per candidate for the side table -- tbeg, tidx, length | strand) */
 		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + (bm->mates ? 20 : 4) * (size_t)np);
 		slot = (int32_t*)malloc(sizeof(int32_t) * (bm->mates ? 2 : 1) * (size_t)np);
 		if (!d_map) goto done;
 		if (!slot) { fail(c, "out of host memory%s", ""); goto done; }
+		if (RA) for (int64_t g = 0; g < ng; ++g) for (int64_t i = bm->cand_off[g + 1] - RA; i < bm->cand_off[g + 1]; ++i) slot[i] = (int32_t)(nrecs - 1);
 		for (int64_t j = 0; j < nj; ++j)
 			for (int h = 0; h < 2; ++h) if (jix[2 * j + h] >= 0) slot[jix[2 * j + h]] = (int32_t)(2 * j + h);
 		for (int64_t f = 0; f < nfb; ++f) slot[fb[f]] = (int32_t)(2 * nj + f);
@@ -3420,7 +3521,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		const struct ssw_out_rec* d_rec = (const struct ssw_out_rec*)d_brec;
 		const int64_t* d_off = (const int64_t*)d_map; const int64_t* d_tbeg = (const int64_t*)(d_map + 8 * ((size_t)ng + 1));      /* (mates only) */
 		const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1) + (bm->mates ? 8 * (size_t)np : 0));
-		unsigned char* d_sel = d_brec + rec_bytes;      /* best: [ng] records, [ng] selections; top-k: [nout] records, [nout] positions, [ng] counts */
+		ssw_gpu_result* const fbrec = pf.fbrec;
 		if ((nfb > 0 && ssw_shim_h2d((void*)(d_rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
 		    ssw_shim_h2d((void*)d_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)d_slot, slot, 4 * (size_t)np, c->stream)) {
 			fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
@@ -3431,6 +3532,57 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			if (ssw_shim_h2d((void*)d_tbeg, src->tbeg, 8 * (size_t)np, c->stream) || ssw_shim_h2d((void*)(d_slot + np), tidx, 4 * (size_t)np, c->stream) ||
 			    ssw_shim_h2d((void*)(d_slot + 2 * np), ls, 4 * (size_t)np, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
 		}
+		if (RA) {
+			/* ---- rescue: k_materescue over the caller's candidates, the slot table (24 bytes per slot) to the host, the non-empty slots
+			   through a plan + fill of their own behind the records the device holds */
+			unsigned char* d_rs = (unsigned char*)ensure(c, &c->res, sizeof(ssw_gpu_rescued) * (size_t)ng * RA + 4 * (size_t)ng);
+			if (!d_rs) goto done;
+			ssw_materescue_args ra; memset(&ra, 0, sizeof ra);
+			ra.m.rec = d_rec; ra.m.cand_off = d_off; ra.m.slot = d_slot; ra.m.tbeg = d_tbeg; ra.m.tidx = d_slot + np; ra.m.len_strand = (const uint32_t*)(d_slot + 2 * np);
+			ra.m.nfrag = ng / 2; ra.m.min_score = bm->min_score; ra.m.min_insert = bm->min_insert; ra.m.max_insert = bm->max_insert;
+			ra.m.unpaired_penalty = bm->unpaired_penalty; ra.m.orientation = bm->orientation;
+			ra.slots = (struct ssw_rescue_slot*)d_rs; ra.mate_q = (const int32_t*)(d_rs + sizeof(ssw_gpu_rescued) * (size_t)ng * RA);
+			ra.qoff = Q->d_off; ra.toff = T->d_off; ra.nfwd = bm->nfwd; ra.max_anchors = RA; ra.anchor_min_score = bm->anchor_min_score;
+			ra.rescue_pad = bm->rescue_pad; ra.side_tbeg = (int64_t*)d_tbeg; ra.side_tidx = (int32_t*)(d_slot + np); ra.side_ls = (uint32_t*)(d_slot + 2 * np);
+			ra.win = (ssw_win*)src->d_win;
+			void* e0 = next_event(c); void* e1 = next_event(c);
+			if (ssw_shim_memset((void*)(d_rec + (nrecs - 1)), 0, sizeof(struct ssw_out_rec), c->stream) ||
+			    ssw_shim_h2d((void*)ra.mate_q, bm->mate_q, 4 * (size_t)ng, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(e0, c->stream);
+			if (ssw_shim_launch_materescue(&ra, c->stream)) { fail(c, "materescue launch failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(e1, c->stream);
+			if (ssw_shim_d2h(bm->r_slots, ra.slots, sizeof(ssw_gpu_rescued) * (size_t)ng * RA, c->stream) || ssw_shim_stream_sync(c->stream)) {
+				fail(c, "result download failed: %s", ssw_shim_last_error()); goto done;
+			}
+			rescue_ms = ssw_shim_event_elapsed_ms(e0, e1);
+			for (int64_t g = 0; g < ng; ++g)
+				for (int32_t r = 0; r < RA; ++r) {
+					const ssw_gpu_rescued* s = &bm->r_slots[g * RA + r];
+					if (s->tlen <= 0) continue;
+					const int64_t i = bm->cand_off[g + 1] - RA + r;
+					bm->r_qidx[i] = s->qidx; bm->r_tidx[i] = s->tidx; bm->r_tbeg[i] = s->tbeg; bm->r_tlen[i] = s->tlen;
+					rlist[nresc++] = i;
+				}
+			if (nresc > 0) {
+				timing_add(&acc, &c->tm);
+				memset(&c->tm, 0, sizeof c->tm);
+				const int64_t rec0 = nrecs;
+				if (pairs_fill(c, Q, T, qidx, src, np, rlist, nresc, prm, &env, bm, key, rec0, 0, &pf2, &st, &acc)) goto done;
+				d_brec = pf2.d_brec; d_rec = (const struct ssw_out_rec*)d_brec;
+				if (pf2.d_mat) d_mat = pf2.d_mat;
+				else if (d_mat) {      /* (the fallback's nested calls used the workspace the matrix of the first fill lay in) */
+					if (!(d_mat = (int8_t*)ensure(c, &c->pairs, ((size_t)n * n + 15) / 16 * 16))) goto done;
+					if (ssw_shim_h2d(d_mat, prm->mat, (size_t)n * n, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+				}
+				for (int64_t j = 0; j < pf2.nj; ++j)
+					for (int h = 0; h < 2; ++h) if (pf2.jix[2 * j + h] >= 0) slot[pf2.jix[2 * j + h]] = (int32_t)(rec0 + 2 * j + h);
+				for (int64_t f = 0; f < pf2.nfb; ++f) slot[pf2.fb[f]] = (int32_t)(rec0 + 2 * pf2.nj + f);
+				nrecs = rec0 + 2 * pf2.nj + pf2.nfb;
+				if ((pf2.nfb > 0 && ssw_shim_h2d((void*)(d_rec + rec0 + 2 * pf2.nj), pf2.fbrec, sizeof(ssw_gpu_result) * (size_t)pf2.nfb, c->stream)) ||
+				    ssw_shim_h2d((void*)d_slot, slot, 4 * (size_t)np, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+			}
+		}
+		unsigned char* d_sel = d_brec + sizeof(struct ssw_out_rec) * (size_t)nrecs;      /* best: [ng] records, [ng] selections; top-k: [nout] records, [nout] positions, [ng] counts */
 		ssw_shim_event_record(c->ev_a, c->stream);
 		if (bm->mates) {
 			ssw_matebest_args ma; memset(&ma, 0, sizeof ma);
@@ -3463,7 +3615,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			if (ssw_shim_d2h(results, ga.out, sizeof(ssw_gpu_result) * (size_t)ng, c->stream) || ssw_shim_d2h(bm->sel, ga.sel, sizeof(ssw_gpu_best) * (size_t)ng, c->stream) ||
 			    ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
 		}
-		c->tm.reduce_ms = ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+		c->tm.reduce_ms = rescue_ms + ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);      /* (rescue_ms: k_materescue; 0 without a rescue stage) */
 		/* ---- the winners alone go on: the fused path's through the reverse pass and the traceback (their fill records reused), the others
 		   through the fallback once more with the caller's flag.  One survivor list over all output slots; top-k: every slot that holds a
 		   candidate (pairs_flagged applies the reference's gate, and takes the fill's word mark out of the records it leaves alone) */
@@ -3508,15 +3660,13 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		if (cigar_pool) *cigar_pool = pool;
 		if (cigar_words) *cigar_words = w;
 	}
-	for (int64_t k = 0; k < nk; ++k) {      /* (the fallback's cells came with its batches) */
-		const int64_t i = perm[k]; acc.t.cells += (Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) * ps_tlen(src, T, i); }
-	for (int64_t k = 0; k < nlong; ++k) acc.t.cells += (int64_t)lk[k].len * lk[k].tl;
+	acc.t.rescue_windows = nresc;
 	acc.t.total_ms = wall_ms() - t_start;
 	c->tm = acc.t;
 	rc = 0;
 done:
-	free(kcount); free(key); free(perm); free(fb); free(lk); free(lb); free(jobs); free(jix); free(stage); free(st.words);
-	free(fbrec); free(slot); free(wlist); free(wrec);
+	pair_fill_free(&pf); pair_fill_free(&pf2);
+	free(key); free(st.words); free(slot); free(wlist); free(wrec); free(rlist);
 	return rc;
 }
 
@@ -3718,53 +3868,76 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
  * ------------------------------------------------------------------------------------------------ */
 static void mates_pad(ssw_gpu_mates* m) { memset(m, 0, sizeof *m); m->pos1 = m->pos2 = -1; }
 
-static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
-                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
-                                      const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
-                                      int32_t orientation, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+/* "<who>: <what> (<detail>)" */
+static int fail_who_d(ssw_gpu_ctx* c, const char* who, const char* what, const char* detail)
+{
+	char msg[400];
+	snprintf(msg, sizeof msg, "%s: %s (%s)", who, what, detail);
+	return fail(c, "%s", msg);
+}
+
+/* the argument checks of ssw_gpu_align_windows_mates_lib, shared with the rescue entry point: -1 refused (message written), 1 no fragments
+   (nothing to do), 0 go on with *np_out candidates */
+static int mates_check(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+                       const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                       const ssw_gpu_params* prm, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+                       const void* sel, const void* results, int64_t* np_out)
 {
 	char msg[200];
-	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
-	if (cigar_words) *cigar_words = 0;
-	if (nf < 0 || (nf > 0 && (!cand_off || !sel || !results))) return fail(c, "align_windows_mates: NULL argument%s", "");
-	if (check_common(c, "align_windows_mates", Q, T, prm)) return -1;
-	if (nf == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }
+	if (nf < 0 || (nf > 0 && (!cand_off || !sel || !results))) return fail_who(c, who, "NULL argument");
+	if (check_common(c, who, Q, T, prm)) return -1;
+	if (nf == 0) { memset(&c->tm, 0, sizeof c->tm); return 1; }
 	if (nf > 0x7fffff00 / 2) {
 		snprintf(msg, sizeof msg, "%lld fragments", (long long)nf);
-		return fail(c, "align_windows_mates: more than 2^31 output slots in one call (%s)", msg);
+		return fail_who_d(c, who, "more than 2^31 output slots in one call", msg);
 	}
 	if (min_insert < 0 || min_insert > max_insert) {
 		snprintf(msg, sizeof msg, "min_insert = %d, max_insert = %d", min_insert, max_insert);
-		return fail(c, "align_windows_mates: 0 <= min_insert <= max_insert required (%s)", msg);
+		return fail_who_d(c, who, "0 <= min_insert <= max_insert required", msg);
 	}
 	if (unpaired_penalty < 0 || unpaired_penalty > 65535) {
 		snprintf(msg, sizeof msg, "unpaired_penalty = %d", unpaired_penalty);
-		return fail(c, "align_windows_mates: unpaired_penalty must be 0 .. 65535 (%s)", msg);
+		return fail_who_d(c, who, "unpaired_penalty must be 0 .. 65535", msg);
 	}
 	if (orientation < SSW_GPU_MATES_FR || orientation > SSW_GPU_MATES_FF) {
 		snprintf(msg, sizeof msg, "orientation = %d", orientation);
-		return fail(c, "align_windows_mates: orientation must be SSW_GPU_MATES_FR, _RF or _FF (%s)", msg);
+		return fail_who_d(c, who, "orientation must be SSW_GPU_MATES_FR, _RF or _FF", msg);
 	}
 	if (nfwd < 0 || nfwd > Q->count) {
 		snprintf(msg, sizeof msg, "nfwd = %d, %d queries", nfwd, Q->count);
-		return fail(c, "align_windows_mates: nfwd outside the query set (%s)", msg);
+		return fail_who_d(c, who, "nfwd outside the query set", msg);
 	}
 	if (cand_off[0] != 0) {
 		snprintf(msg, sizeof msg, "fragment 0 starts at candidate %lld", (long long)cand_off[0]);
-		return fail(c, "align_windows_mates: cand_off[0] must be 0 (%s)", msg);
+		return fail_who_d(c, who, "cand_off[0] must be 0", msg);
 	}
 	const int64_t ng = 2 * nf;
 	for (int64_t g = 0; g < ng; ++g) {
 		const int64_t sz = cand_off[g + 1] - cand_off[g];
 		if (sz >= 0 && sz <= SSW_GPU_MATES_GROUP_MAX) continue;
 		snprintf(msg, sizeof msg, "fragment %lld, mate %d: candidates [%lld, %lld)", (long long)(g >> 1), (int)(g & 1) + 1, (long long)cand_off[g], (long long)cand_off[g + 1]);
-		return sz < 0 ? fail(c, "align_windows_mates: cand_off decreases (%s)", msg)
-		              : fail(c, "align_windows_mates: more than 4096 candidates in a group (%s)", msg);
+		return fail_who_d(c, who, sz < 0 ? "cand_off decreases" : "more than 4096 candidates in a group", msg);
 	}
 	const int64_t np = cand_off[ng];
-	if (np > 0x7fffff00) return fail(c, "align_windows_mates: %s", "more than 2^31 candidates in one call");
-	if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) return fail(c, "align_windows_mates: NULL argument%s", "");
-	if (windows_check(c, "align_windows_mates", Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
+	if (np > 0x7fffff00) return fail_who(c, who, "more than 2^31 candidates in one call");
+	if (np > 0 && (!qidx || !tidx || !tbeg || !tlen)) return fail_who(c, who, "NULL argument");
+	if (windows_check(c, who, Q, T, qidx, tidx, tbeg, tlen, np)) return -1;
+	*np_out = np;
+	return 0;
+}
+
+static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                      const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
+                                      int32_t orientation, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
+	if (cigar_words) *cigar_words = 0;
+	int64_t np = 0;
+	const int chk = mates_check(c, "align_windows_mates", Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm, min_insert, max_insert, unpaired_penalty,
+	                            orientation, sel, results, &np);
+	if (chk) return chk < 0 ? -1 : 0;
+	const int64_t ng = 2 * nf;
 	if (np == 0) {      /* empty groups only */
 		memset(&c->tm, 0, sizeof c->tm);
 		for (int64_t g = 0; g < ng; ++g) topk_pad(&results[g]);
@@ -3798,6 +3971,116 @@ int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
 {
 	return ssw_gpu_align_windows_mates_lib(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
 	                                       unpaired_penalty, SSW_GPU_MATES_FR, sel, results, cigar_pool, cigar_words);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Mate rescue (ssw_gpu_align_windows_mates_rescue): ssw_gpu_align_windows_mates_lib over the AUGMENTED list -- every group followed by
+ * max_anchors rescue slots, which k_materescue fills on the device from the other mate's best candidates (pairs_core's rescue stage).
+ * The augmented list is built here, with the slots empty; pairs_core enters the windows of the non-empty ones.  Device state beyond
+ * the mates call's: 24 bytes per slot, 4 of mate_q per group, and the records and maps of the slots like any other candidate's.
+ * ------------------------------------------------------------------------------------------------ */
+static int align_windows_mates_rescue_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+                                             const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                             const int32_t* mate_q, const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert,
+                                             int32_t unpaired_penalty, int32_t orientation, int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
+                                             ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	static const char who[] = "align_windows_mates_rescue";
+	char msg[240];
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	int64_t np = 0;
+	const int chk = mates_check(c, who, Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm, min_insert, max_insert, unpaired_penalty, orientation,
+	                            sel, results, &np);
+	if (chk) return chk < 0 ? -1 : 0;
+	if (!mate_q || !origin) return fail_who(c, who, "NULL argument");
+	if ((int64_t)Q->count != 2 * (int64_t)nfwd) {
+		snprintf(msg, sizeof msg, "nfwd = %d, %d queries", nfwd, Q->count);
+		return fail_who_d(c, who, "queries->count must be 2 * nfwd, the reverse complements resident", msg);
+	}
+	if (max_anchors < 1 || max_anchors > SSW_GPU_RESCUE_ANCHORS_MAX) {
+		snprintf(msg, sizeof msg, "max_anchors = %d", max_anchors);
+		return fail_who_d(c, who, "max_anchors must be 1 .. 8", msg);
+	}
+	if (rescue_pad < 0 || rescue_pad > 65535) {
+		snprintf(msg, sizeof msg, "rescue_pad = %d", rescue_pad);
+		return fail_who_d(c, who, "rescue_pad must be 0 .. 65535", msg);
+	}
+	if (anchor_min_score < 0) {
+		snprintf(msg, sizeof msg, "anchor_min_score = %d", anchor_min_score);
+		return fail_who_d(c, who, "anchor_min_score must be >= 0", msg);
+	}
+	const int64_t ng = 2 * nf, A = max_anchors;
+	for (int64_t g = 0; g < ng; ++g) {
+		const int64_t sz = cand_off[g + 1] - cand_off[g];
+		if (mate_q[g] < 0 || mate_q[g] >= nfwd) {
+			snprintf(msg, sizeof msg, "fragment %lld, mate %d: mate_q = %d, nfwd = %d", (long long)(g >> 1), (int)(g & 1) + 1, mate_q[g], nfwd);
+			return fail_who_d(c, who, "mate_q outside the forward reads", msg);
+		}
+		if (sz + A > SSW_GPU_MATES_GROUP_MAX) {
+			snprintf(msg, sizeof msg, "fragment %lld, mate %d: %lld candidates + %d rescue slots", (long long)(g >> 1), (int)(g & 1) + 1, (long long)sz, max_anchors);
+			return fail_who_d(c, who, "more than 4096 candidates and rescue slots in a group", msg);
+		}
+		for (int64_t i = cand_off[g]; i < cand_off[g + 1]; ++i)
+			if (qidx[i] != mate_q[g] && qidx[i] != nfwd + mate_q[g]) {
+				snprintf(msg, sizeof msg, "pair %lld of fragment %lld, mate %d: query %d, mate_q = %d, nfwd = %d", (long long)i, (long long)(g >> 1), (int)(g & 1) + 1,
+				         qidx[i], mate_q[g], nfwd);
+				return fail_who_d(c, who, "a candidate's query is neither strand of its mate's read", msg);
+			}
+	}
+	const int64_t npa = np + ng * A;
+	if (npa > 0x7fffff00) return fail_who(c, who, "more than 2^31 candidates and rescue slots in one call");
+	/* the augmented list: group g = the caller's candidates, then A empty slots (tlen 0) on the mate's forward read */
+	int64_t* off_a = (int64_t*)malloc(sizeof(int64_t) * ((size_t)ng + 1 + (size_t)npa));
+	int32_t* q_a = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)npa);
+	ssw_gpu_rescued* slots = (ssw_gpu_rescued*)malloc(sizeof(ssw_gpu_rescued) * (size_t)(ng * A));
+	int rc = -1;
+	if (!off_a || !q_a || !slots) { fail(c, "out of host memory%s", ""); goto out; }
+	int64_t* b_a = off_a + ng + 1; int32_t* t_a = q_a + npa; int32_t* l_a = q_a + 2 * npa;
+	off_a[0] = 0;
+	for (int64_t g = 0; g < ng; ++g) {
+		const int64_t c0 = cand_off[g], sz = cand_off[g + 1] - c0, a0 = off_a[g];
+		if (sz > 0) {
+			memcpy(q_a + a0, qidx + c0, sizeof(int32_t) * (size_t)sz); memcpy(t_a + a0, tidx + c0, sizeof(int32_t) * (size_t)sz);
+			memcpy(b_a + a0, tbeg + c0, sizeof(int64_t) * (size_t)sz); memcpy(l_a + a0, tlen + c0, sizeof(int32_t) * (size_t)sz);
+		}
+		for (int64_t i = a0 + sz; i < a0 + sz + A; ++i) { q_a[i] = mate_q[g]; t_a[i] = 0; b_a[i] = 0; l_a[i] = 0; }
+		off_a[g + 1] = a0 + sz + A;
+	}
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = t_a; src.tbeg = b_a; src.tlen = l_a; src.who = who;
+	best_mode bm; memset(&bm, 0, sizeof bm);
+	bm.cand_off = off_a; bm.ngroups = ng; bm.min_score = min_score; bm.mates = sel;
+	bm.nfwd = nfwd; bm.min_insert = min_insert; bm.max_insert = max_insert; bm.unpaired_penalty = unpaired_penalty;
+	bm.orientation = orientation;
+	bm.rescue_anchors = max_anchors; bm.anchor_min_score = anchor_min_score; bm.rescue_pad = rescue_pad; bm.mate_q = mate_q;
+	bm.r_qidx = q_a; bm.r_tidx = t_a; bm.r_tbeg = b_a; bm.r_tlen = l_a; bm.r_slots = slots;
+	rc = pairs_core(c, Q, T, q_a, &src, npa, prm, results, cigar_pool, cigar_words, &bm);
+	if (rc == 0)
+		for (int64_t g = 0; g < ng; ++g) {
+			const int32_t pos = g & 1 ? sel[g >> 1].pos2 : sel[g >> 1].pos1;
+			ssw_gpu_rescued* o = &origin[g];
+			if (pos < 0) { o->tbeg = 0; o->tlen = 0; o->tidx = -1; o->qidx = -1; o->anchor = -1; continue; }
+			const int64_t i = off_a[g] + pos, sz = cand_off[g + 1] - cand_off[g];
+			o->tbeg = b_a[i]; o->tlen = l_a[i]; o->tidx = t_a[i]; o->qidx = q_a[i];
+			o->anchor = pos >= sz ? slots[g * A + (pos - sz)].anchor : -1;
+		}
+out:
+	free(off_a); free(q_a); free(slots);
+	return rc;
+}
+
+int ssw_gpu_align_windows_mates_rescue(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                                       const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                       const int32_t* mate_q, const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert,
+                                       int32_t unpaired_penalty, int32_t orientation, int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
+                                       ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!c) return fail(0, "align_windows_mates_rescue: NULL context%s", "");
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	return ctx_leave(c, align_windows_mates_rescue_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, mate_q, prm, min_score, min_insert,
+	                                                      max_insert, unpaired_penalty, orientation, max_anchors, anchor_min_score, rescue_pad,
+	                                                      sel, results, origin, cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------

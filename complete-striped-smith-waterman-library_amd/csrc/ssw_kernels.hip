@@ -4529,6 +4529,111 @@ __global__ void __launch_bounds__(256) k_matebest(ssw_matebest_args a)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * k_materescue (ssw_materescue_args): the rescue windows of every fragment (ssw_gpu_align_windows_mates_rescue), on k_matebest's geometry
+ * and digests -- one DPP row of 16 lanes per fragment, the same 24-byte digests in the same 18 KiB of LDS (fragments of more than
+ * MB_LDS_CAND augmented candidates form them again when needed).  The groups are augmented: the last max_anchors positions of either
+ * group are the rescue slots, which hold nothing yet and are neither formed nor read here.
+ * Per mate h (0, 1) and rank r (0 .. max_anchors - 1; both loops are wavefront-uniform, so every lane meets every rotation):
+ *   the anchor is the maximum key score1 << 32 | ~position STRICTLY BELOW rank r - 1's among the caller's candidates of mate 1 - h with
+ *   score1 >= max(min_score, anchor_min_score, 1) (k_grouptopk's selection by repeated maximum); the lanes then stride over the caller's
+ *   eligible candidates of mate h for a proper partner of it (mb_proper), an OR over the row; lane 0 writes the slot: empty when there is
+ *   no anchor or it has a partner, else the columns a proper partner can occupy -- [B + mn - L - P, B + mx - 1 + P] where the rescued
+ *   mate lies downstream of the anchor, [E + 1 - mx - P, E - mn + L + P] upstream (mb_proper's choice of the downstream one) -- clipped
+ *   to the anchor's target; fewer than one column: empty.  A non-empty slot goes into the side table and the window table as well.
+ * No atomics, no waiting; the LDS hand-off stays inside a wavefront (wave_lds_fence).
+ * ------------------------------------------------------------------------------------------------ */
+__global__ void __launch_bounds__(256) k_materescue(ssw_materescue_args a)
+{
+	SSW_DYN_LDS(lds);
+	const ssw_matebest_args& m = a.m;
+	const int64_t f = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;      /* (a row is inside the list or outside it as a whole) */
+	const int l = (int)threadIdx.x & 15;
+	const u32 base = ((u32)threadIdx.x >> 4) * (u32)(MB_LDS_CAND * MB_DIGEST);
+	const bool live = f < m.nfrag;
+	const int lo = m.min_score > 1 ? m.min_score : 1;
+	const u32 alo = (u32)(a.anchor_min_score > lo ? a.anchor_min_score : lo);
+	const int A = a.max_anchors;
+	int64_t c0 = 0;
+	int n1 = 0, n2 = 0;      /* augmented sizes: the caller's candidates are positions 0 .. n - A - 1 of either group */
+	bool in_lds = false;
+	if (live) {
+		c0 = m.cand_off[2 * f];
+		const int64_t c1 = m.cand_off[2 * f + 1];
+		n1 = (int)(c1 - c0); n2 = (int)(m.cand_off[2 * f + 2] - c1);
+		in_lds = n1 + n2 <= MB_LDS_CAND;
+		if (in_lds)
+			for (int p = l; p < n1 + n2; p += 16) {
+				if (p >= n1 - A && (p < n1 || p >= n1 + n2 - A)) continue;      /* a rescue slot */
+				const mb_dig d = mb_form(m, c0 + p, lo);
+				const u32 off = base + (u32)p * MB_DIGEST;
+				lds_st32(lds, off, d.s); lds_st32(lds, off + 4, d.ts);
+				lds_st32(lds, off + 8, (u32)(unsigned long long)d.E); lds_st32(lds, off + 12, (u32)((unsigned long long)d.E >> 32));
+				lds_st32(lds, off + 16, (u32)(unsigned long long)d.EL); lds_st32(lds, off + 20, (u32)((unsigned long long)d.EL >> 32));
+			}
+	}
+	wave_lds_fence();      /* the row's digests are in LDS before any of its lanes reads another lane's */
+	for (int h = 0; h < 2; ++h) {
+		/* digests of the rescued mate's group start at hg0, the anchors' at og0; nh / no: the caller's candidates of either */
+		const int hg0 = h ? n1 : 0, og0 = h ? 0 : n1, nh = (h ? n2 : n1) - A, no = (h ? n1 : n2) - A;
+		unsigned long long prev = ~0ull;
+		for (int r = 0; r < A; ++r) {
+			unsigned long long key = 0;
+			if (live)
+				for (int p = l; p < no; p += 16) {
+					const mb_dig d = mb_get(m, lds, base, in_lds, c0, og0 + p, lo);
+					const unsigned long long k = ((unsigned long long)d.s << 32) | (u32)~(u32)p;
+					if (d.s >= alo && k < prev && k > key) key = k;
+				}
+			key = gt_rowmax<8>(key); key = gt_rowmax<4>(key); key = gt_rowmax<2>(key); key = gt_rowmax<1>(key);
+			prev = key;      /* (0: no anchor of this rank, and none of a later one -- no key lies below 0) */
+			const int apos = (int)~(u32)key;
+			mb_dig da; da.s = 0; da.ts = 0; da.E = 0; da.EL = 0;
+			u32 found = 0;
+			if (live && key) {
+				da = mb_get(m, lds, base, in_lds, c0, og0 + apos, lo);
+				for (int p = l; p < nh; p += 16) {
+					const mb_dig db = mb_get(m, lds, base, in_lds, c0, hg0 + p, lo);
+					if (db.s && (h ? mb_proper(m, da, db) : mb_proper(m, db, da))) found = 1;
+				}
+			}
+			found |= xl_row_ror<8>(found); found |= xl_row_ror<4>(found); found |= xl_row_ror<2>(found); found |= xl_row_ror<1>(found);
+			if (!live || l != 0) continue;
+			const int32_t q = a.mate_q[2 * f + h];
+			ssw_rescue_slot s;
+			s.tbeg = 0; s.tlen = 0; s.tidx = 0; s.qidx = q; s.anchor = -1;
+			if (key && !found) {
+				const u32 sa = da.ts >> 31, sr = m.orientation == SSW_MATES_FF ? sa : sa ^ 1u;      /* strand of the anchor / of a proper partner */
+				const int32_t t = (int32_t)(da.ts & 0x7fffffffu);
+				const long long L = (long long)(a.qoff[q + 1] - a.qoff[q]), P = a.rescue_pad, mn = m.min_insert, mx = m.max_insert;
+				/* mb_proper: mate 1 is the downstream one exactly when its strand bit differs from "RF" */
+				const u32 down1 = (h ? sa : sr) ^ (u32)(m.orientation == SSW_MATES_RF);
+				const bool down = h ? !down1 : down1 != 0;
+				long long w0 = down ? da.EL + 1 + mn - L - P : da.E + 1 - mx - P;
+				long long w1 = down ? da.EL + 1 + mx - 1 + P : da.E - mn + L + P;
+				const long long tl = (long long)(a.toff[t + 1] - a.toff[t]);
+				if (w0 < 0) w0 = 0;
+				if (w1 > tl - 1) w1 = tl - 1;
+				if (w1 - w0 > 0x7ffffffell) w1 = w0 + 0x7ffffffell;      /* (a window has a 32-bit length) */
+				if (w1 >= w0) {
+					s.tbeg = w0; s.tlen = (int32_t)(w1 - w0 + 1); s.tidx = t; s.qidx = q + (sr ? a.nfwd : 0); s.anchor = apos;
+					const int64_t i = c0 + hg0 + nh + r;      /* the slot's position in the augmented list */
+					a.side_tbeg[i] = w0; a.side_tidx[i] = t; a.side_ls[i] = (u32)L | (sr << 31);
+					if (a.win) { ssw_win w; w.start = a.toff[t] + w0; w.len = s.tlen; w.pad = 0; a.win[i] = w; }
+				}
+			}
+			a.slots[(2 * f + h) * A + r] = s;
+		}
+	}
+}
+
+/* k_copy16 (ssw_copy16_args): a plain copy, 16 bytes per thread */
+__global__ void __launch_bounds__(256) k_copy16(ssw_copy16_args a)
+{
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < a.n16) ((u32x4*)a.dst)[i] = ((const u32x4*)a.src)[i];
+}
+
+/* ------------------------------------------------------------------------------------------------
  * k_selftest: (a) the cross-lane primitives applied to the lane id, so that tests can pin the DPP semantics the
  * chains rely on (and that the CPU emulator assumes) on real hardware; (b) a packed-int16 VALU issue-rate probe
  * (8 independent v_pk_add_i16/v_pk_max_i16/v_pk_sub_u16 chains) whose measured rate is the roofline's "peak".
@@ -4730,6 +4835,23 @@ extern "C" int ssw_shim_launch_matebest(const ssw_matebest_args* a, void* stream
 	ssw_matebest_args args = *a;
 	if (args.nfrag <= 0) return 0;
 	SSW_LAUNCH(k_matebest, ssw_matebest_args, args, (args.nfrag + 15) / 16, 256, MB_LDS_BYTES, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_materescue(const ssw_materescue_args* a, void* stream)
+{
+	ssw_materescue_args args = *a;
+	if (args.m.nfrag <= 0) return 0;
+	if (args.max_anchors < 1 || args.max_anchors > SSW_RESCUE_ANCHORS_MAX) return -2;
+	SSW_LAUNCH(k_materescue, ssw_materescue_args, args, (args.m.nfrag + 15) / 16, 256, MB_LDS_BYTES, stream);
+	return SSW_LAUNCH_OK();
+}
+
+extern "C" int ssw_shim_launch_copy16(const ssw_copy16_args* a, void* stream)
+{
+	ssw_copy16_args args = *a;
+	if (args.n16 <= 0) return 0;
+	SSW_LAUNCH(k_copy16, ssw_copy16_args, args, (args.n16 + 255) / 256, 256, 0, stream);
 	return SSW_LAUNCH_OK();
 }
 

@@ -51,7 +51,7 @@ class Timing(C.Structure):
                 ("trace_ms", C.c_double), ("n_word", C.c_int64), ("n_byte", C.c_int64), ("fill_kernel", C.c_char * 48),
                 ("fill_ops_per_row", C.c_double), ("fill_rows_per_lane", C.c_int32), ("fill_strips", C.c_int32),
                 ("db_repeats", C.c_int64), ("fill_pipelined", C.c_int64), ("win_copied", C.c_int64), ("best_flagged", C.c_int64),
-                ("db_long_pairs", C.c_int64)]
+                ("db_long_pairs", C.c_int64), ("rescue_windows", C.c_int64)]
 
 
 HIT_DTYPE = np.dtype([("score1", "<u2"), ("score2", "<u2"), ("ref_end1", "<i4"), ("read_end1", "<i4"), ("ref_end2", "<i4")], align=True)
@@ -74,6 +74,9 @@ assert BEST_DTYPE.itemsize == 16
 MATES_DTYPE = np.dtype([("pos1", "<i4"), ("pos2", "<i4"), ("n_eligible1", "<i4"), ("n_eligible2", "<i4"), ("score", "<i4"),
                         ("second_score", "<i4"), ("n_proper", "<i4"), ("proper", "<u2"), ("pad", "<u2")], align=True)
 assert MATES_DTYPE.itemsize == 32
+# ssw_gpu_rescued (include/ssw_gpu.h): where the chosen candidate of a mate came from (ssw_gpu_align_windows_mates_rescue)
+RESCUED_DTYPE = np.dtype([("tbeg", "<i8"), ("tlen", "<i4"), ("tidx", "<i4"), ("qidx", "<i4"), ("anchor", "<i4")], align=True)
+assert RESCUED_DTYPE.itemsize == 24
 # SSW_GPU_MATES_FR / _RF / _FF (include/ssw_gpu.h): the library orientation of the proper-pair rule
 MATES_ORIENTATION = {"fr": 0, "rf": 1, "ff": 2}
 
@@ -165,6 +168,12 @@ def load(path=None):
                                                       C.c_void_p, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                       C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_align_windows_mates_lib.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows_mates_rescue"):
+        L.ssw_gpu_align_windows_mates_rescue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_mates_rescue.restype = C.c_int
     if hasattr(L, "ssw_gpu_pool_align_windows_mates"):
         L.ssw_gpu_pool_align_windows_mates.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
@@ -582,6 +591,53 @@ class Context(object):
         if rebase and nf > 0:
             _mates_rebase(sel, res, co, tb)
         return sel, res, cig
+
+    def align_windows_mates_rescue(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mate_q, mat, n, min_insert, max_insert,
+                                   unpaired_penalty, max_anchors=2, anchor_min_score=0, rescue_pad=16, min_score=0, rebase=False, gapO=3, gapE=1,
+                                   flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, orientation="fr"):
+        """align_windows_mates with mate rescue on the device (ssw_gpu_align_windows_mates_rescue): every group is followed by max_anchors
+        rescue slots, windows in which a proper partner of the OTHER mate's best candidates would lie; mate_q[2 f + h] is the forward read
+        of mate h of fragment f, `queries` holds the reads and their reverse complements (with_revcomp: count == 2 nfwd)
+        -> (sel [nfrag] of MATES_DTYPE with pos1 / pos2 in the AUGMENTED groups, records [nfrag, 2] of RESULT_DTYPE, origin [nfrag, 2] of
+        RESCUED_DTYPE -- window, query and anchor of every chosen candidate --, uint32 CIGAR pool in (fragment, mate) order).  rebase=True
+        adds origin["tbeg"] to ref_begin1, ref_end1 and ref_end2 where they are >= 0 (the winner's window may not be the caller's)."""
+        orient = _orientation(orientation)
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        mq = np.ascontiguousarray(mate_q, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1 or co.shape[0] % 2 != 1:
+            raise ValueError("cand_off must be a 1-D array of 2 nfrag + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        nf = (int(co.shape[0]) - 1) // 2
+        if mq.shape != (2 * nf,):
+            raise ValueError("mate_q must be a 1-D array of 2 nfrag read indices")
+        if nf > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[2 nfrag] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        sel = np.zeros(nf, dtype=MATES_DTYPE)
+        res = np.zeros((nf, 2), dtype=RESULT_DTYPE)
+        org = np.zeros((nf, 2), dtype=RESCUED_DTYPE)
+        pool = _u32p()
+        words = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self.lib.ssw_gpu_align_windows_mates_rescue(self.h, queries.h, targets.h, vp(co), nf, vp(qi), vp(ti), vp(tb), vp(tl), int(nfwd), vp(mq),
+                                                         C.byref(p), int(min_score), int(min_insert), int(max_insert), int(unpaired_penalty), orient,
+                                                         int(max_anchors), int(anchor_min_score), int(rescue_pad), vp(sel), vp(res), vp(org),
+                                                         C.byref(pool) if want_cigar else None, C.byref(words))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_align_windows_mates_rescue: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
+        if want_cigar and pool:
+            C.CDLL(None).free(pool)
+        if rebase and nf > 0:
+            for f in ("ref_begin1", "ref_end1", "ref_end2"):
+                res[f] = np.where(res[f] >= 0, res[f] + org["tbeg"], res[f]).astype(res[f].dtype)
+        return sel, res, org, cig
 
     def search_db(self, queries, targets, mat, n, gapO=3, gapE=1, maskLen=-1, score_size=2, chunk=0, on_chunk=None):
         """streamed database search (ssw_gpu_search_db): on_chunk(target_first, hits[nq, target_count] of HIT_DTYPE) is called for

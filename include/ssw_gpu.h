@@ -93,6 +93,7 @@ typedef struct {
 	int64_t db_long_pairs; /* database search (ssw_gpu_align_batch against four or more targets, ssw_gpu_search_db, ssw_gpu_search_topk): the (query, target)
 	                          pairs answered by the long class of the database path -- queries above k_filldb's 640 residues on the strip kernel's pair
 	                          mode, two targets per job; 0 when there are none and for the other entry points */
+	int64_t rescue_windows; /* ssw_gpu_align_windows_mates_rescue: the non-empty rescue slots the call filled; 0 for the other entry points */
 	/* new fields are only ever appended here; ssw_gpu_last_timing_sized lets a caller built against an older header keep its layout */
 } ssw_gpu_timing;
 
@@ -335,7 +336,9 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * Nothing else depends on it: S, the ranking, n_proper's meaning, the one-mate case, the records and the CIGAR order.  In k_matebest it
  * is one wave-uniform argument.  An orientation outside 0 .. 2 returns -1 with a message before anything is launched or written.
  * Over several contexts or devices: ssw_gpu_pool_align_windows_mates below.  C++: BatchAligner::AlignWindowsMates (ssw_gpu_cpp.h).
- * Not provided: more than the best two combinations; an insert-size likelihood; mate rescue; a CLI option.
+ * Mate rescue -- aligning a mate without a usable candidate where the other mate's anchors and the insert range put it:
+ * ssw_gpu_align_windows_mates_rescue below.
+ * Not provided: more than the best two combinations; an insert-size likelihood; a CLI option.
  */
 #define SSW_GPU_MATES_GROUP_MAX 4096
 #define SSW_GPU_MATES_FR 0
@@ -366,6 +369,71 @@ int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* querie
                                     int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
                                     ssw_gpu_mates* sel, ssw_gpu_result* results,
                                     uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Mate rescue on the device: ssw_gpu_align_windows_mates_lib with the missing mate looked for where its partner says it must be.  Seeding
+ * misses a diverged, repetitive or short mate; its fragment then has no proper combination although the other mate is well anchored.
+ * Here every group gets max_anchors RESCUE SLOTS behind the caller's candidates, filled on the device between the forward fill of the
+ * caller's candidates and the selection; only non-empty slots cost any fill.  All arguments before mate_q, and params .. orientation,
+ * mean what they mean for ssw_gpu_align_windows_mates_lib; E, B, eligibility and the proper test are the ones defined there.
+ * With A = max_anchors, P = rescue_pad, L = the length of read mate_q[2 f + h], mn / mx = min_insert / max_insert:
+ *   Anchors of mate h of fragment f: the caller's candidates of the OTHER mate that are eligible (status 0, score1 > 0, score1 >=
+ *     min_score) and have score1 >= anchor_min_score, ranked by score1 descending, then position ascending; anchor r = 0 .. A - 1 is the
+ *     r-th of that order.
+ *   Rescue slot r of mate h is EMPTY (tbeg 0, tlen 0) when there is no r-th anchor, or when the anchor already has a proper partner
+ *     among the caller's eligible candidates of mate h.  Otherwise it lies on the anchor's target, on the strand a proper partner needs
+ *     (FR, RF: the opposite of the anchor's; FF: the same), with query mate_q[2 f + h] on the plus and nfwd + mate_q[2 f + h] on the minus
+ *     strand, and its window is the set of columns a proper partner can occupy (the orientation table above says which of the two lies
+ *     downstream), both ends inclusive:
+ *       rescued mate downstream:  [B(anchor) + mn - L - P,  B(anchor) + mx - 1 + P]
+ *       rescued mate upstream:    [E(anchor) + 1 - mx - P,  E(anchor) - mn + L + P]
+ *     clipped to [0, len(target) - 1]; fewer than one column left: the slot is empty.  (A window is cut at 2^31 - 1 columns.)
+ *     Rescue windows are never generated from rescue candidates.
+ *   The AUGMENTED list: group 2 f + h = the caller's candidates in their order, then the A slots.  sel, results, *cigar_pool and
+ *     *cigar_words equal, bit for bit, what ssw_gpu_align_windows_mates_lib returns for that list with the same remaining arguments:
+ *     pos1 / pos2 are positions in the augmented group (a value >= the caller's group size names slot pos - size), n_eligible* and
+ *     n_proper count the augmented list; an empty slot is the record of an empty target -- score 0, never eligible.
+ *   origin[2 f + h]: window and query of the chosen candidate of mate h + 1, anchor as in the struct; where pos is -1: tbeg 0, tlen 0,
+ *     tidx -1, qidx -1, anchor -1.  Positions of results are window-relative: add origin.tbeg (the winner's window may not be the caller's).
+ * On the device: k_materescue (k_matebest's geometry and digests: one 16-lane row per fragment) reads the anchors' records where the fill
+ * left them and writes 24 bytes per slot; the slot table comes to the host; the non-empty slots are planned and filled like any other
+ * candidates (k_fillpairs / the strip kernel's pair mode; outside the envelopes the fallback at flag 0 first, and once more with the
+ * caller's flag where they win), their records appended to the same device array; k_matebest runs over the augmented list; the
+ * winners-only reverse pass and traceback are unchanged.
+ * Memory beyond ssw_gpu_align_windows_mates_lib's (inputs / outputs of the call, not scratch under ssw_gpu_get_budget): 24 bytes per slot
+ * (2 * nfrag * A slots), the record (48), slot map (4), side table (16) and window table (32) entries of the slots, and 8 bytes of mate_q
+ * per fragment; on the host the augmented copy of the four candidate arrays (20 bytes per candidate and slot).
+ * Errors (-1 with a message that names the fragment, mate or pair, before anything is launched or written): every check of
+ * ssw_gpu_align_windows_mates_lib; queries->count != 2 * nfwd (the reverse complements must be resident: ssw_gpu_seqs_with_revcomp);
+ * mate_q or origin NULL; a mate_q outside [0, nfwd); a caller's candidate of group g whose qidx is neither mate_q[g] nor nfwd + mate_q[g];
+ * max_anchors outside 1 .. SSW_GPU_RESCUE_ANCHORS_MAX; rescue_pad outside 0 .. 65535; anchor_min_score < 0; a group whose size plus
+ * max_anchors exceeds SSW_GPU_MATES_GROUP_MAX.  nfrag == 0 returns 0 with *cigar_words = 0.  SSW_GPU_BUSY and the context lock as for
+ * ssw_gpu_align_windows.
+ * ssw_gpu_last_timing: rescue_windows is the number of non-empty slots; reduce_ms the device time of k_materescue plus k_matebest;
+ * fill_ms, fill_launches and fill_cells cover both fills.  The augmented copy and the slot table are host work per candidate and slot
+ * whether or not a window is filled (measured: DESIGN 6.18): a list with nothing to rescue is cheaper through
+ * ssw_gpu_align_windows_mates_lib.
+ * Not provided: a pool variant and a BatchAligner method; a CLI option; an insert-size likelihood; rescue from rescue candidates.
+ */
+#define SSW_GPU_RESCUE_ANCHORS_MAX 8
+typedef struct {            /* where the chosen candidate of a mate came from: 24 bytes */
+	int64_t tbeg;           /* its window, target coordinates */
+	int32_t tlen;
+	int32_t tidx;
+	int32_t qidx;           /* the query it was aligned with (strand included) */
+	int32_t anchor;         /* -1: one of the caller's candidates; >= 0: a rescue window, generated from the candidate at this position of the
+	                           OTHER mate's group */
+} ssw_gpu_rescued;
+int ssw_gpu_align_windows_mates_rescue(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                                       const int64_t* cand_off, int64_t nfrag,
+                                       const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                       int32_t nfwd,
+                                       const int32_t* mate_q,      /* [2 nfrag]: forward read index, in [0, nfwd), of mate h of fragment f at 2 f + h */
+                                       const ssw_gpu_params* params, int32_t min_score,
+                                       int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+                                       int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
+                                       ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin,
+                                       uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
