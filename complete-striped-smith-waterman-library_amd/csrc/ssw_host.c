@@ -507,7 +507,7 @@ int ssw_gpu_last_timing(const ssw_gpu_ctx* c, ssw_gpu_timing* out) { return ssw_
 /* Column-frame form (lanes.h): stored values are true value + phi(column).  For gap penalties gapO > gapE and a bucket
    whose true scores stay <= top, picks the renormalisation period K (a power of two >= 64, K * gapE <= ~4096) and the base offset
    so that every live operand is a non-negative number below 0x7C00; returns 0 when the bucket does not fit (plain int16 form then).
-   lanes = lanes per chain (16 or 64). */
+   lanes = lanes per chain (16 or 64; 8: the half-row chains, whose blocked row frame holds the rows of class 3 a further 3 x gapE up). */
 static int ssw_frame_params(const ssw_knobs* kn, int64_t top, int gapO, int gapE, int minmat, int lanes, int32_t* base, int32_t* kmask)
 {
 	if (gapO <= gapE || gapE < 1) return 0;
@@ -515,10 +515,11 @@ static int ssw_frame_params(const ssw_knobs* kn, int64_t top, int gapO, int gapE
 	if (kn->frame_k) { K = 16; while (K * 2 <= kn->frame_k && K < 1024) K <<= 1; }   /* tests: renormalise often */
 	while (K > 64 && (int64_t)K * gapE > 4096) K >>= 1;
 	const int b = (minmat < 0 ? -minmat : 0) + gapO + 2 * gapE + 8;     /* diag + score' >= 0, F - gapE >= 0, t >= 0 */
+	const int up = lanes + 2 + (lanes == 8 ? 3 : 0);
 	/* a bucket near the top of the range still fits with a shorter period (15-kb reads at match 2, proteins with a large max(mat)): halve
 	   K down to 64 before giving the bucket to the 9-instruction plain form */
-	while (K > 64 && top + b + (int64_t)(K + lanes + 2) * gapE >= 31744) K >>= 1;
-	if (top + b + (int64_t)(K + lanes + 2) * gapE >= 31744) return 0;
+	while (K > 64 && top + b + (int64_t)(K + up) * gapE >= 31744) K >>= 1;
+	if (top + b + (int64_t)(K + up) * gapE >= 31744) return 0;
 	*base = b; *kmask = K - 1;
 	return 1;
 }
@@ -761,6 +762,23 @@ static int keyed_cmp(const void* a, const void* b)
 	if (x->key != y->key) return x->key < y->key ? -1 : 1;
 	if (x->sub != y->sub) return x->sub < y->sub ? -1 : 1;
 	return x->q < y->q ? -1 : (x->q > y->q);
+}
+
+/* VALU instructions of k_fill8<R>'s recurrence per (row, column) of a query pair, counted as chain_row8 / cm_finish8 (ssw_kernels.hip) emit
+   them: five per row, F's 4 x gapE after every class-3 row but the last, and the column maximum per class -- a maximum of three per two
+   values, a single one for an odd value of classes 1 to 3, the three class offsets and the last fold.  R = 19: 112 / 19 = 5.89.  R = 9 is
+   the one instance without the blocked row frame (RowFrame8<9>::P in ssw_kernels.hip): the column frame's 6.5 */
+static double fill8_ops_per_row(int R)
+{
+	if (R == 9) return 6.5;
+	int cm = 0, last = 1;      /* last: values of the closing fold, class 0 first */
+	for (int k = 0; k < 4 && k < R; ++k) {
+		const int n = (R - 1 - k) / 4 + 1 + (k == 0);
+		cm += (n - 1) / 2;
+		if (k == 0) last += (n & 1) == 0;
+		else { cm += 1 + ((n & 1) == 0); ++last; }
+	}
+	return (double)(5 * R + (R - 1) / 4 + cm + last / 2) / R;
 }
 
 /* remembers which fill kernel evaluated most cells of the call (ssw_gpu_timing.fill_kernel) */
@@ -2434,7 +2452,7 @@ static int fill_launch(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, in
 	else if (B->lanes == 64 && B->tailR) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR);
 	else if (B->lanes == 64) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
 	else snprintf(nm, sizeof nm, "k_chainx<%d,16 lanes> x %d strips", B->R, B->strips);
-	note_fill_kernel(c, lc, &bc->best_fill_cells, nm, !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
+	note_fill_kernel(c, lc, &bc->best_fill_cells, nm, use_half ? fill8_ops_per_row(B->half) : !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
 	return 0;
 }
 

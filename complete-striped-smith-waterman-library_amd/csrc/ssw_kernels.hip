@@ -389,32 +389,79 @@ template <int... I> struct RowSeqTo<0, I...> { typedef RowSeq<I...> type; };
 template <int R, int... I> SSW_DEV void rows_set(Rows8<R>& a, u32 v, RowSeq<I...>) { ((row_at<I>(a) = v), ...); }
 template <int R, int... I> SSW_DEV void rows_sub(Rows8<R>& a, u32 k, RowSeq<I...>) { ((row_at<I>(a) -= k), ...); }
 
-/* row r of chain_rows_fr<R, 0, R, true>; x: diag + score, formed by the row above -- before that row's H was replaced, so that the old H[r]
-   dies one instruction before the new one is born and both can live in one register */
+/* BLOCKED ROW FRAME: on top of the column frame, row r of a position -- its H, E, F, t -- is held a further (r mod 4) x gapE up.
+   F then passes from a row to the next one of the following class as it is, max(F, t), and pays 4 x gapE once after every class-3 row; the
+   class difference of the diagonal sits in the profile (build_profile8), E takes the floor of its class (four registers that rotate from
+   step to step), and the column maximum is kept per class and brought to class 0 once per step (cm_finish8).  KL: class of the last row,
+   in which H and the open F leave the position.
+   P: the period.  R8 = 9 keeps P = 1 -- one class, the column frame alone, instruction for instruction the recurrence it had: with four floors
+   and four accumulators the instance does not fit the 72 registers of its seven wavefronts per SIMD (36 bytes of scratch) */
+template <int R> struct RowFrame8 {
+	static constexpr int P = R == 9 ? 1 : 4;
+	static constexpr int cls(int r) { return r % P; }
+	static constexpr int KL = cls(R - 1);
+	/* values that class k folds in one step: its rows, and for class 0 the maximum that comes in from the position above */
+	static constexpr int count(int k) { return k < R && k < P ? (R - 1 - k) / P + 1 + (k == 0) : 0; }
+	static constexpr bool LEFT0 = (count(0) & 1) == 0;      /* class 0 ends on a single value: it goes into the last fold as it is */
+	static constexpr int ROW0 = (R - 1) / P * P;            /* ... and this is its row */
+};
+template <int R, int... I> SSW_DEV void rows_set_cls(Rows8<R>& a, u32 v, u32 g, RowSeq<I...>) { ((row_at<I>(a) = v + (u32)RowFrame8<R>::cls(I) * g), ...); }
+SSW_DEV u32 pk_max_all(u32 a) { return a; }
+SSW_DEV u32 pk_max_all(u32 a, u32 b) { return pk_max(a, b); }
+template <typename... T> SSW_DEV u32 pk_max_all(u32 a, u32 b, u32 c, T... rest) { return pk_max_all(pk_max3_fr(a, b, c), rest...); }
+
+/* row r of a step; x: diag + score, formed by the row above -- before that row's H was replaced, so that the old H[r] dies one instruction
+   before the new one is born and both can live in one register.  a0 .. a3: the column maximum per class, the rows r - P and r in one
+   maximum of three (H of row r - P is this step's, just written); fl0 .. fl3: phi(column + 1) in the four classes */
 template <int R, int r>
-SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& f, u32& cm, u32 c1, u32 gapE2, u32 fl)
+SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
+                        u32 c1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3)
 {
+	typedef RowFrame8<R> F;
+	constexpr int P = F::P, k = F::cls(r), j = r / P + (k == 0), n = F::count(k);
 	u32& Hr = row_at<r>(H); u32& Er = row_at<r>(E);
+	u32& a = k == 0 ? a0 : k == 1 ? a1 : k == 2 ? a2 : a3;
 	const u32 xn = r + 1 < R ? Hr + sc[(r + 1) >> 2][(r + 1) & 3] : 0u;
 	const u32 h = pk_max3_fr(x, Er, f);
 	const u32 t = h - c1;
-	Er = pk_max3_fr(Er, t, fl);
+	Er = pk_max3_fr(Er, t, k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3);
 	f = pk_max(f, t);
-	if (r != R - 1) f -= gapE2;      /* the last row leaves f OPEN */
-	if ((r & 1) == 1) cm = pk_max3_fr(cm, row_at<(r > 0 ? r - 1 : 0)>(H), h);
-	else if (r == R - 1) cm = pk_max(cm, h);
+	if (r != R - 1 && F::cls(r + 1) == 0) f -= (u32)(k + 1) * gapE2;      /* back to class 0; the last row leaves f OPEN, in its own class */
+	if (j == 0) a = h;
+	else if ((j & 1) == 0) a = pk_max3_fr(a, row_at<(r >= P ? r - P : 0)>(H), h);
+	else if (j == n - 1 && k != 0) a = pk_max(a, h);      /* (class 0's single value waits for cm_finish8) */
 	Hr = h;
 	x = xn;
 }
-template <int R, int... I>
-SSW_DEV void chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32& cm, u32 c1, u32 gapE2, u32 fl, RowSeq<I...>)
+/* the step's column maximum in class 0 from the four classes' */
+template <int R>
+SSW_DEV u32 cm_finish8(Rows8<R>& H, u32 a0, u32 a1, u32 a2, u32 a3, u32 gapE2)
 {
-	u32 x = d + sc[0][0];
-	(chain_row8<R, I>(sc, H, E, x, f, cm, c1, gapE2, fl), ...);
+	typedef RowFrame8<R> F;
+	if constexpr (F::P == 1) {
+		if constexpr (F::LEFT0) return pk_max_all(a0, row_at<F::ROW0>(H));
+		else return a0;
+	} else if constexpr (R >= 4) {
+		const u32 b1 = a1 - gapE2, b2 = a2 - 2u * gapE2, b3 = a3 - 3u * gapE2;
+		if constexpr (F::LEFT0) return pk_max_all(a0, row_at<F::ROW0>(H), b1, b2, b3);
+		else return pk_max_all(a0, b1, b2, b3);
+	} else if constexpr (R == 3) return pk_max_all(a0, row_at<0>(H), a1 - gapE2, a2 - 2u * gapE2);
+	else if constexpr (R == 2) return pk_max_all(a0, row_at<0>(H), a1 - gapE2);
+	else return pk_max_all(a0, row_at<0>(H));
+}
+template <int R, int... I>
+SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32 cm, u32 c1, u32 gapE2,
+                           u32 fl0, u32 fl1, u32 fl2, u32 fl3, RowSeq<I...>)
+{
+	u32 x = d + sc[0][0], a0 = cm, a1 = 0, a2 = 0, a3 = 0;
+	(chain_row8<R, I>(sc, H, E, x, f, a0, a1, a2, a3, c1, gapE2, fl0, fl1, fl2, fl3), ...);
+	return cm_finish8<R>(H, a0, a1, a2, a3, gapE2);
 }
 
 /* profile of two pairs: word ((b*C + c)*16 + chain*8 + p)*4 + k = scores of residue b against rows p*R + 4c + k of pair `chain`.  All 8R rows
-   are live (zero score below the read); a pair that does not exist gets dead rows: its chain stays at the floor */
+   are live (zero score below the read); a pair that does not exist gets dead rows: its chain stays at the floor.  A live entry carries the
+   column frame's + gapE and the difference between the row's class and the class of the row above it, whose H is the diagonal: + gapE into
+   classes 1 to 3, - 3 gapE into class 0, and for a position's first row minus the class of the last row of the position above */
 template <int R>
 SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const int8_t* mat, int n,
                             const int8_t* const (&q)[4], const int (&len)[4], bool live1, int gapE)
@@ -432,7 +479,8 @@ SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const i
 			int lo = 0, hi = 0;
 			if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
 			if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
-			v = fr_pack(lo + gapE, hi + gapE);
+			const int fr = (1 + RowFrame8<R>::cls(r) - (r == 0 ? RowFrame8<R>::KL : RowFrame8<R>::cls(r - 1))) * gapE;
+			v = fr_pack(lo + fr, hi + fr);
 		}
 		lds_st32(lds, (u32)w * 4u, v);
 	}
@@ -441,19 +489,20 @@ SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const i
 /* the 16 lanes of a row turn what position 7 of BOTH chains parked during the steps [s1, s1 + 16) into true values: the chain's maximum into
    its ring, v(c) = max3(F, Hlast + 2 gapE, phi + gapE) - (phi + gapE) into the v ring (and its mirror).  One phi serves both: lane l takes
    step s1 + l of either chain, and all 16 steps lie in one renormalisation period (Hlast was parked as the register stood, already
-   dropped with the rest).  Steps 0..6 are the null columns before the chain's first, where H sits at the floor and F below it: v = 0 */
-SSW_DEV void fill_stage8(unsigned char* lds, u32 rbl, int s1, bool low8, u32 lgd, int fr_base, int fr_kmask, int gapE, u32 gE2)
+   dropped with the rest).  Steps 0..6 are the null columns before the chain's first, where H sits at the floor and F below it: v = 0.
+   The maximum is parked in class 0 of the row frame, F and Hlast in the class of the chain's last row, klg = class x gapE (packed) higher */
+SSW_DEV void fill_stage8(unsigned char* lds, u32 rbl, int s1, bool low8, u32 lgd, int fr_base, int fr_kmask, int gapE, u32 gE2, u32 klg)
 {
 	/* phi(column + 1) of step s1 + l: the open F and Hlast + 2 gapE are one gapE above the column's frame.  s1 and the period are multiples
 	   of 16, so the lane's share l * gapE (lgd, packed) adds to a wavefront-uniform term */
-	const u32 ph = pk_dup(fr_base + ((s1 & fr_kmask) + 2) * gapE) + lgd;
+	const u32 ph = pk_dup(fr_base + ((s1 & fr_kmask) + 2) * gapE) + lgd, phl = ph + klg;
 	const u32 sc = rbl + 2 * PARK8_BYTES + 4u * ((u32)s1 & 16u), sv = rbl + 2 * PARK8_BYTES + 2 * CRING8_BYTES + 4u * ((u32)s1 & 48u);
 	const bool mir = ((u32)s1 & 48u) == 0 && low8;
 #pragma unroll
 	for (u32 ch = 0; ch < 2; ++ch) {
 		const u32 p = rbl + ch * PARK8_BYTES;
 		const u32 cm = lds_ld32(lds, p), f = lds_ld32(lds, p + 64u), h = lds_ld32(lds, p + 128u);
-		const u32 vv = pk_max3_fr(f, h + 2u * gE2, ph) - ph;
+		const u32 vv = pk_max3_fr(f, h + 2u * gE2, phl) - phl;
 		lds_st32(lds, sc + ch * CRING8_BYTES, cm - (ph - gE2));
 		lds_st32(lds, sv + ch * VRING8_BYTES, vv);
 		if (mir) lds_st32(lds, sv + ch * VRING8_BYTES + 256u, vv);      /* slots 0..7 once more behind the ring */
@@ -585,14 +634,18 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	__syncthreads();
 
 	const u32 zero0 = pk_dup(fr_phi(0, pos, 8, a.fr_base, a.fr_kmask, gapEi) - gapEi);
-	u32 fl = zero0 + a.gapE2;
+	/* row frame: the floors of the four classes, phi(column + 1) + class x gapE, are one quantity at four consecutive steps -- per step
+	   the names rotate and one is computed; 16 steps per trip bring every name back to its register */
+	constexpr int KL = RowFrame8<R>::KL;
+	const u32 klg = (u32)KL * a.gapE2;
+	u32 fl0 = zero0 + a.gapE2, fl1 = fl0 + a.gapE2, fl2 = fl1 + a.gapE2, fl3 = fl2 + a.gapE2;
 	typedef typename RowSeqTo<R>::type Rows;
 	Rows8<R> H, E;
-	rows_set(H, zero0, Rows()); rows_set(E, fl, Rows());
-	u32 Hlast = zero0, Fout = zero0 + a.gapE2, cmout = zero0, hsave = zero0;
+	rows_set_cls(H, zero0, a.gapE2, Rows()); rows_set_cls(E, fl0, a.gapE2, Rows());
+	u32 Hlast = zero0 + klg, Fout = zero0 + klg + a.gapE2, cmout = zero0, hsave = zero0 + klg;      /* (H and the open F leave a position in class KL) */
 	const u32 lane_prof = (u32)(ch * 8 + pos) * 16u;
 	const u32 gO = a.gapO2 - a.gapE2, gE = a.gapE2;
-	const u32 gEv = opaque(gE);
+	const u32 gEv = opaque(klg + gE);                      /* F comes down to class 0 while the next position takes it over */
 	u32 fin = 0;
 	const u32 park = rb + (u32)ch * PARK8_BYTES, rbl = opaque(rb + 4u * (u32)l16);      /* position 7 of each chain parks, every lane of the row reads one step back */
 	const u32 lgd = pk_dup(l16 * gapEi);
@@ -602,7 +655,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 		if (s0 > 0 && (s0 & a.fr_kmask) == 0) {
 			const u32 k = (u32)(a.fr_kmask + 1) * a.gapE2;
 			rows_sub(H, k, Rows()); rows_sub(E, k, Rows());
-			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl -= k;
+			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl0 -= k; fl1 -= k; fl2 -= k; fl3 -= k;
 		}
 		{   /* stage target columns [s0+16, s0+32), prefetch [s0+32, s0+48) */
 			const int p = (s0 + 16 + l16) & 63;
@@ -614,7 +667,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 			nxt = (u32)code * G::PSTRIDE;
 		}
 		wave_lds_fence();      /* what position 7 parked in the last 16 steps is visible to the row */
-		if (s0 >= 16) fill_stage8(lds, rbl, s0 - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE);
+		if (s0 >= 16) fill_stage8(lds, rbl, s0 - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE, klg);
 		wave_lds_fence();      /* one fence for both chains: the rings are complete up to step s0 - 1 */
 		if (s0 >= 32)          /* columns [s0-32, s0-16) are complete in the rings, and so are the eight before them */
 			fill_flush8(lds, rb, s0 - 32, l16, store_from, ncols, live1, o16, o8, a.cm_stride, gq, gapEi, gapOi);
@@ -626,11 +679,13 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 #pragma unroll
 			for (int c = 0; c < C; ++c) sc[c] = lds_ld128(lds, paddr + 256u * c);
 			const u32 hprev = Hlast;                              /* H of the chain's last row one column back */
-			const u32 hin = xl_row_shr2_umax(Hlast, fl); fl += gE;
+			/* head of the chain: the zero that row_shr fills in becomes phi(column) in class KL, which is that class's floor of the step before */
+			const u32 hin = xl_row_shr2_umax(Hlast, KL == 0 ? fl0 : KL == 1 ? fl1 : KL == 2 ? fl2 : fl3);
+			if constexpr (RowFrame8<R>::P == 1) fl0 += gE;
+			else { const u32 up = fl3 + gE; fl0 = fl1; fl1 = fl2; fl2 = fl3; fl3 = up; }
 			xl_row_shr2_sub_keep(fin, Fout, gEv);
 			u32 f = fin, d = hsave;
-			u32 cm = xl_row_shr2_zero(cmout);
-			chain_rows_fr8(sc, H, E, d, f, cm, gO, gE, fl, Rows());
+			const u32 cm = chain_rows_fr8(sc, H, E, d, f, xl_row_shr2_zero(cmout), gO, gE, fl0, fl1, fl2, fl3, Rows());
 			hsave = hin; Hlast = row_at<R - 1>(H); Fout = f; cmout = cm;
 			if (pos == 7) {      /* raw: the frame of this step (hprev: one gapE below it) */
 				lds_st32(lds, park + 4u * j, cm); lds_st32(lds, park + 64u + 4u * j, f); lds_st32(lds, park + 128u + 4u * j, hprev);
@@ -638,7 +693,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 		}
 	}
 	wave_lds_fence();
-	fill_stage8(lds, rbl, nsteps - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE);
+	fill_stage8(lds, rbl, nsteps - 16, low8, lgd, a.fr_base, a.fr_kmask, gapEi, gE, klg);
 	wave_lds_fence();
 	for (int base = nsteps - 32; base < nsteps; base += 16)
 		if (base >= 0) fill_flush8(lds, rb, base, l16, store_from, ncols, live1, o16, o8, a.cm_stride, gq, gapEi, gapOi);
