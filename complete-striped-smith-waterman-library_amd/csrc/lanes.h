@@ -219,6 +219,27 @@ SSW_DEV u32 pk_max3_fr(u32 a, u32 b, u32 c) { return pk_max3_nonneg(a, b, c); }
    at run time (diag + score >= 0 for every live row), so the packed sum is exact in both halves. */
 #define FR_DEAD 32768
 SSW_DEV u32 fr_pack(int lo, int hi) { return (u32)lo + ((u32)hi << 16); }
+/* the frame adds of TWO rows in one 64-bit add (v_lshl_add_u64 on a register pair): x0 = h0 + s0, x1 = h1 + s1, with s0 | s1 two neighbouring
+   words of the profile.  The packed-sum trick one level up: a live s0 whose signed sum lo + hi x 65536 is negative has borrowed 1 from s1
+   when the profile was built (fr_borrows), and gives it back as the carry out of bit 31 -- for a live row h + s >= 0 holds in BOTH halves.
+   A dead word (FR_DEAD twice: h + 0x80008000 stays below 2^32) and a zero word neither borrow nor carry.  The emulation checks exactly that:
+   the low add carries if and only if its word borrowed, so that the pair add equals the two 32-bit adds of the words before the borrow */
+SSW_DEV bool fr_borrows(u32 s0) { return (int32_t)s0 < 0 && s0 != fr_pack(FR_DEAD, FR_DEAD); }
+template <bool HPAIR> SSW_DEV void fr_add_pair(u32 h0, u32 h1, u32 s0, u32 s1, u32& x0, u32& x1)
+{
+	unsigned long long h = (unsigned long long)h1 << 32 | h0, s = (unsigned long long)s1 << 32 | s0;
+#ifdef SSW_SIMT_EMU
+	if ((((unsigned long long)h0 + s0) >> 32 != 0) != fr_borrows(s0)) emu::fail("fr_add_pair: the low word's carry does not match its borrow");
+#else
+	/* the profile words as one opaque register pair (no instruction): the compiler otherwise adds the upper words on their own, in 32 bits,
+	   beside a 64-bit add of the lower ones.  HPAIR: the same for H -- the small instances still do it to rows 0 and 1 without, the large
+	   ones lose registers with it (k_fill8<15>: 12 bytes of scratch) */
+	asm("" : "+v"(s));
+	if constexpr (HPAIR) asm("" : "+v"(h));
+#endif
+	const unsigned long long x = h + s;
+	x0 = (u32)x; x1 = (u32)(x >> 32);
+}
 SSW_DEV u32 umax32(u32 a, u32 b) { return a > b ? a : b; }
 /* 0xffff in every half where a > b (unsigned), else 0: saturating difference, min(., 1), x 0xffff -- three packed instructions.  One asm
    block on the device: written with the builtins, LLVM recognises the idiom at every step (umin(x, 1) -> x != 0, ...) and emits two 16-bit

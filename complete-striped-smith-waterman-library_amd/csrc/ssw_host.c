@@ -765,8 +765,9 @@ static int keyed_cmp(const void* a, const void* b)
 }
 
 /* VALU instructions of k_fill8<R>'s recurrence per (row, column) of a query pair, counted as chain_row8 / cm_finish8 (ssw_kernels.hip) emit
-   them: five per row, F's 4 x gapE after every class-3 row but the last, and the column maximum per class -- a maximum of three per two
-   values, a single one for an odd value of classes 1 to 3, the three class offsets and the last fold.  R = 19: 112 / 19 = 5.89.  R = 9 is
+   them: four per row and one diagonal add per two rows (a 64-bit add on a register pair; the last row of an odd R has its own), F's 4 x gapE
+   after every class-3 row but the last, and the column maximum per class -- a maximum of three per two values, a single one for an odd
+   value of classes 1 to 3, the three class offsets and the last fold.  R = 19: 103 / 19 = 5.42.  R = 9 is
    the one instance without the blocked row frame (RowFrame8<9>::P in ssw_kernels.hip): the column frame's 6.5 */
 static double fill8_ops_per_row(int R)
 {
@@ -778,7 +779,7 @@ static double fill8_ops_per_row(int R)
 		if (k == 0) last += (n & 1) == 0;
 		else { cm += 1 + ((n & 1) == 0); ++last; }
 	}
-	return (double)(5 * R + (R - 1) / 4 + cm + last / 2) / R;
+	return (double)(4 * R + (R + 1) / 2 + (R - 1) / 4 + cm + last / 2) / R;
 }
 
 /* remembers which fill kernel evaluated most cells of the call (ssw_gpu_timing.fill_kernel) */

@@ -404,6 +404,10 @@ template <int R> struct RowFrame8 {
 	static constexpr int count(int k) { return k < R && k < P ? (R - 1 - k) / P + 1 + (k == 0) : 0; }
 	static constexpr bool LEFT0 = (count(0) & 1) == 0;      /* class 0 ends on a single value: it goes into the last fold as it is */
 	static constexpr int ROW0 = (R - 1) / P * P;            /* ... and this is its row */
+	/* diag + score of rows 2j and 2j + 1 in ONE 64-bit add (fr_add_pair: lanes.h): their profile words are an aligned pair of the quad a
+	   ds_read_b128 delivers, and the H of rows 2j - 1 and 2j neighbours.  R8 = 9 keeps its rows as they were */
+	static constexpr bool PAIR = P != 1;
+	static constexpr bool HPAIR = R <= 7;      /* fr_add_pair: H as an opaque register pair too */
 };
 template <int R, int... I> SSW_DEV void rows_set_cls(Rows8<R>& a, u32 v, u32 g, RowSeq<I...>) { ((row_at<I>(a) = v + (u32)RowFrame8<R>::cls(I) * g), ...); }
 SSW_DEV u32 pk_max_all(u32 a) { return a; }
@@ -411,17 +415,22 @@ SSW_DEV u32 pk_max_all(u32 a, u32 b) { return pk_max(a, b); }
 template <typename... T> SSW_DEV u32 pk_max_all(u32 a, u32 b, u32 c, T... rest) { return pk_max_all(pk_max3_fr(a, b, c), rest...); }
 
 /* row r of a step; x: diag + score, formed by the row above -- before that row's H was replaced, so that the old H[r] dies one instruction
-   before the new one is born and both can live in one register.  a0 .. a3: the column maximum per class, the rows r - P and r in one
-   maximum of three (H of row r - P is this step's, just written); fl0 .. fl3: phi(column + 1) in the four classes */
+   before the new one is born and both can live in one register.  With PAIR an odd row forms it for the two rows below it at once, from its
+   own old H and the old H of the row below (x2: the second sum, which the even row hands on), and the last row of an odd R has its own add.
+   a0 .. a3: the column maximum per class, the rows r - P and r in one maximum of three (H of row r - P is this step's, just written);
+   fl0 .. fl3: phi(column + 1) in the four classes */
 template <int R, int r>
-SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
+SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& x2, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
                         u32 c1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3)
 {
 	typedef RowFrame8<R> F;
 	constexpr int P = F::P, k = F::cls(r), j = r / P + (k == 0), n = F::count(k);
 	u32& Hr = row_at<r>(H); u32& Er = row_at<r>(E);
 	u32& a = k == 0 ? a0 : k == 1 ? a1 : k == 2 ? a2 : a3;
-	const u32 xn = r + 1 < R ? Hr + sc[(r + 1) >> 2][(r + 1) & 3] : 0u;
+	u32 xn = 0u;
+	if constexpr (F::PAIR && (r & 1) == 0) xn = x2;
+	else if constexpr (F::PAIR && r + 2 < R) fr_add_pair<F::HPAIR>(Hr, row_at<(r + 2 < R ? r + 1 : 0)>(H), sc[(r + 1) >> 2][(r + 1) & 3], sc[(r + 1) >> 2][(r + 2) & 3], xn, x2);
+	else if constexpr (r + 1 < R) xn = Hr + sc[(r + 1) >> 2][(r + 1) & 3];
 	const u32 h = pk_max3_fr(x, Er, f);
 	const u32 t = h - c1;
 	Er = pk_max3_fr(Er, t, k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3);
@@ -453,15 +462,18 @@ template <int R, int... I>
 SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32 cm, u32 c1, u32 gapE2,
                            u32 fl0, u32 fl1, u32 fl2, u32 fl3, RowSeq<I...>)
 {
-	u32 x = d + sc[0][0], a0 = cm, a1 = 0, a2 = 0, a3 = 0;
-	(chain_row8<R, I>(sc, H, E, x, f, a0, a1, a2, a3, c1, gapE2, fl0, fl1, fl2, fl3), ...);
+	u32 x, x2 = 0, a0 = cm, a1 = 0, a2 = 0, a3 = 0;
+	if constexpr (RowFrame8<R>::PAIR && R >= 2) fr_add_pair<RowFrame8<R>::HPAIR>(d, row_at<0>(H), sc[0][0], sc[0][1], x, x2);      /* rows 0 and 1: the incoming diagonal and the old H[0] */
+	else x = d + sc[0][0];
+	(chain_row8<R, I>(sc, H, E, x, x2, f, a0, a1, a2, a3, c1, gapE2, fl0, fl1, fl2, fl3), ...);
 	return cm_finish8<R>(H, a0, a1, a2, a3, gapE2);
 }
 
 /* profile of two pairs: word ((b*C + c)*16 + chain*8 + p)*4 + k = scores of residue b against rows p*R + 4c + k of pair `chain`.  All 8R rows
    are live (zero score below the read); a pair that does not exist gets dead rows: its chain stays at the floor.  A live entry carries the
    column frame's + gapE and the difference between the row's class and the class of the row above it, whose H is the diagonal: + gapE into
-   classes 1 to 3, - 3 gapE into class 0, and for a position's first row minus the class of the last row of the position above */
+   classes 1 to 3, - 3 gapE into class 0, and for a position's first row minus the class of the last row of the position above.  Rows 2j and
+   2j + 1 are one 64-bit addend (RowFrame8::PAIR): the word of row 2j + 1 is 1 lower where the live word of row 2j is negative as a whole */
 template <int R>
 SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const int8_t* mat, int n,
                             const int8_t* const (&q)[4], const int (&len)[4], bool live1, int gapE)
@@ -476,11 +488,16 @@ SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const i
 		if (b == n || (ch && !live1)) v = fr_pack(FR_DEAD, FR_DEAD);
 		else if (r >= R) v = 0;
 		else {
-			int lo = 0, hi = 0;
-			if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
-			if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
-			const int fr = (1 + RowFrame8<R>::cls(r) - (r == 0 ? RowFrame8<R>::KL : RowFrame8<R>::cls(r - 1))) * gapE;
-			v = fr_pack(lo + fr, hi + fr);
+			const auto entry = [&](int r, int row) {
+				int lo = 0, hi = 0;
+				if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
+				if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
+				const int fr = (1 + RowFrame8<R>::cls(r) - (r == 0 ? RowFrame8<R>::KL : RowFrame8<R>::cls(r - 1))) * gapE;
+				return fr_pack(lo + fr, hi + fr);
+			};
+			v = entry(r, row);
+			/* the upper word of a pair (fr_add_pair) lends 1 to a negative lower word; the last row of an odd R is added alone */
+			if (RowFrame8<R>::PAIR && (r & 1) && fr_borrows(entry(r - 1, row - 1))) v -= 1u;
 		}
 		lds_st32(lds, (u32)w * 4u, v);
 	}

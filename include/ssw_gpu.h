@@ -78,7 +78,7 @@ typedef struct {
 	/* the fill kernel that evaluated most cells in the call (for roofline accounting) */
 	char fill_kernel[48];  /* e.g. "k_fill<10,frame>", "k_chainq<12,frame> x 14 strips", "k_chainq<12,pairs,frame> x 13 strips + 1 of 1", "k_filldb<19,frame>" */
 	double fill_ops_per_row; /* VALU instructions of the recurrence per (row, column) of a query pair in that kernel: 6.5 (column frame) / 7.5 / 8.5 / 9;
-	                            k_fill8<R> (column frame + blocked row frame): its own count per instance, 5.89 at R = 19.
+	                            k_fill8<R> (column frame + blocked row frame, one diagonal add per two rows): its own count per instance, 5.42 at R = 19.
 	                            k_chainq<R,pairs,..> reports the batch fill's 6.5 / 9 although it merges the two halves' profile entries per row
 	                            (one more instruction): a roofline computed from it is understated for that kernel */
 	int32_t fill_rows_per_lane;
