@@ -463,6 +463,7 @@ typedef struct {
    A combination (a of mate 1, b of mate 2) is PROPER when both lie on one target, on the strands of the library `orientation` -- opposite
    for FR and RF, equal for FF -- and the upstream one's B and the downstream one's E span min_insert .. max_insert columns (upstream: the
    plus-strand one for FR, the minus-strand one for RF, mate 1 on the plus and mate 2 on the minus strand for FF); its score is score1(a) + score1(b), less unpaired_penalty unless proper.
+   Under a pair model (ins_pen != NULL) a proper combination of span D pays ins_pen[D - min_insert] in turn; nothing else changes.
    Order: that score descending, then position of a, then position of b ascending. */
 struct ssw_mate_rec {        /* byte-for-byte the layout of ssw_gpu_mates (include/ssw_gpu.h) */
 	int32_t pos1, pos2, n_eligible1, n_eligible2, score, second_score, n_proper;
@@ -484,6 +485,7 @@ typedef struct {
 	int32_t min_insert, max_insert;
 	int32_t unpaired_penalty;    /* 0 .. 65535 */
 	int32_t orientation;         /* SSW_MATES_FR / RF / FF: which strands and which order make a combination proper */
+	const uint16_t* ins_pen;     /* pair model: [max_insert - min_insert + 1], what a proper combination of span min_insert + i pays; NULL: nothing */
 	struct ssw_mate_rec* sel;    /* [nfrag] */
 	struct ssw_out_rec* out;     /* [2 * nfrag]: the chosen candidates' records as the fill wrote them (SSW_OUT_WORD kept), the record of an
 	                                empty target where a mate has none */

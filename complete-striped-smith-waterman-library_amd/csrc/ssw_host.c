@@ -3114,6 +3114,8 @@ typedef struct {
 	const int64_t* cand_off; int64_t ngroups; int32_t min_score; ssw_gpu_best* sel;
 	int32_t k, max_drop; int32_t* pos; int32_t* n_eligible;
 	ssw_gpu_mates* mates; int32_t nfwd, min_insert, max_insert, unpaired_penalty, orientation;
+	/* pair model (ssw_gpu_align_windows_mates_model): the caller's penalty table, n_ins = max_insert - min_insert + 1 entries; NULL: the flat rule */
+	const uint16_t* ins_pen; int64_t n_ins;
 	/* mate rescue (ssw_gpu_align_windows_mates_rescue; rescue_anchors == 0: none): the list is the augmented one, its four arrays are the
 	   entry point's own (r_*: the same memory, writable -- pairs_core enters the non-empty rescue slots), r_slots receives the slot table */
 	int32_t rescue_anchors, anchor_min_score, rescue_pad; const int32_t* mate_q;
@@ -3527,8 +3529,10 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		/* ---- select: candidate -> record slot, k_groupbest (k_grouptopk, k_matebest), one selection + one record (k positions + k records) per group to the host */
 		const int64_t ng = bm->ngroups;
 		int64_t nrecs = 2 * nj + nfb + (RA ? 1 : 0);      /* records of the call on the device (rescue: the last one is the empty slots') */
-		/* (4 bytes per candidate, 8 per group; mates: 16 more per candidate for the side table -- tbeg, tidx, length | strand) */
-		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, 8 * ((size_t)ng + 1) + (bm->mates ? 20 : 4) * (size_t)np);
+		/* (4 bytes per candidate, 8 per group; mates: 16 more per candidate for the side table -- tbeg, tidx, length | strand --, and behind it
+		   the pair model's penalty table, 2 bytes per entry) */
+		const size_t map_bytes = 8 * ((size_t)ng + 1) + (bm->mates ? 20 : 4) * (size_t)np;
+		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, map_bytes + (bm->ins_pen ? 2 * (size_t)bm->n_ins : 0));
 		slot = (int32_t*)malloc(sizeof(int32_t) * (bm->mates ? 2 : 1) * (size_t)np);
 		if (!d_map) goto done;
 		if (!slot) { fail(c, "out of host memory%s", ""); goto done; }
@@ -3550,6 +3554,10 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			for (int64_t i = 0; i < np; ++i) ls[i] = (uint32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) | (qidx[i] >= bm->nfwd ? 0x80000000u : 0u);
 			if (ssw_shim_h2d((void*)d_tbeg, src->tbeg, 8 * (size_t)np, c->stream) || ssw_shim_h2d((void*)(d_slot + np), tidx, 4 * (size_t)np, c->stream) ||
 			    ssw_shim_h2d((void*)(d_slot + 2 * np), ls, 4 * (size_t)np, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+			/* (once per call, before the rescue stage: k_materescue does not read it, k_matebest does, on the same stream) */
+			if (bm->ins_pen && ssw_shim_h2d(d_map + map_bytes, bm->ins_pen, 2 * (size_t)bm->n_ins, c->stream)) {
+				fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
+			}
 		}
 		if (RA) {
 			/* ---- rescue: k_materescue over the caller's candidates, the slot table (24 bytes per slot) to the host, the non-empty slots
@@ -3608,6 +3616,7 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			ma.rec = d_rec; ma.cand_off = d_off; ma.slot = d_slot; ma.tbeg = d_tbeg; ma.tidx = d_slot + np; ma.len_strand = (const uint32_t*)(d_slot + 2 * np);
 			ma.nfrag = ng / 2; ma.min_score = bm->min_score; ma.min_insert = bm->min_insert; ma.max_insert = bm->max_insert;
 			ma.unpaired_penalty = bm->unpaired_penalty; ma.orientation = bm->orientation;
+			ma.ins_pen = bm->ins_pen ? (const uint16_t*)(d_map + map_bytes) : 0;
 			ma.out = (struct ssw_out_rec*)d_sel; ma.sel = (struct ssw_mate_rec*)(d_sel + sizeof(struct ssw_out_rec) * (size_t)ng);
 			if (ssw_shim_launch_matebest(&ma, c->stream)) { fail(c, "matebest launch failed: %s", ssw_shim_last_error()); goto done; }
 			ssw_shim_event_record(c->ev_b, c->stream);
@@ -3883,7 +3892,8 @@ int ssw_gpu_align_windows_best(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_
  * Best candidate pair per read pair (ssw_gpu_align_windows_mates): the same select mode over 2 * nfrag groups, the selection per FRAGMENT
  * (k_matebest).  Device state that outlives a fill launch, an input / output of the call like the window table: per candidate 48 bytes of
  * record, 4 of slot map and 16 of side table (tbeg, tidx, read length | strand), per fragment 128 bytes of output (two records, one
- * selection) and 16 of offsets.
+ * selection) and 16 of offsets; under a pair model (ssw_gpu_align_windows_mates_model) the penalty table, 2 bytes per entry, behind the side
+ * table.
  * ------------------------------------------------------------------------------------------------ */
 static void mates_pad(ssw_gpu_mates* m) { memset(m, 0, sizeof *m); m->pos1 = m->pos2 = -1; }
 
@@ -3945,17 +3955,31 @@ static int mates_check(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, c
 	return 0;
 }
 
-static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+/* the pair model's own refusals, after mates_check's (min_insert <= max_insert holds): a table over more than SSW_GPU_INSERT_TABLE_MAX spans */
+static int model_check(ssw_gpu_ctx* c, const char* who, int32_t min_insert, int32_t max_insert, const uint16_t* ins_pen)
+{
+	const int64_t n_ins = (int64_t)max_insert - min_insert + 1;
+	if (!ins_pen || n_ins <= SSW_GPU_INSERT_TABLE_MAX) return 0;
+	char msg[200];
+	snprintf(msg, sizeof msg, "min_insert = %d, max_insert = %d: %lld entries", min_insert, max_insert, (long long)n_ins);
+	return fail_who_d(c, who, "insert_penalty covers more than 65536 spans", msg);
+}
+
+/* (who: the entry point's name in messages; ins_pen: the pair model's table or NULL -- ssw_gpu_align_windows_mates_lib is the NULL case) */
+static int align_windows_mates_locked(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
                                       const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
                                       const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty,
-                                      int32_t orientation, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+                                      int32_t orientation, const uint16_t* ins_pen, ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool,
+                                      int64_t* cigar_words)
 {
 	if (cigar_pool) *cigar_pool = 0;      /* (as ssw_gpu_align_windows_best: the pool outputs are emptied before the argument checks) */
 	if (cigar_words) *cigar_words = 0;
 	int64_t np = 0;
-	const int chk = mates_check(c, "align_windows_mates", Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm, min_insert, max_insert, unpaired_penalty,
+	const int chk = mates_check(c, who, Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm, min_insert, max_insert, unpaired_penalty,
 	                            orientation, sel, results, &np);
-	if (chk) return chk < 0 ? -1 : 0;
+	if (chk < 0) return -1;
+	if (model_check(c, who, min_insert, max_insert, ins_pen)) return -1;
+	if (chk) return 0;
 	const int64_t ng = 2 * nf;
 	if (np == 0) {      /* empty groups only */
 		memset(&c->tm, 0, sizeof c->tm);
@@ -3964,11 +3988,11 @@ static int align_windows_mates_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, con
 		return 0;
 	}
 	pair_src src; memset(&src, 0, sizeof src);
-	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = "align_windows_mates";
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = who;
 	best_mode bm; memset(&bm, 0, sizeof bm);
 	bm.cand_off = cand_off; bm.ngroups = ng; bm.min_score = min_score; bm.mates = sel;
 	bm.nfwd = nfwd; bm.min_insert = min_insert; bm.max_insert = max_insert; bm.unpaired_penalty = unpaired_penalty;
-	bm.orientation = orientation;
+	bm.orientation = orientation; bm.ins_pen = ins_pen; bm.n_ins = (int64_t)max_insert - min_insert + 1;
 	return pairs_core(c, Q, T, qidx, &src, np, prm, results, cigar_pool, cigar_words, &bm);
 }
 
@@ -3979,8 +4003,27 @@ int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const
 {
 	if (!c) return fail(0, "align_windows_mates: NULL context%s", "");
 	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
-	return ctx_leave(c, align_windows_mates_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
-	                                               unpaired_penalty, orientation, sel, results, cigar_pool, cigar_words));
+	return ctx_leave(c, align_windows_mates_locked(c, "align_windows_mates", Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert,
+	                                               max_insert, unpaired_penalty, orientation, 0, sel, results, cigar_pool, cigar_words));
+}
+
+/* ssw_gpu_align_windows_mates_lib under a pair model: the four pairing arguments in one struct, and a penalty per span of a proper combination */
+int ssw_gpu_align_windows_mates_model(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                      const ssw_gpu_params* prm, int32_t min_score, const ssw_gpu_pair_model* model,
+                                      ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	static const char who[] = "align_windows_mates_model";
+	if (!c) return fail(0, "%s: NULL context", who);
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	if (!model) {      /* (the pool outputs are emptied as by every other refusal) */
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return ctx_leave(c, fail_who_d(c, who, "NULL argument", "model"));
+	}
+	return ctx_leave(c, align_windows_mates_locked(c, who, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, model->min_insert,
+	                                               model->max_insert, model->unpaired_penalty, model->orientation, model->insert_penalty, sel, results,
+	                                               cigar_pool, cigar_words));
 }
 
 int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
@@ -3998,20 +4041,22 @@ int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
  * The augmented list is built here, with the slots empty; pairs_core enters the windows of the non-empty ones.  Device state beyond
  * the mates call's: 24 bytes per slot, 4 of mate_q per group, and the records and maps of the slots like any other candidate's.
  * ------------------------------------------------------------------------------------------------ */
-static int align_windows_mates_rescue_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
-                                             const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+static int align_windows_mates_rescue_locked(ssw_gpu_ctx* c, const char* who, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off,
+                                             int64_t nf, const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
                                              const int32_t* mate_q, const ssw_gpu_params* prm, int32_t min_score, int32_t min_insert, int32_t max_insert,
-                                             int32_t unpaired_penalty, int32_t orientation, int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
-                                             ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin, uint32_t** cigar_pool, int64_t* cigar_words)
+                                             int32_t unpaired_penalty, int32_t orientation, const uint16_t* ins_pen, int32_t max_anchors,
+                                             int32_t anchor_min_score, int32_t rescue_pad, ssw_gpu_mates* sel, ssw_gpu_result* results,
+                                             ssw_gpu_rescued* origin, uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	static const char who[] = "align_windows_mates_rescue";
 	char msg[240];
 	if (cigar_pool) *cigar_pool = 0;
 	if (cigar_words) *cigar_words = 0;
 	int64_t np = 0;
 	const int chk = mates_check(c, who, Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm, min_insert, max_insert, unpaired_penalty, orientation,
 	                            sel, results, &np);
-	if (chk) return chk < 0 ? -1 : 0;
+	if (chk < 0) return -1;
+	if (model_check(c, who, min_insert, max_insert, ins_pen)) return -1;
+	if (chk) return 0;
 	if (!mate_q || !origin) return fail_who(c, who, "NULL argument");
 	if ((int64_t)Q->count != 2 * (int64_t)nfwd) {
 		snprintf(msg, sizeof msg, "nfwd = %d, %d queries", nfwd, Q->count);
@@ -4071,7 +4116,7 @@ static int align_windows_mates_rescue_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs*
 	best_mode bm; memset(&bm, 0, sizeof bm);
 	bm.cand_off = off_a; bm.ngroups = ng; bm.min_score = min_score; bm.mates = sel;
 	bm.nfwd = nfwd; bm.min_insert = min_insert; bm.max_insert = max_insert; bm.unpaired_penalty = unpaired_penalty;
-	bm.orientation = orientation;
+	bm.orientation = orientation; bm.ins_pen = ins_pen; bm.n_ins = (int64_t)max_insert - min_insert + 1;
 	bm.rescue_anchors = max_anchors; bm.anchor_min_score = anchor_min_score; bm.rescue_pad = rescue_pad; bm.mate_q = mate_q;
 	bm.r_qidx = q_a; bm.r_tidx = t_a; bm.r_tbeg = b_a; bm.r_tlen = l_a; bm.r_slots = slots;
 	rc = pairs_core(c, Q, T, q_a, &src, npa, prm, results, cigar_pool, cigar_words, &bm);
@@ -4097,9 +4142,30 @@ int ssw_gpu_align_windows_mates_rescue(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, co
 {
 	if (!c) return fail(0, "align_windows_mates_rescue: NULL context%s", "");
 	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
-	return ctx_leave(c, align_windows_mates_rescue_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, mate_q, prm, min_score, min_insert,
-	                                                      max_insert, unpaired_penalty, orientation, max_anchors, anchor_min_score, rescue_pad,
-	                                                      sel, results, origin, cigar_pool, cigar_words));
+	return ctx_leave(c, align_windows_mates_rescue_locked(c, "align_windows_mates_rescue", Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, mate_q, prm,
+	                                                      min_score, min_insert, max_insert, unpaired_penalty, orientation, 0, max_anchors, anchor_min_score,
+	                                                      rescue_pad, sel, results, origin, cigar_pool, cigar_words));
+}
+
+/* ssw_gpu_align_windows_mates_rescue under a pair model: the rescue stage does not look at the table, the selection over the augmented list does */
+int ssw_gpu_align_windows_mates_rescue_model(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                                             const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                                             const int32_t* mate_q, const ssw_gpu_params* prm, int32_t min_score, const ssw_gpu_pair_model* model,
+                                             int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
+                                             ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	static const char who[] = "align_windows_mates_rescue_model";
+	if (!c) return fail(0, "%s: NULL context", who);
+	if (ctx_enter(c, cigar_pool, cigar_words)) return SSW_GPU_BUSY;
+	if (!model) {      /* (the pool outputs are emptied as by every other refusal) */
+		if (cigar_pool) *cigar_pool = 0;
+		if (cigar_words) *cigar_words = 0;
+		return ctx_leave(c, fail_who_d(c, who, "NULL argument", "model"));
+	}
+	return ctx_leave(c, align_windows_mates_rescue_locked(c, who, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, mate_q, prm, min_score,
+	                                                      model->min_insert, model->max_insert, model->unpaired_penalty, model->orientation,
+	                                                      model->insert_penalty, max_anchors, anchor_min_score, rescue_pad, sel, results, origin,
+	                                                      cigar_pool, cigar_words));
 }
 
 /* ------------------------------------------------------------------------------------------------

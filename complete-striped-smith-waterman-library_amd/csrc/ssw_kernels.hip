@@ -4471,6 +4471,13 @@ __global__ void __launch_bounds__(256) k_grouptopk(ssw_grouptopk_args a)
  *        (S + 65536) << 32 | ~c,   S = score1(a) + score1(b) - (proper ? 0 : unpaired_penalty) >= -65533
  *      so that a plain maximum is the ranking and 0 means none; a lane keeps its best two and counts the proper ones.  (pos1, pos2) advance
  *      by 16 combinations without a division; the digest of pos1 is fetched again only when pos1 changes.
+ *      With a pair model's penalty table (a.ins_pen != NULL; ssw_gpu_align_windows_mates_model) a proper combination of span D pays
+ *      ins_pen[D - min_insert] where the flat rule has 0 (mb_span hands out the span the proper test computes anyway).  The entries are
+ *      16-bit like unpaired_penalty, and both scores of an eligible x eligible combination are at least 1, so S >= 2 - 65535 = -65533
+ *      still: S + 65536 >= 3 fits the high half, the key is never 0, and "0 means none" holds.  The table is read with one plain
+ *      16-bit global load per proper combination -- at most 128 KiB, a few KiB as a rule, shared by every row and cache-resident; it is
+ *      not staged in LDS, whose 18 KiB per workgroup are what keeps eight workgroups on a CU.  `a.ins_pen != NULL` is a wave-uniform
+ *      test of a kernel argument: without a table the subtracted term is the flat rule's select and no load is issued.
  * Both steps end in gb_merge's four row rotations, outside every loop: trip counts may differ between the rows of a wavefront.  Lane 0
  * writes the 32-byte selection, lanes 0..2 copy the record chosen for mate 1 (or the padding record) and lanes 3..5 that of mate 2,
  * 16 bytes each.  No atomics, no waiting; the LDS hand-off stays inside a wavefront (wave_lds_fence).
@@ -4506,11 +4513,20 @@ SSW_DEV mb_dig mb_get(const ssw_matebest_args& a, const unsigned char* lds, u32 
    min_insert <= E(downstream) - B(upstream) + 1 <= max_insert with B = E - len + 1.  Downstream is the minus-strand one (FR), the
    plus-strand one (RF), mate 2 on the plus and mate 1 on the minus strand (FF): x exactly when x's strand bit differs from "RF".
    a.orientation is a kernel argument: both tests are wave-uniform selects, no branch. */
-SSW_DEV bool mb_proper(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y)
+/* mb_span: the same test, and the span D - min_insert of a proper combination in `idx` (0 .. max_insert - min_insert; 0 when not proper) */
+SSW_DEV bool mb_span(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y, u32& idx)
 {
+	idx = 0;
 	if ((x.ts ^ y.ts) != (a.orientation == SSW_MATES_FF ? 0u : 0x80000000u)) return false;
 	const long long ins = ((x.ts >> 31) ^ (u32)(a.orientation == SSW_MATES_RF)) ? x.E - y.EL : y.E - x.EL;
-	return ins >= (long long)a.min_insert && ins <= (long long)a.max_insert;
+	const bool pr = ins >= (long long)a.min_insert && ins <= (long long)a.max_insert;
+	if (pr) idx = (u32)(ins - (long long)a.min_insert);
+	return pr;
+}
+SSW_DEV bool mb_proper(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y)
+{
+	u32 idx;
+	return mb_span(a, x, y, idx);
 }
 
 __global__ void __launch_bounds__(256) k_matebest(ssw_matebest_args a)
@@ -4561,8 +4577,11 @@ __global__ void __launch_bounds__(256) k_matebest(ssw_matebest_args a)
 			if (da.s) {
 				const mb_dig db = mb_get(a, lds, base, in_lds, c0, n1 + (int)p2, lo);
 				if (db.s) {
-					const bool pr = mb_proper(a, da, db);
-					const unsigned long long k = ((unsigned long long)(da.s + db.s + 65536u - (pr ? 0u : (u32)a.unpaired_penalty)) << 32) | (u32)~c;
+					u32 di;
+					const bool pr = mb_span(a, da, db, di);
+					u32 pen = pr ? 0u : (u32)a.unpaired_penalty;
+					if (a.ins_pen && pr) pen = a.ins_pen[di];      /* (di <= max_insert - min_insert: inside the table) */
+					const unsigned long long k = ((unsigned long long)(da.s + db.s + 65536u - pen) << 32) | (u32)~c;
 					if (k > m1) { m2 = m1; m1 = k; } else if (k > m2) m2 = k;
 					npr += pr;
 				}

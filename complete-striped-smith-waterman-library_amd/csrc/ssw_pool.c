@@ -73,6 +73,7 @@ struct pool_call {
 	int32_t* pos; int32_t* n_eligible;
 	ssw_gpu_mates* mates;        /* ssw_gpu_align_windows_mates: one selection per fragment, and the rule's arguments */
 	int32_t min_insert, max_insert, unpaired_penalty, orientation;
+	const uint16_t* ins_pen;     /* pair model: the caller's penalty table, read-only and shared by the workers (each context uploads its own copy); NULL: the flat rule */
 	int64_t next;                /* next block index (atomic) */
 	int failed;                  /* first failure stops the hand-out (atomic) */
 	pthread_mutex_t err_lock;
@@ -185,7 +186,11 @@ static int run_windows(pool_call* k, pool_worker* w, win_scratch* ws, int64_t b,
 	int64_t* const cn = k->want_cigars ? &k->cig[b].n : 0;
 	if (k->cand_off) {
 		for (int64_t g = 0; g <= ng; ++g) ws->lco[g] = k->cand_off[g0 + g] - p0;
-		if (k->mates)
+		if (k->mates && k->ins_pen) {
+			const ssw_gpu_pair_model pm = { k->min_insert, k->max_insert, k->unpaired_penalty, k->orientation, k->ins_pen };
+			rc = ssw_gpu_align_windows_mates_model(w->ctx, Q, w->targets, ws->lco, cnt, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, m, k->prm,
+			                                       k->min_score, &pm, k->mates + u0, k->results + 2 * u0, cw, cn);
+		} else if (k->mates)
 			rc = ssw_gpu_align_windows_mates_lib(w->ctx, Q, w->targets, ws->lco, cnt, ws->lq, k->wt + p0, k->wbeg + p0, k->wlen + p0, m, k->prm,
 			                                     k->min_score, k->min_insert, k->max_insert, k->unpaired_penalty, k->orientation, k->mates + u0,
 			                                     k->results + 2 * u0, cw, cn);
@@ -491,17 +496,13 @@ int ssw_gpu_pool_align_windows_topk(ssw_gpu_pool* p, const int8_t* qcodes, const
 /* ssw_gpu_align_windows_mates_lib over the pool: a unit is a fragment -- two groups, two records, one selection.  Every check of the
    single-context call is made here over the whole list, so that the message names the caller's fragment, mate or pair and nothing is
    written before it */
-int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
-                                     const int64_t* cand_off, int64_t nfrag,
-                                     const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
-                                     int64_t block, const ssw_gpu_params* prm, int32_t min_score,
-                                     int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
-                                     ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+static int pool_mates(ssw_gpu_pool* p, const char* who, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+                      const int64_t* cand_off, int64_t nfrag,
+                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                      int64_t block, const ssw_gpu_params* prm, int32_t min_score,
+                      int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation, const uint16_t* ins_pen,
+                      ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
 {
-	const char* const who = "pool_align_windows_mates";
-	if (!p) return -1;
-	if (cigar_pool) *cigar_pool = 0;
-	if (cigar_words) *cigar_words = 0;
 	if (!qoffsets || nq < 0 || nfrag < 0 || !prm || !prm->mat || (nfrag > 0 && (!cand_off || !sel || !results))) {
 		snprintf(p->err, sizeof p->err, "%s: NULL argument", who);
 		return -1;
@@ -517,6 +518,11 @@ int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, cons
 	}
 	if (orientation < SSW_GPU_MATES_FR || orientation > SSW_GPU_MATES_FF) {
 		snprintf(p->err, sizeof p->err, "%s: orientation must be SSW_GPU_MATES_FR, _RF or _FF (orientation = %d)", who, orientation);
+		return -1;
+	}
+	if (ins_pen && (int64_t)max_insert - min_insert + 1 > SSW_GPU_INSERT_TABLE_MAX) {
+		snprintf(p->err, sizeof p->err, "%s: insert_penalty covers more than 65536 spans (min_insert = %d, max_insert = %d: %lld entries)", who, min_insert,
+		         max_insert, (long long)max_insert - min_insert + 1);
 		return -1;
 	}
 	if (nfrag > 0x7fffff00 / 2) {
@@ -547,6 +553,7 @@ int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, cons
 	c.cand_off = cand_off; c.wq = qidx; c.wt = tidx; c.wbeg = tbeg; c.wlen = tlen;
 	c.min_score = min_score; c.mates = sel;
 	c.min_insert = min_insert; c.max_insert = max_insert; c.unpaired_penalty = unpaired_penalty; c.orientation = orientation;
+	c.ins_pen = ins_pen;
 	if (block <= 0) block = windows_auto_block(p, cand_off[2 * nfrag]);
 	c.nblocks = cut_groups(cand_off, nfrag, 2, block, 0);
 	c.bstart = (int64_t*)malloc(sizeof(int64_t) * ((size_t)c.nblocks + 1));
@@ -556,6 +563,36 @@ int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, cons
 	const int rc = pool_run(p, &c, cigar_pool, cigar_words);
 	free(c.bstart);
 	return rc;
+}
+
+int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+                                     const int64_t* cand_off, int64_t nfrag,
+                                     const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                     int64_t block, const ssw_gpu_params* prm, int32_t min_score,
+                                     int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+                                     ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!p) return -1;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	return pool_mates(p, "pool_align_windows_mates", qcodes, qoffsets, nq, with_revcomp, cand_off, nfrag, qidx, tidx, tbeg, tlen, block, prm, min_score,
+	                  min_insert, max_insert, unpaired_penalty, orientation, 0, sel, results, cigar_pool, cigar_words);
+}
+
+/* ssw_gpu_align_windows_mates_model over the pool: the same blocks and checks, the model's table handed to every worker's call */
+int ssw_gpu_pool_align_windows_mates_model(ssw_gpu_pool* p, const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+                                           const int64_t* cand_off, int64_t nfrag,
+                                           const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                           int64_t block, const ssw_gpu_params* prm, int32_t min_score, const ssw_gpu_pair_model* model,
+                                           ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words)
+{
+	if (!p) return -1;
+	if (cigar_pool) *cigar_pool = 0;
+	if (cigar_words) *cigar_words = 0;
+	if (!model) { snprintf(p->err, sizeof p->err, "pool_align_windows_mates_model: NULL argument (model)"); return -1; }
+	return pool_mates(p, "pool_align_windows_mates_model", qcodes, qoffsets, nq, with_revcomp, cand_off, nfrag, qidx, tidx, tbeg, tlen, block, prm,
+	                  min_score, model->min_insert, model->max_insert, model->unpaired_penalty, model->orientation, model->insert_penalty, sel, results,
+	                  cigar_pool, cigar_words);
 }
 
 static int pool_run(ssw_gpu_pool* p, pool_call* kk, uint32_t** cigar_pool, int64_t* cigar_words)

@@ -11,6 +11,7 @@ This module never computes alignments itself: if the shared library (and through
 is missing, loading or calling fails loudly.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -35,6 +36,12 @@ class Params(C.Structure):
     _fields_ = [("mat", _i8p), ("n", C.c_int32), ("gapO", C.c_uint8), ("gapE", C.c_uint8), ("flag", C.c_uint8),
                 ("filters", C.c_uint16), ("filterd", C.c_int32), ("maskLen", C.c_int32), ("score_size", C.c_int8),
                 ("mark_mismatch", C.c_int8)]
+
+
+class PairModel(C.Structure):
+    """ssw_gpu_pair_model (include/ssw_gpu.h)."""
+    _fields_ = [("min_insert", C.c_int32), ("max_insert", C.c_int32), ("unpaired_penalty", C.c_int32), ("orientation", C.c_int32),
+                ("insert_penalty", C.POINTER(C.c_uint16))]
 
 
 class Result(C.Structure):
@@ -88,6 +95,42 @@ def _orientation(o):
             raise ValueError("orientation must be 'fr', 'rf', 'ff' or 0 .. 2")
         return MATES_ORIENTATION[o.lower()]
     return int(o)
+
+
+def _insert_table(insert_penalty, min_insert, max_insert):
+    """the insert_penalty keyword of the mates calls -> a C-contiguous uint16 array of max_insert - min_insert + 1 entries"""
+    t = np.asarray(insert_penalty)
+    if t.ndim != 1 or t.dtype.kind not in "iu":
+        raise ValueError("insert_penalty must be a 1-D integer array")
+    if t.shape[0] != int(max_insert) - int(min_insert) + 1:
+        raise ValueError("insert_penalty must have max_insert - min_insert + 1 = %d entries, not %d"
+                         % (int(max_insert) - int(min_insert) + 1, t.shape[0]))
+    if t.shape[0] > 0 and (int(t.min()) < 0 or int(t.max()) > 65535):
+        raise ValueError("insert_penalty entries must be 0 .. 65535")
+    return np.ascontiguousarray(t, dtype=np.uint16)
+
+
+def _pair_model(min_insert, max_insert, unpaired_penalty, orient, table):
+    return PairModel(int(min_insert), int(max_insert), int(unpaired_penalty), orient, table.ctypes.data_as(C.POINTER(C.c_uint16)))
+
+
+def insert_penalty_normal(mean, sd, min_insert, max_insert, match, cap):
+    """a penalty table for the insert_penalty keyword, for a library whose insert sizes are normal(mean, sd): entry i, for the span
+    D = min_insert + i, is min(cap, floor(0.721 * match * (-ln erfc(|D - mean| / (sd * sqrt 2))) + 0.5)), and cap where erfc
+    underflows to 0.  It is BWA-MEM's log-scaled insert term (0.721 = 1 / ln 4: log base 4 of the two-sided tail probability, in units
+    of the match score) with the sign turned into a penalty, 0 at the mean -> uint16 [max_insert - min_insert + 1].  Host arithmetic only."""
+    min_insert, max_insert, cap = int(min_insert), int(max_insert), int(cap)
+    if not sd > 0:
+        raise ValueError("sd must be > 0")
+    if min_insert > max_insert:
+        raise ValueError("min_insert <= max_insert required")
+    if cap < 0 or cap > 65535:
+        raise ValueError("cap must be 0 .. 65535")
+    out = np.zeros(max_insert - min_insert + 1, dtype=np.uint16)
+    for i in range(out.shape[0]):
+        e = math.erfc(abs(min_insert + i - mean) / (sd * math.sqrt(2.0)))
+        out[i] = cap if e <= 0.0 else min(cap, int(math.floor(0.721 * match * (-math.log(e)) + 0.5)))
+    return out
 
 
 def _mates_rebase(sel, res, co, tb):
@@ -179,6 +222,20 @@ def load(path=None):
                                                        C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_pool_align_windows_mates.restype = C.c_int
+    if hasattr(L, "ssw_gpu_align_windows_mates_model"):
+        L.ssw_gpu_align_windows_mates_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_int32, C.POINTER(Params), C.c_int32, C.POINTER(PairModel),
+                                                        C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_mates_model.restype = C.c_int
+        L.ssw_gpu_align_windows_mates_rescue_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Params), C.c_int32,
+                                                               C.POINTER(PairModel), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_align_windows_mates_rescue_model.restype = C.c_int
+        L.ssw_gpu_pool_align_windows_mates_model.argtypes = [C.c_void_p, _i8p, _i64p, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32,
+                                                             C.POINTER(PairModel), C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
+        L.ssw_gpu_pool_align_windows_mates_model.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -546,14 +603,17 @@ class Context(object):
 
     def align_windows_mates(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mat, n, min_insert, max_insert, unpaired_penalty,
                             min_score=0, rebase=False, gapO=3, gapE=1, flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True,
-                            mark_mismatch=False, out=None, orientation="fr"):
+                            mark_mismatch=False, out=None, orientation="fr", insert_penalty=None):
         """best candidate pair per read pair (ssw_gpu_align_windows_mates_lib): cand_off has 2 nfrag + 1 offsets, group 2 f the candidates of
         mate 1 of fragment f and group 2 f + 1 those of mate 2; candidate i is on the minus strand iff qidx[i] >= nfwd
         -> (sel [nfrag] of MATES_DTYPE, records [nfrag, 2] of RESULT_DTYPE -- the chosen candidates', or the empty record where pos1 / pos2
         is -1 --, uint32 CIGAR pool in (fragment, mate) order).  rebase=True adds the chosen candidate's tbeg to ref_begin1, ref_end1 and
         ref_end2 where they are >= 0.  `out`: (sel, records) to fill.  orientation: "fr" (default), "rf", "ff" or 0 .. 2 -- the
-        library orientation of the proper-pair rule (SSW_GPU_MATES_*)."""
+        library orientation of the proper-pair rule (SSW_GPU_MATES_*).  insert_penalty: None, or a 1-D integer array of
+        max_insert - min_insert + 1 entries 0 .. 65535 -- what a proper combination of span min_insert + i pays
+        (ssw_gpu_align_windows_mates_model; insert_penalty_normal builds one)."""
         orient = _orientation(orientation)
+        table = None if insert_penalty is None else _insert_table(insert_penalty, min_insert, max_insert)
         co = np.ascontiguousarray(cand_off, dtype=np.int64)
         qi = np.ascontiguousarray(qidx, dtype=np.int32)
         ti = np.ascontiguousarray(tidx, dtype=np.int32)
@@ -578,11 +638,19 @@ class Context(object):
                 raise ValueError("out must be C-contiguous arrays: MATES_DTYPE [nfrag], RESULT_DTYPE [nfrag, 2]")
         pool = _u32p()
         words = C.c_int64(0)
-        rc = self.lib.ssw_gpu_align_windows_mates_lib(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
-                                                      ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
-                                                      int(nfwd), C.byref(p), int(min_score), int(min_insert), int(max_insert),
-                                                      int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
-                                                      res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        if table is not None:
+            pm = _pair_model(min_insert, max_insert, unpaired_penalty, orient, table)
+            rc = self.lib.ssw_gpu_align_windows_mates_model(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), nf,
+                                                            qi.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                                                            tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p), int(nfwd), C.byref(p),
+                                                            int(min_score), C.byref(pm), sel.ctypes.data_as(C.c_void_p),
+                                                            res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        else:
+            rc = self.lib.ssw_gpu_align_windows_mates_lib(self.h, queries.h, targets.h, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
+                                                          ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                          int(nfwd), C.byref(p), int(min_score), int(min_insert), int(max_insert),
+                                                          int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
+                                                          res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
         if rc != 0:
             raise RuntimeError("ssw_gpu_align_windows_mates: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
         cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
@@ -594,14 +662,18 @@ class Context(object):
 
     def align_windows_mates_rescue(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mate_q, mat, n, min_insert, max_insert,
                                    unpaired_penalty, max_anchors=2, anchor_min_score=0, rescue_pad=16, min_score=0, rebase=False, gapO=3, gapE=1,
-                                   flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, orientation="fr"):
+                                   flag=0, filters=0, filterd=0, maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, orientation="fr",
+                                   insert_penalty=None):
         """align_windows_mates with mate rescue on the device (ssw_gpu_align_windows_mates_rescue): every group is followed by max_anchors
         rescue slots, windows in which a proper partner of the OTHER mate's best candidates would lie; mate_q[2 f + h] is the forward read
         of mate h of fragment f, `queries` holds the reads and their reverse complements (with_revcomp: count == 2 nfwd)
         -> (sel [nfrag] of MATES_DTYPE with pos1 / pos2 in the AUGMENTED groups, records [nfrag, 2] of RESULT_DTYPE, origin [nfrag, 2] of
         RESCUED_DTYPE -- window, query and anchor of every chosen candidate --, uint32 CIGAR pool in (fragment, mate) order).  rebase=True
-        adds origin["tbeg"] to ref_begin1, ref_end1 and ref_end2 where they are >= 0 (the winner's window may not be the caller's)."""
+        adds origin["tbeg"] to ref_begin1, ref_end1 and ref_end2 where they are >= 0 (the winner's window may not be the caller's).
+        insert_penalty as Context.align_windows_mates (ssw_gpu_align_windows_mates_rescue_model): the rescue windows do not depend on it,
+        the selection over the augmented list does."""
         orient = _orientation(orientation)
+        table = None if insert_penalty is None else _insert_table(insert_penalty, min_insert, max_insert)
         co = np.ascontiguousarray(cand_off, dtype=np.int64)
         qi = np.ascontiguousarray(qidx, dtype=np.int32)
         ti = np.ascontiguousarray(tidx, dtype=np.int32)
@@ -625,10 +697,17 @@ class Context(object):
         pool = _u32p()
         words = C.c_int64(0)
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self.lib.ssw_gpu_align_windows_mates_rescue(self.h, queries.h, targets.h, vp(co), nf, vp(qi), vp(ti), vp(tb), vp(tl), int(nfwd), vp(mq),
-                                                         C.byref(p), int(min_score), int(min_insert), int(max_insert), int(unpaired_penalty), orient,
-                                                         int(max_anchors), int(anchor_min_score), int(rescue_pad), vp(sel), vp(res), vp(org),
-                                                         C.byref(pool) if want_cigar else None, C.byref(words))
+        if table is not None:
+            pm = _pair_model(min_insert, max_insert, unpaired_penalty, orient, table)
+            rc = self.lib.ssw_gpu_align_windows_mates_rescue_model(self.h, queries.h, targets.h, vp(co), nf, vp(qi), vp(ti), vp(tb), vp(tl), int(nfwd),
+                                                                   vp(mq), C.byref(p), int(min_score), C.byref(pm), int(max_anchors),
+                                                                   int(anchor_min_score), int(rescue_pad), vp(sel), vp(res), vp(org),
+                                                                   C.byref(pool) if want_cigar else None, C.byref(words))
+        else:
+            rc = self.lib.ssw_gpu_align_windows_mates_rescue(self.h, queries.h, targets.h, vp(co), nf, vp(qi), vp(ti), vp(tb), vp(tl), int(nfwd), vp(mq),
+                                                             C.byref(p), int(min_score), int(min_insert), int(max_insert), int(unpaired_penalty), orient,
+                                                             int(max_anchors), int(anchor_min_score), int(rescue_pad), vp(sel), vp(res), vp(org),
+                                                             C.byref(pool) if want_cigar else None, C.byref(words))
         if rc != 0:
             raise RuntimeError("ssw_gpu_align_windows_mates_rescue: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
         cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)
@@ -908,14 +987,15 @@ class Pool(object):
 
     def align_windows_mates(self, reads, cand_off, qidx, tidx, tbeg, tlen, mat, n, min_insert, max_insert, unpaired_penalty, min_score=0,
                             orientation="fr", with_revcomp=False, rebase=False, block=0, gapO=3, gapE=1, flag=0, filters=0, filterd=0,
-                            maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None, packed=None):
+                            maskLen=-1, score_size=2, want_cigar=True, mark_mismatch=False, out=None, packed=None, insert_penalty=None):
         """Context.align_windows_mates over the pool (ssw_gpu_pool_align_windows_mates): reads from the host, windows of the pool's targets;
         cand_off has 2 nfrag + 1 offsets.  with_revcomp: qidx = nq + i names the reverse complement of read i -- the minus strand;
         without it everything is on the plus strand.  block: candidates per block of whole fragments (0: a few blocks per worker) -- the
         output does not depend on it
         -> (sel [nfrag] of MATES_DTYPE, records [nfrag, 2], uint32 CIGAR pool in (fragment, mate) order); orientation, rebase and out as
-        Context.align_windows_mates."""
+        Context.align_windows_mates; insert_penalty too (ssw_gpu_pool_align_windows_mates_model)."""
         orient = _orientation(orientation)
+        table = None if insert_penalty is None else _insert_table(insert_penalty, min_insert, max_insert)
         codes, off = packed if packed is not None else _pack(reads)
         co = np.ascontiguousarray(cand_off, dtype=np.int64)
         qi = np.ascontiguousarray(qidx, dtype=np.int32)
@@ -941,12 +1021,21 @@ class Pool(object):
                 raise ValueError("out must be C-contiguous arrays: MATES_DTYPE [nfrag], RESULT_DTYPE [nfrag, 2]")
         pool = _u32p()
         words = C.c_int64(0)
-        rc = self.lib.ssw_gpu_pool_align_windows_mates(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1,
-                                                       1 if with_revcomp else 0, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
-                                                       ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
-                                                       int(block), C.byref(p), int(min_score), int(min_insert), int(max_insert),
-                                                       int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
-                                                       res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        if table is not None:
+            pm = _pair_model(min_insert, max_insert, unpaired_penalty, orient, table)
+            rc = self.lib.ssw_gpu_pool_align_windows_mates_model(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1,
+                                                                 1 if with_revcomp else 0, co.ctypes.data_as(C.c_void_p), nf,
+                                                                 qi.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                                                                 tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p), int(block), C.byref(p),
+                                                                 int(min_score), C.byref(pm), sel.ctypes.data_as(C.c_void_p),
+                                                                 res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
+        else:
+            rc = self.lib.ssw_gpu_pool_align_windows_mates(self.h, codes.ctypes.data_as(_i8p), off.ctypes.data_as(_i64p), len(off) - 1,
+                                                           1 if with_revcomp else 0, co.ctypes.data_as(C.c_void_p), nf, qi.ctypes.data_as(C.c_void_p),
+                                                           ti.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                           int(block), C.byref(p), int(min_score), int(min_insert), int(max_insert),
+                                                           int(unpaired_penalty), orient, sel.ctypes.data_as(C.c_void_p),
+                                                           res.ctypes.data_as(C.c_void_p), C.byref(pool) if want_cigar else None, C.byref(words))
         if rc != 0:
             raise RuntimeError("ssw_gpu_pool_align_windows_mates: " + self.error())
         cig = np.ctypeslib.as_array(pool, shape=(words.value,)).copy() if want_cigar and words.value > 0 else np.zeros(0, dtype=np.uint32)

@@ -319,7 +319,8 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * the fallback once more for those that win.
  * Memory (inputs / outputs of the call like the window table, not scratch under ssw_gpu_get_budget): per candidate 48 bytes of record, 4
  * of slot map and a side table of 16 (tbeg, tidx, read length | strand); per fragment 128 bytes of output (two records, one selection)
- * and 16 of offsets.  Fill launches are cut to the budget as for ssw_gpu_align_windows.
+ * and 16 of offsets; under a pair model (ssw_gpu_align_windows_mates_model) 2 bytes per entry of the penalty table.  Fill launches are
+ * cut to the budget as for ssw_gpu_align_windows.
  * Errors (-1 with a message that names the fragment or the pair, before anything is launched or written): a NULL array, cand_off[0] != 0,
  * a decreasing cand_off, a group of more than SSW_GPU_MATES_GROUP_MAX candidates (pos1 * n2 + pos2 has to fit the 32-bit half of a
  * selection key with room to spare), 2 * nfrag or the candidate count beyond 0x7fffff00, nfwd outside [0, queries->count], min_insert < 0
@@ -339,7 +340,8 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * Over several contexts or devices: ssw_gpu_pool_align_windows_mates below.  C++: BatchAligner::AlignWindowsMates (ssw_gpu_cpp.h).
  * Mate rescue -- aligning a mate without a usable candidate where the other mate's anchors and the insert range put it:
  * ssw_gpu_align_windows_mates_rescue below.
- * Not provided: more than the best two combinations; an insert-size likelihood; a CLI option.
+ * An insert-size penalty per span in place of the flat "every proper combination costs the same": ssw_gpu_align_windows_mates_model below.
+ * Not provided: more than the best two combinations; estimating the insert-size distribution from data; MAPQ; a CLI option.
  */
 #define SSW_GPU_MATES_GROUP_MAX 4096
 #define SSW_GPU_MATES_FR 0
@@ -403,7 +405,8 @@ int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* querie
  * winners-only reverse pass and traceback are unchanged.
  * Memory beyond ssw_gpu_align_windows_mates_lib's (inputs / outputs of the call, not scratch under ssw_gpu_get_budget): 24 bytes per slot
  * (2 * nfrag * A slots), the record (48), slot map (4), side table (16) and window table (32) entries of the slots, and 8 bytes of mate_q
- * per fragment; on the host the augmented copy of the four candidate arrays (20 bytes per candidate and slot).
+ * per fragment; on the host the augmented copy of the four candidate arrays (20 bytes per candidate and slot).  Under a pair model
+ * (ssw_gpu_align_windows_mates_rescue_model) the penalty table's device copy, 2 bytes per entry, uploaded once per call.
  * Errors (-1 with a message that names the fragment, mate or pair, before anything is launched or written): every check of
  * ssw_gpu_align_windows_mates_lib; queries->count != 2 * nfwd (the reverse complements must be resident: ssw_gpu_seqs_with_revcomp);
  * mate_q or origin NULL; a mate_q outside [0, nfwd); a caller's candidate of group g whose qidx is neither mate_q[g] nor nfwd + mate_q[g];
@@ -414,7 +417,8 @@ int ssw_gpu_align_windows_mates_lib(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* querie
  * fill_ms, fill_launches and fill_cells cover both fills.  The augmented copy and the slot table are host work per candidate and slot
  * whether or not a window is filled (measured: DESIGN 6.18): a list with nothing to rescue is cheaper through
  * ssw_gpu_align_windows_mates_lib.
- * Not provided: a pool variant and a BatchAligner method; a CLI option; an insert-size likelihood; rescue from rescue candidates.
+ * Under a pair model (an insert-size penalty per span): ssw_gpu_align_windows_mates_rescue_model below.
+ * Not provided: a pool variant and a BatchAligner method; a CLI option; rescue from rescue candidates.
  */
 #define SSW_GPU_RESCUE_ANCHORS_MAX 8
 typedef struct {            /* where the chosen candidate of a mate came from: 24 bytes */
@@ -435,6 +439,64 @@ int ssw_gpu_align_windows_mates_rescue(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* que
                                        int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
                                        ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin,
                                        uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Pair model: ssw_gpu_align_windows_mates_lib's four pairing arguments plus an optional INSERT-SIZE PENALTY TABLE, so that a proper
+ * combination is priced by where its span D lies in the library's insert distribution, as a paired-end mapper scores it, and not merely
+ * by D being inside min_insert .. max_insert.  Groups, candidates and eligibility, E and B, the orientation table that defines D, the
+ * meaning of proper (one target, the orientation's strands, min_insert <= D <= max_insert), n_proper and proper, the one-mate case, the
+ * ranking order (S descending, then pos1, then pos2 ascending), the records and the CIGAR order are exactly
+ * ssw_gpu_align_windows_mates_lib's.  Only the score of a combination changes:
+ *   S(a, b) = score1(a) + score1(b) - (proper ? insert_penalty[D - min_insert] : unpaired_penalty)            (signed)
+ * insert_penalty is a host array of max_insert - min_insert + 1 entries, entry i for span D = min_insert + i, read during the call only;
+ * NULL stands for all zero.  The table is used AS GIVEN: it is not clamped against unpaired_penalty, so an entry above unpaired_penalty
+ * ranks that proper combination below an improper one of equal score sum (proper / n_proper still report properness as defined above).
+ * A caller who wants "a proper pair never scores below an improper one" caps the table at unpaired_penalty.  Entries are 0 .. 65535 like
+ * unpaired_penalty, so S >= 1 + 1 - 65535 = -65533 as before; second_score == 0 still means "no second combination" only when
+ * n_eligible1 * n_eligible2 < 2 (a real S of 0 is possible under any penalty, as with the flat rule).
+ * With insert_penalty == NULL or an all-zero table, sel, results, cigar_off and the pool words are bit for bit
+ * ssw_gpu_align_windows_mates_lib's.  A table for a normal insert distribution on BWA-MEM's scale: ssw_amd.insert_penalty_normal
+ * (Python; plain host arithmetic).
+ * ssw_gpu_align_windows_mates_model           ssw_gpu_align_windows_mates_lib under the model.
+ * ssw_gpu_align_windows_mates_rescue_model    ssw_gpu_align_windows_mates_rescue under the model: the rescue rule -- anchors, the "already has
+ *     a proper partner" test, the window formulas, clipping -- does not look at the table, so the slot table is the flat call's; only the
+ *     final selection over the augmented list does, and its answer is bit for bit ssw_gpu_align_windows_mates_model's over that list.
+ * ssw_gpu_pool_align_windows_mates_model (further down)   ssw_gpu_pool_align_windows_mates under the model.
+ * On the device: k_matebest's combination loop already computes D for the proper test; with a table it subtracts one 16-bit global load
+ * at D - min_insert where the flat rule subtracts nothing (no LDS: the selection's 18 KiB per workgroup stay as they are).
+ * Memory beyond the sibling's (an input of the call, not scratch under ssw_gpu_get_budget): the device copy of the table, 2 bytes per
+ * entry (at most 128 KiB), uploaded once per call on the call's stream -- also when the rescue stage runs.
+ * Errors (-1 with a message, before anything is launched or written): model == NULL; a non-NULL table with max_insert - min_insert + 1 >
+ * SSW_GPU_INSERT_TABLE_MAX (with a NULL table the range stays unlimited); every refusal of the sibling, applied to the model's fields.
+ * C++: BatchAligner::AlignWindowsMates' insert_penalty argument.  Python: the insert_penalty keyword of Context.align_windows_mates,
+ * Context.align_windows_mates_rescue and Pool.align_windows_mates.
+ * Not provided: estimating the distribution from data; MAPQ; a pool or BatchAligner variant of the rescue call; a CLI option.
+ */
+#define SSW_GPU_INSERT_TABLE_MAX 65536
+typedef struct {
+	int32_t min_insert, max_insert;      /* as ssw_gpu_align_windows_mates_lib */
+	int32_t unpaired_penalty;            /* 0 .. 65535 */
+	int32_t orientation;                 /* SSW_GPU_MATES_FR / _RF / _FF */
+	const uint16_t* insert_penalty;      /* host pointer: max_insert - min_insert + 1 entries, entry i for span D = min_insert + i; NULL: all zero */
+} ssw_gpu_pair_model;
+int ssw_gpu_align_windows_mates_model(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                                      const int64_t* cand_off, int64_t nfrag,
+                                      const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                      int32_t nfwd,
+                                      const ssw_gpu_params* params, int32_t min_score,
+                                      const ssw_gpu_pair_model* model,
+                                      ssw_gpu_mates* sel, ssw_gpu_result* results,
+                                      uint32_t** cigar_pool, int64_t* cigar_words);
+int ssw_gpu_align_windows_mates_rescue_model(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                                             const int64_t* cand_off, int64_t nfrag,
+                                             const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                                             int32_t nfwd,
+                                             const int32_t* mate_q,
+                                             const ssw_gpu_params* params, int32_t min_score,
+                                             const ssw_gpu_pair_model* model,
+                                             int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
+                                             ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin,
+                                             uint32_t** cigar_pool, int64_t* cigar_words);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
@@ -602,6 +664,20 @@ int ssw_gpu_pool_align_windows_mates(ssw_gpu_pool* pool,
         const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
         int64_t block, const ssw_gpu_params* params, int32_t min_score,
         int32_t min_insert, int32_t max_insert, int32_t unpaired_penalty, int32_t orientation,
+        ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
+/*
+ * ssw_gpu_pool_align_windows_mates under a pair model (ssw_gpu_pair_model above): bit for bit what ONE context gives for
+ * ssw_gpu_align_windows_mates_model over all the reads, whatever the workers and `block`.  model->insert_penalty is one read-only host
+ * array shared by the workers for the length of the call; every worker's context makes its own device copy per block (2 bytes per entry).
+ * Errors as ssw_gpu_pool_align_windows_mates, over the whole list before any worker starts, and: model == NULL; a non-NULL table with
+ * max_insert - min_insert + 1 > SSW_GPU_INSERT_TABLE_MAX.
+ */
+int ssw_gpu_pool_align_windows_mates_model(ssw_gpu_pool* pool,
+        const int8_t* qcodes, const int64_t* qoffsets, int32_t nq, int with_revcomp,
+        const int64_t* cand_off, int64_t nfrag,
+        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+        int64_t block, const ssw_gpu_params* params, int32_t min_score,
+        const ssw_gpu_pair_model* model,
         ssw_gpu_mates* sel, ssw_gpu_result* results, uint32_t** cigar_pool, int64_t* cigar_words);
 /* per worker, accumulated over the last pool call: blocks taken, reads uploaded, DP cells (readLen x refLen), device milliseconds */
 typedef struct { int32_t device; int64_t blocks; int64_t queries; int64_t cells; double busy_ms; } ssw_gpu_pool_stat;

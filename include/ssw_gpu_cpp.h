@@ -377,6 +377,8 @@ class BatchAligner {
   // Alignment where nothing was chosen).  For a winner on the reverse strand the aligned sequence is the reverse complement of reads[r]:
   // query_begin / query_end and the '=' / 'X' runs of cigar_string refer to it (DNA tables: codes 0 .. 3 are complemented, every other
   // character is kept, as the device does).  rebase = true adds the chosen window's begin to the three reference positions.
+  // insert_penalty (optional): the pair model's table (ssw_gpu_pair_model) -- max_insert - min_insert + 1 entries, entry i what a proper
+  // combination of span min_insert + i pays where the flat rule has 0; another length throws.  nullptr: the flat rule, the same call as before.
   struct MateWindow {
     int32_t reference;
     int64_t begin;
@@ -393,8 +395,11 @@ class BatchAligner {
   };
   void AlignWindowsMates(const std::vector<std::string>& reads, const std::vector<std::vector<MateWindow> >& candidates, const Filter& filter,
                          std::vector<Alignment>* alignments, std::vector<MatePair>* pairs, int32_t maskLen, int32_t min_insert, int32_t max_insert,
-                         int32_t unpaired_penalty, int32_t min_score = 0, int32_t orientation = SSW_GPU_MATES_FR, bool rebase = false) const {
+                         int32_t unpaired_penalty, int32_t min_score = 0, int32_t orientation = SSW_GPU_MATES_FR, bool rebase = false,
+                         const std::vector<uint16_t>* insert_penalty = nullptr) const {
     if (!targets_) throw std::runtime_error("BatchAligner::AlignWindowsMates: no reference sequences");
+    if (insert_penalty && (int64_t)insert_penalty->size() != (int64_t)max_insert - min_insert + 1)
+      throw std::runtime_error("BatchAligner::AlignWindowsMates: insert_penalty must have max_insert - min_insert + 1 entries");
     if (reads.size() % 2 != 0) throw std::runtime_error("BatchAligner::AlignWindowsMates: two reads per fragment");
     if (candidates.size() != reads.size()) throw std::runtime_error("BatchAligner::AlignWindowsMates: one candidate list per read");
     const int32_t nr = (int32_t)reads.size(), nf = nr / 2;
@@ -426,8 +431,16 @@ class BatchAligner {
     std::vector<ssw_gpu_result> res((size_t)nr);
     std::vector<ssw_gpu_mates> sel((size_t)nf);
     uint32_t* pool = 0; int64_t words = 0;
-    const int rc = ssw_gpu_align_windows_mates_lib(ctx_, Q, targets_, cand_off.data(), nf, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), nr, &p,
-                                                   min_score, min_insert, max_insert, unpaired_penalty, orientation, sel.data(), res.data(), &pool, &words);
+    int rc;
+    if (insert_penalty) {
+      ssw_gpu_pair_model model; memset(&model, 0, sizeof model);
+      model.min_insert = min_insert; model.max_insert = max_insert; model.unpaired_penalty = unpaired_penalty; model.orientation = orientation;
+      model.insert_penalty = insert_penalty->data();
+      rc = ssw_gpu_align_windows_mates_model(ctx_, Q, targets_, cand_off.data(), nf, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), nr, &p,
+                                             min_score, &model, sel.data(), res.data(), &pool, &words);
+    } else
+      rc = ssw_gpu_align_windows_mates_lib(ctx_, Q, targets_, cand_off.data(), nf, qidx.data(), tidx.data(), tbeg.data(), tlen.data(), nr, &p,
+                                           min_score, min_insert, max_insert, unpaired_penalty, orientation, sel.data(), res.data(), &pool, &words);
     ssw_gpu_seqs_free(Q);
     if (rc != 0) { free(pool); throw std::runtime_error(std::string("ssw_gpu_align_windows_mates: ") + (rc == SSW_GPU_BUSY ? ssw_gpu_strerror(rc) : ssw_gpu_last_error(ctx_))); }
     for (int32_t f = 0; f < nf; ++f) {
