@@ -240,6 +240,35 @@ template <bool HPAIR> SSW_DEV void fr_add_pair(u32 h0, u32 h1, u32 s0, u32 s1, u
 	const unsigned long long x = h + s;
 	x0 = (u32)x; x1 = (u32)(x >> 32);
 }
+/* the frame subtracts of TWO rows in one 64-bit add: y0 = x0 - c, y1 = x1 - c on the register pair that fr_add_pair delivers, c = gapO - gapE in
+   both halves, nc = -(c:c) as one 64-bit addend (uniform: a scalar register pair).  No borrow crosses a word while x0 >= c, none a half while
+   the low 15 bits of every half of x hold at least c: a live half is a value of the frame above the matrix minimum (ssw_frame_params), a
+   dead half 0x8000 + H of the row above, which stays a negative binary16 pattern.  The emulation checks exactly that */
+SSW_DEV void fr_sub_pair(u32& x0, u32& x1, u32 c, unsigned long long nc, u32& y0, u32& y1)
+{
+	unsigned long long x = (unsigned long long)x1 << 32 | x0;
+#ifdef SSW_SIMT_EMU
+	const u32 ch = c & 0xffffu;
+	if ((x0 & 0x7fffu) < ch || ((x0 >> 16) & 0x7fffu) < ch || (x1 & 0x7fffu) < ch || ((x1 >> 16) & 0x7fffu) < ch || x0 < c)
+		emu::fail("fr_sub_pair: a borrow crosses a half or a word");
+	if (x + nc != ((unsigned long long)(x1 - c) << 32 | (x0 - c))) emu::fail("fr_sub_pair: the pair subtract differs from the two 32-bit subtracts");
+#else
+	/* one register pair (no instruction), as the profile words of fr_add_pair -- and the rows go on with ITS halves: with the sums of fr_add_pair
+	   live beside it the pair is a copy, two v_mov per pair of rows */
+	asm("" : "+v"(x));
+	x0 = (u32)x; x1 = (u32)(x >> 32);
+#endif
+	const unsigned long long y = x + nc;
+	y0 = (u32)y; y1 = (u32)(y >> 32);
+}
+/* the same check for the one row that is subtracted alone (the last row of an odd R) */
+SSW_DEV u32 fr_sub_one(u32 x, u32 c)
+{
+#ifdef SSW_SIMT_EMU
+	if ((x & 0x7fffu) < (c & 0xffffu) || ((x >> 16) & 0x7fffu) < (c & 0xffffu)) emu::fail("fr_sub_one: a borrow crosses a half");
+#endif
+	return x - c;
+}
 SSW_DEV u32 umax32(u32 a, u32 b) { return a > b ? a : b; }
 /* 0xffff in every half where a > b (unsigned), else 0: saturating difference, min(., 1), x 0xffff -- three packed instructions.  One asm
    block on the device: written with the builtins, LLVM recognises the idiom at every step (umin(x, 1) -> x != 0, ...) and emits two 16-bit

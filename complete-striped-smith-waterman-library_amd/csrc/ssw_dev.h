@@ -85,6 +85,7 @@ typedef struct {
 	int32_t form;            /* form of the recurrence: 3: column frame (ssw_frame_params in ssw_host.c says when), 6.5 instructions per row of
 	                            which 3 are 32-bit adds; 0: plain int16 with the reference's saturation, 9 */
 	int32_t fr_base, fr_kmask;   /* form 3: phi(column) = fr_base + ((step & fr_kmask) + lanes - lane) * gapE */
+	int32_t dg;              /* k_fill8 only: gaps open from the diagonal candidate alone (fill8_diag_gaps in ssw_host.c says when that is exact) */
 } ssw_fill_args;
 
 /* several fill launches (geometry buckets of one register class) as ONE grid: k_fillm */

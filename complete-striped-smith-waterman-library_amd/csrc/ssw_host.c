@@ -72,6 +72,7 @@ typedef struct {
 	int pipe_low_prio;      /* SSW_GPU_PIPE_PRIO=low: the extra streams of a pipelined series at the LOWEST dispatch priority (the first form of round 6; measured slower) */
 	int pipe_parts;         /* SSW_GPU_PIPE_PARTS=2..8: the number of scratch parts / streams of a pipelined series (default 2; more were measured slower) */
 	int no_fill_half;       /* SSW_GPU_FILL_HALF=0: the 16-lane kernel also where the half-row chains (k_fill8) apply */
+	int no_fill_dg;         /* SSW_GPU_FILL_DG=0: k_fill8 opens gaps from every H (the recurrence before the diagonal-gap form) also where the scoring allows the diagonal alone */
 	int no_pipe;            /* SSW_GPU_PIPE=0: the launches of a chunked short-query bucket one after the other on the main stream (the form before round 6) */
 	int no_lit_spec;        /* SSW_GPU_LIT_SPEC=0: the lane-model kernel runs its 16-bit rules after the 8-bit ones (never both side by side: the form before round 6) */
 	int trace_no_cls80;     /* SSW_GPU_TRACE_CLS80=0: no 80-KiB LDS class for the traceback teams (the classes before round 6) */
@@ -126,6 +127,9 @@ struct ssw_gpu_seqs {
 	int64_t* h_off;
 	int32_t count;
 	int64_t total;
+	/* every residue code of the set lies in [code_lo, code_hi] (codes_ranged; 0: not known).  The fill kernels turn a code outside [0, n) into a
+	   null column; k_fill8's diagonal-gap form is exact only for targets without one (fill8_diag_gaps) */
+	int codes_ranged; int32_t code_lo, code_hi;
 };
 
 static __thread char g_open_err[512];   /* error of the last failed ssw_gpu_open of this thread */
@@ -177,6 +181,7 @@ static void knobs_load(ssw_knobs* k)
 	k->no_lit_spec = env_is("SSW_GPU_LIT_SPEC", '0');
 	k->no_pipe = env_is("SSW_GPU_PIPE", '0');
 	k->no_fill_half = env_is("SSW_GPU_FILL_HALF", '0');
+	k->no_fill_dg = env_is("SSW_GPU_FILL_DG", '0');
 	k->pipe_low_prio = env_is("SSW_GPU_PIPE_PRIO", 'l');
 	k->pipe_any_count = env_is("SSW_GPU_PIPE_EVEN", '0');
 	{ const int v = env_int("SSW_GPU_TRACE_W1MAX", 0); if (v >= 2 && v <= 254) k->trace_w1max = v; }
@@ -408,6 +413,12 @@ ssw_gpu_seqs* ssw_gpu_seqs_upload(ssw_gpu_ctx* c, const int8_t* codes, const int
 	    ssw_shim_stream_sync(us)) {
 		fail(c, "upload failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(s); return 0;
 	}
+	{
+		const int8_t* p = codes + offsets[0];
+		int lo = 127, hi = -128;
+		for (int64_t i = 0; i < s->total; ++i) { if (p[i] < lo) lo = p[i]; if (p[i] > hi) hi = p[i]; }
+		s->codes_ranged = 1; s->code_lo = lo; s->code_hi = hi;      /* (an empty set: lo > hi, inside every alphabet) */
+	}
 	return s;
 }
 
@@ -437,7 +448,17 @@ ssw_gpu_seqs* ssw_gpu_seqs_upload_ascii(ssw_gpu_ctx* c, const char* text, const 
 	}
 	ssw_shim_free(d_text); ssw_shim_free(d_tab);
 	if (!ok) { fail(c, "ascii upload failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(s); return 0; }
+	s->codes_ranged = 1; s->code_lo = 127; s->code_hi = -128;      /* whatever the table can deliver */
+	for (int i = 0; i < 128; ++i) { if (table128[i] < s->code_lo) s->code_lo = table128[i]; if (table128[i] > s->code_hi) s->code_hi = table128[i]; }
 	return s;
+}
+
+/* the complement maps the codes 0 .. 3 among themselves and leaves every other code as it is */
+static void seqs_range_revcomp(ssw_gpu_seqs* s, const ssw_gpu_seqs* in)
+{
+	s->codes_ranged = in->codes_ranged;
+	s->code_lo = in->code_lo < 0 || in->code_lo > in->code_hi ? in->code_lo : 0;
+	s->code_hi = in->code_hi > 3 || in->code_lo > in->code_hi ? in->code_hi : 3;
 }
 
 ssw_gpu_seqs* ssw_gpu_seqs_revcomp(ssw_gpu_ctx* c, const ssw_gpu_seqs* in)
@@ -453,6 +474,7 @@ ssw_gpu_seqs* ssw_gpu_seqs_revcomp(ssw_gpu_ctx* c, const ssw_gpu_seqs* in)
 	    ssw_shim_launch_prep(&pa, us) || ssw_shim_stream_sync(us)) {
 		fail(c, "revcomp failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(s); return 0;
 	}
+	seqs_range_revcomp(s, in);
 	return s;
 }
 
@@ -477,6 +499,7 @@ ssw_gpu_seqs* ssw_gpu_seqs_with_revcomp(ssw_gpu_ctx* c, const ssw_gpu_seqs* in)
 	    ssw_shim_launch_prep(&pa, us) || ssw_shim_stream_sync(us)) {
 		fail(c, "revcomp failed: %s", ssw_shim_last_error()); ssw_gpu_seqs_free(s); return 0;
 	}
+	seqs_range_revcomp(s, in);
 	return s;
 }
 
@@ -522,6 +545,19 @@ static int ssw_frame_params(const ssw_knobs* kn, int64_t top, int gapO, int gapE
 	if (top + b + (int64_t)(K + up) * gapE >= 31744) return 0;
 	*base = b; *kmask = K - 1;
 	return 1;
+}
+
+/* k_fill8 may open gaps from the diagonal candidate alone (chain_row8<.., DG> in ssw_kernels.hip; DESIGN.md "Gaps from the diagonal"): that drops a
+   vertical gap directly next to a horizontal one, which never scores more than the diagonal steps and the one gap that replace it when
+   gapO > gapE and no entry of the matrix is below -2 gapE -- and when every cell of the rectangle has a diagonal, that is, the target has no
+   null column: no residue code outside [0, n), known from the upload (a set whose range is not known keeps the full recurrence).  R8 = 9 and
+   R8 = 17 have no instance of the form (RowFrame8<R>::DG in ssw_kernels.hip: no pairs / a wavefront per SIMD lost).  The frame needs nothing more: x - (gapO - gapE) of a live row is
+   >= fr_base + gapE + min(mat) - (gapO - gapE) = 4 gapE + 8, and a dead half keeps H of the row above, >= fr_base + gapE, in its low 15 bits */
+static int fill8_diag_gaps(const ssw_knobs* kn, const ssw_gpu_seqs* T, int R8, int32_t n, int32_t minmat, int gapO, int gapE)
+{
+	if (kn->no_fill_dg || R8 == 9 || R8 == 17 || gapO <= gapE) return 0;
+	if (-(int64_t)minmat > 2 * (int64_t)gapE) return 0;
+	return T->codes_ranged && (T->code_lo > T->code_hi || (T->code_lo >= 0 && T->code_hi < n));
 }
 
 static int32_t halo_for(int32_t P, int32_t maxmat, int32_t gapE)
@@ -768,8 +804,11 @@ static int keyed_cmp(const void* a, const void* b)
    them: four per row and one diagonal add per two rows (a 64-bit add on a register pair; the last row of an odd R has its own), F's 4 x gapE
    after every class-3 row but the last, and the column maximum per class -- a maximum of three per two values, a single one for an odd
    value of classes 1 to 3, the three class offsets and the last fold.  R = 19: 103 / 19 = 5.42.  R = 9 is
-   the one instance without the blocked row frame (RowFrame8<9>::P in ssw_kernels.hip): the column frame's 6.5 */
-static double fill8_ops_per_row(int R)
+   the one instance without the blocked row frame (RowFrame8<9>::P in ssw_kernels.hip): the column frame's 6.5.
+   dg (gaps from the diagonal): three per row, and per two rows one more 64-bit add, the subtract of gapO - gapE (the last row of an odd R its own).
+   R = 19: 94 / 19 = 4.947; the exact counts are in include/ssw_gpu.h.  REPORTED is max(count, 5.0): the row-frame instances are held to
+   5.0 <= fill_ops_per_row < 6.5 by their tests */
+static double fill8_ops_per_row(int R, int dg)
 {
 	if (R == 9) return 6.5;
 	int cm = 0, last = 1;      /* last: values of the closing fold, class 0 first */
@@ -779,7 +818,8 @@ static double fill8_ops_per_row(int R)
 		if (k == 0) last += (n & 1) == 0;
 		else { cm += 1 + ((n & 1) == 0); ++last; }
 	}
-	return (double)(4 * R + (R + 1) / 2 + (R - 1) / 4 + cm + last / 2) / R;
+	const double ops = (double)((dg ? 3 : 4) * R + (dg ? 2 : 1) * ((R + 1) / 2) + (R - 1) / 4 + cm + last / 2) / R;
+	return dg && ops < 5.0 ? 5.0 : ops;
 }
 
 /* remembers which fill kernel evaluated most cells of the call (ssw_gpu_timing.fill_kernel) */
@@ -2380,12 +2420,13 @@ static int fill_args_for(const ssw_gpu_ctx* c, const batch_call* bc, const targe
 	fa->sg16 = fb->sg16; fa->sg8 = fb->sg8; fa->seg_stride = tp->seg_stride;
 	/* column-frame form of the recurrence whenever the bucket's scores leave room for the frame offsets below 31744 (no cell of
 	   the bucket scores more than its padded length x max(mat)); else plain int16 */
-	fa->form = 0; fa->fr_base = 0; fa->fr_kmask = 0;
+	fa->form = 0; fa->fr_base = 0; fa->fr_kmask = 0; fa->dg = 0;
 	if (bc->fill_form != 0 && ssw_frame_params(&c->kn, top, prm->gapO, prm->gapE, bc->minmat, 16, &fa->fr_base, &fa->fr_kmask)) fa->form = 3;
 	/* half-row chains: single-bucket launches of the frame form only (the frame of a chain of 8 positions) */
 	int32_t hb = 0, hk = 0;
 	if (!half || B->use_x || fa->form != 3 || !ssw_frame_params(&c->kn, top, prm->gapO, prm->gapE, bc->minmat, 8, &hb, &hk)) return 0;
 	fa->fr_base = hb; fa->fr_kmask = hk;
+	fa->dg = fill8_diag_gaps(&c->kn, bc->T, half, bc->n, bc->minmat, prm->gapO, prm->gapE);
 	return 1;
 }
 
@@ -2409,7 +2450,7 @@ static int fill_launch(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, in
 	const int use_x = B->use_x, conc = ndefer != 0;
 	const int32_t n = bc->n, refLen = tp->refLen, tile = P->tile, halo = P->halo, ntiles = P->ntiles;
 	ssw_fill_args fa;
-	const int use_half = fill_args_for(c, bc, tp, B, P, p0, np, fb, B->half && !conc, &fa);
+	const int use_half = fill_args_for(c, bc, tp, B, P, p0, np, fb, B->half && !conc ? B->half : 0, &fa);
 	int xform = 0;
 	if (use_x) {
 		int32_t xfr_base = 0, xfr_kmask = 0;
@@ -2448,12 +2489,12 @@ static int fill_launch(ssw_gpu_ctx* c, batch_call* bc, const target_plan* tp, in
 	const int64_t lc = cols * (int64_t)(use_half ? 8 * B->half : B->lanes * (B->tailR ? B->R * (B->strips - 1) + B->tailR : B->R * B->strips)) * 2 * np;
 	c->tm.fill_cells += lc;
 	char nm[48];
-	if (use_half) snprintf(nm, sizeof nm, "k_fill8<%d,frame>", B->half);
+	if (use_half) snprintf(nm, sizeof nm, fa.dg ? "k_fill8<%d,frame> dg" : "k_fill8<%d,frame>", B->half);
 	else if (!use_x) snprintf(nm, sizeof nm, "k_fill<%d,%s>", B->R, fa.form == 3 ? "frame" : "int16");
 	else if (B->lanes == 64 && B->tailR) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips + 1 of %d", B->R, xform == 3 ? "frame" : "int16", B->strips - 1, B->tailR);
 	else if (B->lanes == 64) snprintf(nm, sizeof nm, "k_chainq<%d,%s> x %d strips", B->R, xform == 3 ? "frame" : "int16", B->strips);
 	else snprintf(nm, sizeof nm, "k_chainx<%d,16 lanes> x %d strips", B->R, B->strips);
-	note_fill_kernel(c, lc, &bc->best_fill_cells, nm, use_half ? fill8_ops_per_row(B->half) : !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
+	note_fill_kernel(c, lc, &bc->best_fill_cells, nm, use_half ? fill8_ops_per_row(B->half, fa.dg) : !use_x ? (fa.form == 3 ? 6.5 : 9.0) : (B->lanes == 64 && xform == 3 ? 6.5 : 9.0), use_half ? B->half : B->R, B->strips);
 	return 0;
 }
 
@@ -3775,6 +3816,7 @@ static int windows_fallback(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu
 		}
 		ssw_gpu_seqs* G = seqs_new(c, goff, (int32_t)nd);
 		if (!G) goto out;
+		G->codes_ranged = T->codes_ranged; G->code_lo = T->code_lo; G->code_hi = T->code_hi;      /* windows of T */
 		unsigned char* d_g = (unsigned char*)ssw_shim_malloc(12 * (size_t)nd);
 		ssw_seqgather_args ga; memset(&ga, 0, sizeof ga);
 		ga.src = T->d_codes; ga.src_off = T->d_off; ga.src_beg = (const int64_t*)d_g; ga.idx = (const int32_t*)(d_g + 8 * (size_t)nd);

@@ -408,6 +408,10 @@ template <int R> struct RowFrame8 {
 	   ds_read_b128 delivers, and the H of rows 2j - 1 and 2j neighbours.  R8 = 9 keeps its rows as they were */
 	static constexpr bool PAIR = P != 1;
 	static constexpr bool HPAIR = R <= 7;      /* fr_add_pair: H as an opaque register pair too */
+	/* the instances that have the form with gaps from the diagonal (chain_row8<.., DG>; fill8_diag_gaps in ssw_host.c names the same two
+	   exceptions).  R8 = 17 needs 102 registers in it, four wavefronts per SIMD where the old form's 96 give five, and 28 bytes of scratch when
+	   it is held to 96: it keeps the old form */
+	static constexpr bool DG = PAIR && R != 17;
 };
 template <int R, int... I> SSW_DEV void rows_set_cls(Rows8<R>& a, u32 v, u32 g, RowSeq<I...>) { ((row_at<I>(a) = v + (u32)RowFrame8<R>::cls(I) * g), ...); }
 SSW_DEV u32 pk_max_all(u32 a) { return a; }
@@ -418,29 +422,46 @@ template <typename... T> SSW_DEV u32 pk_max_all(u32 a, u32 b, u32 c, T... rest) 
    before the new one is born and both can live in one register.  With PAIR an odd row forms it for the two rows below it at once, from its
    own old H and the old H of the row below (x2: the second sum, which the even row hands on), and the last row of an odd R has its own add.
    a0 .. a3: the column maximum per class, the rows r - P and r in one maximum of three (H of row r - P is this step's, just written);
-   fl0 .. fl3: phi(column + 1) in the four classes */
-template <int R, int r>
-SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& x2, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
-                        u32 c1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3)
+   fl0 .. fl3: phi(column + 1) in the four classes.
+   DG: gaps open from the diagonal candidate only (DESIGN.md "Gaps from the diagonal"): xc = x - (gapO - gapE) takes the place of t = h - (gapO - gapE)
+   in E and F.  It is formed where x is -- rows 2j and 2j + 1 in one 64-bit add on the pair that fr_add_pair delivers (fr_sub_pair, nc1 = -(c1:c1)) --
+   and leaves the chain h -> t -> F -> h of the next row one maximum per row.  xc goes FIRST into the maxima of three: in a dead row it is the
+   one operand with bit 15 set */
+template <int R, int r, bool DG>
+SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& x2, u32& xc, u32& xc2, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
+                        u32 c1, unsigned long long nc1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3)
 {
 	typedef RowFrame8<R> F;
 	constexpr int P = F::P, k = F::cls(r), j = r / P + (k == 0), n = F::count(k);
 	u32& Hr = row_at<r>(H); u32& Er = row_at<r>(E);
 	u32& a = k == 0 ? a0 : k == 1 ? a1 : k == 2 ? a2 : a3;
-	u32 xn = 0u;
-	if constexpr (F::PAIR && (r & 1) == 0) xn = x2;
-	else if constexpr (F::PAIR && r + 2 < R) fr_add_pair<F::HPAIR>(Hr, row_at<(r + 2 < R ? r + 1 : 0)>(H), sc[(r + 1) >> 2][(r + 1) & 3], sc[(r + 1) >> 2][(r + 2) & 3], xn, x2);
-	else if constexpr (r + 1 < R) xn = Hr + sc[(r + 1) >> 2][(r + 1) & 3];
+	u32 xn = 0u, xcn = 0u;
+	if constexpr (F::PAIR && (r & 1) == 0) { xn = x2; xcn = xc2; }
+	else if constexpr (F::PAIR && r + 2 < R) {
+		fr_add_pair<F::HPAIR>(Hr, row_at<(r + 2 < R ? r + 1 : 0)>(H), sc[(r + 1) >> 2][(r + 1) & 3], sc[(r + 1) >> 2][(r + 2) & 3], xn, x2);
+		if constexpr (DG) fr_sub_pair(xn, x2, c1, nc1, xcn, xc2);
+	} else if constexpr (r + 1 < R) {
+		xn = Hr + sc[(r + 1) >> 2][(r + 1) & 3];
+		if constexpr (DG) xcn = fr_sub_one(xn, c1);
+	}
 	const u32 h = pk_max3_fr(x, Er, f);
-	const u32 t = h - c1;
-	Er = pk_max3_fr(Er, t, k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3);
-	f = pk_max(f, t);
+	if constexpr (DG) {
+		/* F takes E's floor: t kept it at h - (gapO - gapE) >= 0, xc of a dead row or a null column does not, and an F that only decays
+		   leaves the range.  The floor is the true value 0 for the F that enters the next row, below which h never looks */
+		const u32 fl = k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3;
+		Er = pk_max3_fr(xc, Er, fl);
+		f = pk_max3_fr(xc, f, fl);
+	} else {
+		const u32 t = h - c1;
+		Er = pk_max3_fr(Er, t, k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3);
+		f = pk_max(f, t);
+	}
 	if (r != R - 1 && F::cls(r + 1) == 0) f -= (u32)(k + 1) * gapE2;      /* back to class 0; the last row leaves f OPEN, in its own class */
 	if (j == 0) a = h;
 	else if ((j & 1) == 0) a = pk_max3_fr(a, row_at<(r >= P ? r - P : 0)>(H), h);
 	else if (j == n - 1 && k != 0) a = pk_max(a, h);      /* (class 0's single value waits for cm_finish8) */
 	Hr = h;
-	x = xn;
+	x = xn; xc = xcn;
 }
 /* the step's column maximum in class 0 from the four classes' */
 template <int R>
@@ -458,14 +479,19 @@ SSW_DEV u32 cm_finish8(Rows8<R>& H, u32 a0, u32 a1, u32 a2, u32 a3, u32 gapE2)
 	else if constexpr (R == 2) return pk_max_all(a0, row_at<0>(H), a1 - gapE2);
 	else return pk_max_all(a0, row_at<0>(H));
 }
-template <int R, int... I>
-SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32 cm, u32 c1, u32 gapE2,
+template <bool DG, int R, int... I>
+SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32 cm, u32 c1, unsigned long long nc1, u32 gapE2,
                            u32 fl0, u32 fl1, u32 fl2, u32 fl3, RowSeq<I...>)
 {
-	u32 x, x2 = 0, a0 = cm, a1 = 0, a2 = 0, a3 = 0;
-	if constexpr (RowFrame8<R>::PAIR && R >= 2) fr_add_pair<RowFrame8<R>::HPAIR>(d, row_at<0>(H), sc[0][0], sc[0][1], x, x2);      /* rows 0 and 1: the incoming diagonal and the old H[0] */
-	else x = d + sc[0][0];
-	(chain_row8<R, I>(sc, H, E, x, x2, f, a0, a1, a2, a3, c1, gapE2, fl0, fl1, fl2, fl3), ...);
+	u32 x, x2 = 0, xc = 0, xc2 = 0, a0 = cm, a1 = 0, a2 = 0, a3 = 0;
+	if constexpr (RowFrame8<R>::PAIR && R >= 2) {      /* rows 0 and 1: the incoming diagonal and the old H[0] */
+		fr_add_pair<RowFrame8<R>::HPAIR>(d, row_at<0>(H), sc[0][0], sc[0][1], x, x2);
+		if constexpr (DG) fr_sub_pair(x, x2, c1, nc1, xc, xc2);
+	} else {
+		x = d + sc[0][0];
+		if constexpr (DG) xc = fr_sub_one(x, c1);
+	}
+	(chain_row8<R, I, DG>(sc, H, E, x, x2, xc, xc2, f, a0, a1, a2, a3, c1, nc1, gapE2, fl0, fl1, fl2, fl3), ...);
 	return cm_finish8<R>(H, a0, a1, a2, a3, gapE2);
 }
 
@@ -584,9 +610,10 @@ SSW_DEV void fill_flush8(unsigned char* lds, u32 rb, int base, int l16, int stor
 	}
 }
 
-template <int R>
+template <int R, bool DG>
 SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* lds)
 {
+	static_assert(!DG || RowFrame8<R>::DG, "gaps from the diagonal: no such instance");
 	typedef ChainGeom<R> G;
 	constexpr int C = G::C;
 	const int tid = (int)threadIdx.x, l16 = tid & 15, grp = tid >> 4, ch = l16 & 1, pos = l16 >> 1;
@@ -662,6 +689,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	u32 Hlast = zero0 + klg, Fout = zero0 + klg + a.gapE2, cmout = zero0, hsave = zero0 + klg;      /* (H and the open F leave a position in class KL) */
 	const u32 lane_prof = (u32)(ch * 8 + pos) * 16u;
 	const u32 gO = a.gapO2 - a.gapE2, gE = a.gapE2;
+	const unsigned long long ngO = 0ull - ((unsigned long long)gO << 32 | gO);      /* (DG: fr_sub_pair's addend) */
 	const u32 gEv = opaque(klg + gE);                      /* F comes down to class 0 while the next position takes it over */
 	u32 fin = 0;
 	const u32 park = rb + (u32)ch * PARK8_BYTES, rbl = opaque(rb + 4u * (u32)l16);      /* position 7 of each chain parks, every lane of the row reads one step back */
@@ -702,7 +730,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 			else { const u32 up = fl3 + gE; fl0 = fl1; fl1 = fl2; fl2 = fl3; fl3 = up; }
 			xl_row_shr2_sub_keep(fin, Fout, gEv);
 			u32 f = fin, d = hsave;
-			const u32 cm = chain_rows_fr8(sc, H, E, d, f, xl_row_shr2_zero(cmout), gO, gE, fl0, fl1, fl2, fl3, Rows());
+			const u32 cm = chain_rows_fr8<DG>(sc, H, E, d, f, xl_row_shr2_zero(cmout), gO, ngO, gE, fl0, fl1, fl2, fl3, Rows());
 			hsave = hin; Hlast = row_at<R - 1>(H); Fout = f; cmout = cm;
 			if (pos == 7) {      /* raw: the frame of this step (hprev: one gapE below it) */
 				lds_st32(lds, park + 4u * j, cm); lds_st32(lds, park + 64u + 4u * j, f); lds_st32(lds, park + 128u + 4u * j, hprev);
@@ -718,11 +746,11 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 
 /* register budget per class as for k_fill: up to 9 rows per position 72 registers, up to 15 96, beyond that 128.  (R8 = 19 held to 96
    registers -- five wavefronts per SIMD, with spills -- measured 2.9 % slower than at 118 registers and four: docs/NOTEBOOK.md) */
-template <int R>
+template <int R, bool DG>
 __global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(R <= 9 ? 7 : R <= 15 ? 5 : 4, 8) k_fill8(ssw_fill_args a)
 {
 	SSW_DYN_LDS(lds);
-	fill_body8<R>(a, (int)blockIdx.x, lds);
+	fill_body8<R, DG>(a, (int)blockIdx.x, lds);
 }
 
 /* k_fillm: SEVERAL geometry buckets in one launch (round 4).  A batch of mixed read lengths -- the reference's own benchmark: 1000 reads of
@@ -4819,7 +4847,8 @@ extern "C" int ssw_shim_launch_fill(int R, const ssw_fill_args* a, void* stream)
 	return SSW_LAUNCH_OK();
 }
 
-/* half-row chains: R8 = ceil(len / 8) rows per position, odd values up to 23; frame form only */
+/* half-row chains: R8 = ceil(len / 8) rows per position, odd values up to 23; frame form only.  a->dg: gaps from the diagonal only (the
+   instances with RowFrame8::DG: every R8 but 9 and 17) */
 extern "C" int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* stream)
 {
 	ssw_fill_args args = *a;
@@ -4828,7 +4857,9 @@ extern "C" int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* strea
 	if (args.form != 3) return -2;
 	switch (R8) {
 #define X(r) case r: { const size_t ldsb = (size_t)(args.n + 1) * ChainGeom<r>::PSTRIDE + 16 * CHAIN8_BYTES; \
-		SSW_LAUNCH((k_fill8<r>), ssw_fill_args, args, grid, 256, ldsb, stream); } break;
+		if (args.dg && !RowFrame8<r>::DG) return -2; \
+		if (args.dg) SSW_LAUNCH((k_fill8<r, RowFrame8<r>::DG>), ssw_fill_args, args, grid, 256, ldsb, stream); \
+		else SSW_LAUNCH((k_fill8<r, false>), ssw_fill_args, args, grid, 256, ldsb, stream); } break;
 		X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23)
 #undef X
 		default: return -2;

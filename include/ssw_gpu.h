@@ -79,6 +79,9 @@ typedef struct {
 	char fill_kernel[48];  /* e.g. "k_fill<10,frame>", "k_chainq<12,frame> x 14 strips", "k_chainq<12,pairs,frame> x 13 strips + 1 of 1", "k_filldb<19,frame>" */
 	double fill_ops_per_row; /* VALU instructions of the recurrence per (row, column) of a query pair in that kernel: 6.5 (column frame) / 7.5 / 8.5 / 9;
 	                            k_fill8<R> (column frame + blocked row frame, one diagonal add per two rows): its own count per instance, 5.42 at R = 19.
+	                            "k_fill8<R,frame> dg" (gaps open from the diagonal candidate only, where the scoring and the target allow it):
+	                            max(count, 5.0), the counts being 6/1, 17/3, 28/5, 38/7, 56/11, 66/13, 76/15, 94/19 = 4.947, 104/21 = 4.952 and
+	                            114/23 = 4.957 -- the three largest instances report 5.0; R = 9 and R = 17 have no such form.
 	                            k_chainq<R,pairs,..> reports the batch fill's 6.5 / 9 although it merges the two halves' profile entries per row
 	                            (one more instruction): a roofline computed from it is understated for that kernel */
 	int32_t fill_rows_per_lane;
