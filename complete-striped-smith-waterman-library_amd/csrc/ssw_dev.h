@@ -520,6 +520,27 @@ typedef struct {
 } ssw_materescue_args;
 #define SSW_RESCUE_ANCHORS_MAX 8      /* SSW_GPU_RESCUE_ANCHORS_MAX */
 
+/* Insert-size histogram (ssw_gpu_insert_hist): k_matebest's inputs, eligibility, E and B over the same 2 * nfrag groups.  Per fragment the
+   best eligible candidate of either mate (k_groupbest's order) and its runner-up's score1; a fragment in which both mates have one
+   (counter BOTH), either best leads its runner-up by min_margin (UNIQUE) and both bests lie on one target (SAME) is tested under every
+   orientation o whose strand rule its two strands satisfy: the span D_o of the orientation table, 64-bit and unclamped, goes to
+   hist[o * (max_span + 1) + D_o] when 0 <= D_o <= max_span (counter IN + o), else to counter OUT + o.  hist and counters are zero on
+   entry; every update is a 32-bit integer atomic add, so the sums do not depend on the order of arrival. */
+#define SSW_ISTAT_BOTH 0
+#define SSW_ISTAT_UNIQUE 1
+#define SSW_ISTAT_SAME 2
+#define SSW_ISTAT_IN 3                /* + orientation */
+#define SSW_ISTAT_OUT 6               /* + orientation */
+#define SSW_ISTAT_USED 9
+#define SSW_ISTAT_COUNTERS 16         /* words of the counter block (the rest stays 0) */
+typedef struct {
+	ssw_matebest_args m;         /* k_matebest's inputs (min_insert .. orientation, ins_pen, sel / out unused) */
+	int32_t min_margin;          /* 0 .. 65535 */
+	int32_t max_span;            /* 0 .. SSW_GPU_INSERT_SPAN_MAX */
+	uint32_t* hist;              /* [3][max_span + 1] */
+	uint32_t* counters;          /* [SSW_ISTAT_COUNTERS] */
+} ssw_insertstat_args;
+
 /* n 16-byte pieces from src to dst (the call-long record array of a select-mode call moving into a larger allocation) */
 typedef struct {
 	const void* src;
@@ -630,6 +651,7 @@ int ssw_shim_launch_groupbest(const ssw_groupbest_args* a, void* stream);   /* o
 int ssw_shim_launch_grouptopk(const ssw_grouptopk_args* a, void* stream);   /* the same geometry, k ranks per group */
 int ssw_shim_launch_matebest(const ssw_matebest_args* a, void* stream);     /* one DPP row of 16 lanes per fragment (two groups) */
 int ssw_shim_launch_materescue(const ssw_materescue_args* a, void* stream); /* k_matebest's geometry */
+int ssw_shim_launch_insertstat(const ssw_insertstat_args* a, int workgroups, void* stream);   /* k_matebest's rows, striding over the fragments */
 int ssw_shim_launch_copy16(const ssw_copy16_args* a, void* stream);
 int ssw_shim_launch_selftest(const ssw_selftest_args* a, int blocks, void* stream);
 

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <math.h>
 #include <pthread.h>
 #include "ssw.h"
 #include "ssw_gpu.h"
@@ -84,6 +85,7 @@ typedef struct {
 	int no_tail;            /* SSW_GPU_NO_TAIL=1: equal strips for long queries (no short last strip of the strip kernel: the form before the end of round 4) */
 	int no_band;            /* SSW_GPU_NO_BAND=1: the capped reverse pass of the strip kernel visits whole windows (the form before round 4) */
 	int call_trace;         /* SSW_GPU_CALL_TRACE=1: host timestamps of the phases of every batch call on stderr */
+	int istat_groups;       /* SSW_GPU_ISTAT_GROUPS=<n>: k_insertstat on a grid of n workgroups, never more than the fragments need (tests: n = 1, 2 make a few dozen fragments cross the stride loop); 0: four per compute unit */
 	int db_tsub, dbx_slab;  /* SSW_GPU_DB_TSUB / SSW_GPU_DBX_SLAB: targets per chunk of the database search / survivors per traceback slab (tests: force
 	                           several chunks and slabs on toy batches); 0: from the budget */
 } ssw_knobs;
@@ -192,6 +194,7 @@ static void knobs_load(ssw_knobs* k)
 	k->no_tail = env_is("SSW_GPU_NO_TAIL", '1');
 	{ const int v = env_int("SSW_GPU_DB_TSUB", 0); k->db_tsub = v > 0 ? v : 0; }
 	{ const int v = env_int("SSW_GPU_DBX_SLAB", 0); k->dbx_slab = v > 0 ? v : 0; }
+	{ const int v = env_int("SSW_GPU_ISTAT_GROUPS", 0); k->istat_groups = v > 0 ? v : 0; }
 #endif
 }
 #ifdef SSW_GPU_TEST_HOOKS
@@ -3161,11 +3164,15 @@ typedef struct {
 	   entry point's own (r_*: the same memory, writable -- pairs_core enters the non-empty rescue slots), r_slots receives the slot table */
 	int32_t rescue_anchors, anchor_min_score, rescue_pad; const int32_t* mate_q;
 	int32_t* r_qidx; int32_t* r_tidx; int64_t* r_tbeg; int32_t* r_tlen; ssw_gpu_rescued* r_slots;
+	/* insert-size histogram (ssw_gpu_insert_hist; `ihist`): the groups, nfwd and the side table of a mates call, k_insertstat in place of
+	   k_matebest, `ihist` ([3][max_span + 1]) and `icounts` the only outputs -- `results` is NULL, nothing goes on to the flagged phases */
+	uint32_t* ihist; ssw_gpu_insert_counts* icounts; int32_t min_margin, max_span;
 } best_mode;
 /* device bytes of the per-group output behind the call-long record array: record + selection (64; mates: 48 + half of the fragment's 32) /
    k records, k positions and a count */
 static size_t best_out_bytes(const best_mode* bm)
 {
+	if (bm->ihist) return 0;      /* (bins and counters lie behind the slot map) */
 	return bm->k ? (size_t)bm->ngroups * ((sizeof(struct ssw_out_rec) + 4) * (size_t)bm->k + 4) : 64 * (size_t)bm->ngroups;
 }
 
@@ -3572,9 +3579,12 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		int64_t nrecs = 2 * nj + nfb + (RA ? 1 : 0);      /* records of the call on the device (rescue: the last one is the empty slots') */
 		/* (4 bytes per candidate, 8 per group; mates: 16 more per candidate for the side table -- tbeg, tidx, length | strand --, and behind it
 		   the pair model's penalty table, 2 bytes per entry) */
-		const size_t map_bytes = 8 * ((size_t)ng + 1) + (bm->mates ? 20 : 4) * (size_t)np;
-		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, map_bytes + (bm->ins_pen ? 2 * (size_t)bm->n_ins : 0));
-		slot = (int32_t*)malloc(sizeof(int32_t) * (bm->mates ? 2 : 1) * (size_t)np);
+		const int side = bm->mates || bm->ihist;      /* the calls with a side table */
+		const size_t map_bytes = 8 * ((size_t)ng + 1) + (side ? 20 : 4) * (size_t)np;
+		/* (insert histogram: 3 * (max_span + 1) bins and SSW_ISTAT_COUNTERS counters, 32-bit, where a pair model's table would lie) */
+		const size_t istat_bytes = bm->ihist ? 4 * (3 * ((size_t)bm->max_span + 1) + SSW_ISTAT_COUNTERS) : 0;
+		unsigned char* d_map = (unsigned char*)ensure(c, &c->bmap, map_bytes + (bm->ins_pen ? 2 * (size_t)bm->n_ins : 0) + istat_bytes);
+		slot = (int32_t*)malloc(sizeof(int32_t) * (side ? 2 : 1) * (size_t)np);
 		if (!d_map) goto done;
 		if (!slot) { fail(c, "out of host memory%s", ""); goto done; }
 		if (RA) for (int64_t g = 0; g < ng; ++g) for (int64_t i = bm->cand_off[g + 1] - RA; i < bm->cand_off[g + 1]; ++i) slot[i] = (int32_t)(nrecs - 1);
@@ -3584,13 +3594,13 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 		const int32_t K = bm->k;
 		const struct ssw_out_rec* d_rec = (const struct ssw_out_rec*)d_brec;
 		const int64_t* d_off = (const int64_t*)d_map; const int64_t* d_tbeg = (const int64_t*)(d_map + 8 * ((size_t)ng + 1));      /* (mates only) */
-		const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1) + (bm->mates ? 8 * (size_t)np : 0));
+		const int32_t* d_slot = (const int32_t*)(d_map + 8 * ((size_t)ng + 1) + (side ? 8 * (size_t)np : 0));
 		ssw_gpu_result* const fbrec = pf.fbrec;
 		if ((nfb > 0 && ssw_shim_h2d((void*)(d_rec + 2 * nj), fbrec, sizeof(ssw_gpu_result) * (size_t)nfb, c->stream)) ||
 		    ssw_shim_h2d((void*)d_off, bm->cand_off, 8 * ((size_t)ng + 1), c->stream) || ssw_shim_h2d((void*)d_slot, slot, 4 * (size_t)np, c->stream)) {
 			fail(c, "upload failed: %s", ssw_shim_last_error()); goto done;
 		}
-		if (bm->mates) {      /* the side table behind the slot map: [np] targets, [np] query length | minus strand << 31 */
+		if (side) {      /* the side table behind the slot map: [np] targets, [np] query length | minus strand << 31 */
 			uint32_t* ls = (uint32_t*)slot + np;
 			for (int64_t i = 0; i < np; ++i) ls[i] = (uint32_t)(Q->h_off[qidx[i] + 1] - Q->h_off[qidx[i]]) | (qidx[i] >= bm->nfwd ? 0x80000000u : 0u);
 			if (ssw_shim_h2d((void*)d_tbeg, src->tbeg, 8 * (size_t)np, c->stream) || ssw_shim_h2d((void*)(d_slot + np), tidx, 4 * (size_t)np, c->stream) ||
@@ -3651,6 +3661,33 @@ static int pairs_core(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs*
 			}
 		}
 		unsigned char* d_sel = d_brec + sizeof(struct ssw_out_rec) * (size_t)nrecs;      /* best: [ng] records, [ng] selections; top-k: [nout] records, [nout] positions, [ng] counts */
+		if (bm->ihist) {
+			/* ---- insert histogram: bins and counters zeroed on the call's stream, k_insertstat over a bounded grid (four workgroups per
+			   compute unit: every row strides over the fragments and the workgroup issues one atomic per counter), one download */
+			ssw_insertstat_args ia; memset(&ia, 0, sizeof ia);
+			ia.m.rec = d_rec; ia.m.cand_off = d_off; ia.m.slot = d_slot; ia.m.tbeg = d_tbeg; ia.m.tidx = d_slot + np; ia.m.len_strand = (const uint32_t*)(d_slot + 2 * np);
+			ia.m.nfrag = ng / 2; ia.m.min_score = bm->min_score; ia.min_margin = bm->min_margin; ia.max_span = bm->max_span;
+			ia.hist = (uint32_t*)(d_map + map_bytes); ia.counters = ia.hist + 3 * ((size_t)bm->max_span + 1);
+			int wgs = c->dev_cus * 4;
+			if (c->kn.istat_groups > 0) wgs = c->kn.istat_groups;
+			uint32_t cnt[SSW_ISTAT_COUNTERS];
+			if (ssw_shim_memset(ia.hist, 0, istat_bytes, c->stream)) { fail(c, "upload failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(c->ev_a, c->stream);
+			if (ssw_shim_launch_insertstat(&ia, wgs, c->stream)) { fail(c, "insertstat launch failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_shim_event_record(c->ev_b, c->stream);
+			/* (hist is contiguous with the counters: the bins to the caller, the counters to the stack) */
+			if (ssw_shim_d2h(bm->ihist, ia.hist, istat_bytes - sizeof cnt, c->stream) || ssw_shim_d2h(cnt, ia.counters, sizeof cnt, c->stream) ||
+			    ssw_shim_stream_sync(c->stream)) { fail(c, "result download failed: %s", ssw_shim_last_error()); goto done; }
+			ssw_gpu_insert_counts* ic = bm->icounts;
+			ic->n_both = cnt[SSW_ISTAT_BOTH]; ic->n_unique = cnt[SSW_ISTAT_UNIQUE]; ic->n_same = cnt[SSW_ISTAT_SAME];
+			for (int o = 0; o < 3; ++o) { ic->n_in[o] = cnt[SSW_ISTAT_IN + o]; ic->n_out[o] = cnt[SSW_ISTAT_OUT + o]; }
+			c->tm.reduce_ms = ssw_shim_event_elapsed_ms(c->ev_a, c->ev_b);
+			timing_add(&acc, &c->tm);
+			acc.t.total_ms = wall_ms() - t_start;
+			c->tm = acc.t;
+			rc = 0;
+			goto done;
+		}
 		ssw_shim_event_record(c->ev_a, c->stream);
 		if (bm->mates) {
 			ssw_matebest_args ma; memset(&ma, 0, sizeof ma);
@@ -4075,6 +4112,105 @@ int ssw_gpu_align_windows_mates(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw
 {
 	return ssw_gpu_align_windows_mates_lib(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_insert, max_insert,
 	                                       unpaired_penalty, SSW_GPU_MATES_FR, sel, results, cigar_pool, cigar_words);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Insert-size histogram (ssw_gpu_insert_hist): the mates call's groups, checks, fill and side table at flag 0, k_insertstat in place of the
+ * selection.  Device state beyond the fill's records, the slot map and the side table: 3 * (max_span + 1) bins and 16 counters, 32-bit,
+ * behind the side table (at most 768 KiB + 64 bytes); nothing per fragment comes to the host.
+ * ------------------------------------------------------------------------------------------------ */
+static int insert_hist_locked(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nf,
+                              const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                              const ssw_gpu_params* prm, int32_t min_score, int32_t min_margin, int32_t max_span, uint32_t* hist,
+                              ssw_gpu_insert_counts* counts)
+{
+	static const char who[] = "insert_hist";
+	char msg[120];
+	if (!hist || !counts) return fail_who(c, who, "NULL argument");
+	/* the fill is flag 0's whatever the caller's record says: flag, filters, filterd and mark_mismatch are not looked at */
+	ssw_gpu_params p0; memset(&p0, 0, sizeof p0);
+	if (prm) { p0 = *prm; p0.flag = 0; p0.filters = 0; p0.filterd = 0; p0.mark_mismatch = 0; }
+	int64_t np = 0;
+	const int chk = mates_check(c, who, Q, T, cand_off, nf, qidx, tidx, tbeg, tlen, nfwd, prm ? &p0 : 0, 0, 0, 0, SSW_GPU_MATES_FR, hist, counts, &np);
+	if (chk < 0) return -1;
+	if (min_margin < 0 || min_margin > 65535) {
+		snprintf(msg, sizeof msg, "min_margin = %d", min_margin);
+		return fail_who_d(c, who, "min_margin must be 0 .. 65535", msg);
+	}
+	if (max_span < 0 || max_span > SSW_GPU_INSERT_SPAN_MAX) {
+		snprintf(msg, sizeof msg, "max_span = %d", max_span);
+		return fail_who_d(c, who, "max_span must be 0 .. 65535", msg);
+	}
+	memset(hist, 0, sizeof(uint32_t) * 3 * ((size_t)max_span + 1));
+	memset(counts, 0, sizeof *counts);
+	if (chk || np == 0) { memset(&c->tm, 0, sizeof c->tm); return 0; }      /* no fragments, or empty groups only */
+	pair_src src; memset(&src, 0, sizeof src);
+	src.tidx = tidx; src.tbeg = tbeg; src.tlen = tlen; src.who = who;
+	best_mode bm; memset(&bm, 0, sizeof bm);
+	bm.cand_off = cand_off; bm.ngroups = 2 * nf; bm.min_score = min_score; bm.nfwd = nfwd;
+	bm.ihist = hist; bm.icounts = counts; bm.min_margin = min_margin; bm.max_span = max_span;
+	return pairs_core(c, Q, T, qidx, &src, np, &p0, 0, 0, 0, &bm);
+}
+
+int ssw_gpu_insert_hist(ssw_gpu_ctx* c, const ssw_gpu_seqs* Q, const ssw_gpu_seqs* T, const int64_t* cand_off, int64_t nfrag,
+                        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen, int32_t nfwd,
+                        const ssw_gpu_params* prm, int32_t min_score, int32_t min_margin, int32_t max_span, uint32_t* hist,
+                        ssw_gpu_insert_counts* counts)
+{
+	if (!c) return fail(0, "insert_hist: NULL context%s", "");
+	if (ctx_enter(c, 0, 0)) return SSW_GPU_BUSY;
+	return ctx_leave(c, insert_hist_locked(c, Q, T, cand_off, nfrag, qidx, tidx, tbeg, tlen, nfwd, prm, min_score, min_margin, max_span, hist, counts));
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * ssw_gpu_insert_fit: quartiles, outlier bounds, mean and standard deviation of one histogram row and the insert range they give (the
+ * rule of BWA-MEM's mem_pestat, the rounding pinned in integers).  Host arithmetic only.  Every floating-point operation is one
+ * correctly rounded IEEE operation on doubles -- no contraction into fused multiply-adds --, and n * S2 - S1 * S1 is formed exactly in
+ * 128 bits and converted ONCE, so that mean and sd are the same bits on every host.
+ * ------------------------------------------------------------------------------------------------ */
+static int32_t fit_kth(const uint32_t* h, int32_t ne, int64_t k)      /* k-th smallest span, 0-based: the smallest d with h[0] + .. + h[d] > k */
+{
+	int64_t run = 0;
+	for (int32_t d = 0; d < ne; ++d) { run += h[d]; if (run > k) return d; }
+	return ne - 1;
+}
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))      /* (gcc has no FP_CONTRACT pragma) */
+#endif
+int ssw_gpu_insert_fit(const uint32_t* h, int32_t ne, ssw_gpu_insert_stats* out)
+{
+#ifdef __clang__
+#pragma STDC FP_CONTRACT OFF
+#endif
+	if (!h || !out || ne < 1) return -1;
+	int64_t N = 0;
+	for (int32_t d = 0; d < ne; ++d) { N += h[d]; if (N >= ((int64_t)1 << 31)) return -1; }
+	memset(out, 0, sizeof *out);
+	out->n_total = N;
+	if (N < 10) return 1;
+	const int32_t p25 = fit_kth(h, ne, (250 * N + 499) / 1000), p50 = fit_kth(h, ne, (500 * N + 499) / 1000), p75 = fit_kth(h, ne, (750 * N + 499) / 1000);
+	const int64_t iqr = (int64_t)p75 - p25;
+	int64_t lo = p25 - 2 * iqr, hi = p75 + 2 * iqr;
+	if (lo < 1) lo = 1;
+	if (hi > ne - 1) hi = ne - 1;
+	uint64_t n = 0, S1 = 0;      /* (n < 2^31, d < 2^31: S1 < 2^62, S2 < 2^93) */
+	unsigned __int128 S2 = 0;
+	for (int64_t d = lo; d <= hi; ++d) { n += h[d]; S1 += (uint64_t)d * h[d]; S2 += (unsigned __int128)((uint64_t)d * (uint64_t)d) * h[d]; }
+	if (n == 0) return 1;
+	const unsigned __int128 num = (unsigned __int128)n * S2 - (unsigned __int128)S1 * S1;      /* n^2 x variance >= 0 (Cauchy-Schwarz) */
+	const double mean = (double)S1 / (double)n;
+	const double sd = sqrt((double)num / ((double)n * (double)n));
+	int64_t low = (int64_t)floor(mean - 4.0 * sd + 0.499), high = (int64_t)floor(mean + 4.0 * sd + 0.499);
+	if (p25 - 3 * iqr < low) low = p25 - 3 * iqr;
+	if (p75 + 3 * iqr > high) high = p75 + 3 * iqr;
+	out->n_used = (int64_t)n;
+	out->p25 = p25; out->p50 = p50; out->p75 = p75;
+	out->out_lo = (int32_t)lo; out->out_hi = (int32_t)hi;
+	out->sum = S1; out->sum2 = (uint64_t)S2;      /* (S2 fits for n_entries <= 65536) */
+	out->mean = mean; out->sd = sd;
+	out->min_insert = (int32_t)(low > 1 ? low : 1);
+	out->max_insert = (int32_t)(high < ne - 1 ? high : ne - 1);
+	return 0;
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -4541,12 +4541,17 @@ SSW_DEV mb_dig mb_get(const ssw_matebest_args& a, const unsigned char* lds, u32 
    min_insert <= E(downstream) - B(upstream) + 1 <= max_insert with B = E - len + 1.  Downstream is the minus-strand one (FR), the
    plus-strand one (RF), mate 2 on the plus and mate 1 on the minus strand (FF): x exactly when x's strand bit differs from "RF".
    a.orientation is a kernel argument: both tests are wave-uniform selects, no branch. */
+/* mb_rawspan: D of the orientation table for x of mate 1 and y of mate 2 whose strands satisfy `orientation`'s rule, 64-bit, never clamped */
+SSW_DEV long long mb_rawspan(int orientation, const mb_dig& x, const mb_dig& y)
+{
+	return ((x.ts >> 31) ^ (u32)(orientation == SSW_MATES_RF)) ? x.E - y.EL : y.E - x.EL;
+}
 /* mb_span: the same test, and the span D - min_insert of a proper combination in `idx` (0 .. max_insert - min_insert; 0 when not proper) */
 SSW_DEV bool mb_span(const ssw_matebest_args& a, const mb_dig& x, const mb_dig& y, u32& idx)
 {
 	idx = 0;
 	if ((x.ts ^ y.ts) != (a.orientation == SSW_MATES_FF ? 0u : 0x80000000u)) return false;
-	const long long ins = ((x.ts >> 31) ^ (u32)(a.orientation == SSW_MATES_RF)) ? x.E - y.EL : y.E - x.EL;
+	const long long ins = mb_rawspan(a.orientation, x, y);
 	const bool pr = ins >= (long long)a.min_insert && ins <= (long long)a.max_insert;
 	if (pr) idx = (u32)(ins - (long long)a.min_insert);
 	return pr;
@@ -4644,6 +4649,95 @@ __global__ void __launch_bounds__(256) k_matebest(ssw_matebest_args a)
 		else if (piece == 0) { v.y = 0xffffffffu; v.w = 0xffffffffu; }      /* ref_begin1, read_begin1 */
 		else if (piece == 2) { v.x = 0xffffffffu; v.y = 0xffffffffu; }      /* cigar_off */
 		((u32x4*)(a.out + 2 * f + h))[piece] = v;
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * k_insertstat (ssw_insertstat_args): the histogram of the spans between the best candidates of the two mates of every fragment
+ * (ssw_gpu_insert_hist), on k_matebest's geometry -- one DPP row of 16 lanes per fragment -- over a BOUNDED grid: row r of the grid takes
+ * fragments r, r + rows, r + 2 rows, ...; every row runs the same ceil(nfrag / rows) passes (a row past the end of the list idles through
+ * its last one), so that every lane meets every rotation.
+ *   1. The lanes stride over the fragment's n1 + n2 candidates, reading slot map and record as k_groupbest does, and keep TWO key pairs
+ *      score1 << 32 | ~position, one per mate; gb_merge's four rotations, outside the candidate loop, give every lane both mates' best and
+ *      runner-up.
+ *   2. Lane 0 decides: both mates have a best; either leads its runner-up's score1 (0: none) by min_margin; mb_form's digests of the two
+ *      winners lie on one target; then per orientation whose strand rule they satisfy the raw span (mb_rawspan) goes to its bin with one
+ *      32-bit integer atomic add, or to the out-of-range counter.  At most three bins per fragment, spread over the row of the histogram:
+ *      no staging.
+ *   3. The nine counters live in lane 0's registers across the passes; at the end the workgroup sums them in 36 bytes of LDS (LDS atomics,
+ *      16 adders) and issues ONE global atomic per non-zero counter.
+ * Integer sums: the answer does not depend on the order of arrival.
+ * ------------------------------------------------------------------------------------------------ */
+#define IS_LDS_BYTES (4 * SSW_ISTAT_COUNTERS)
+__global__ void __launch_bounds__(256) k_insertstat(ssw_insertstat_args a)
+{
+	SSW_DYN_LDS(lds);
+	const ssw_matebest_args& m = a.m;
+	const int l = (int)threadIdx.x & 15;
+	const int64_t rows = (int64_t)gridDim.x * 16, row = (int64_t)blockIdx.x * 16 + ((int64_t)threadIdx.x >> 4);
+	const int lo = m.min_score > 1 ? m.min_score : 1;
+	const int64_t bins = (int64_t)a.max_span + 1;
+	u32 cn[SSW_ISTAT_USED];
+#pragma unroll
+	for (int j = 0; j < SSW_ISTAT_USED; ++j) cn[j] = 0;
+	if (threadIdx.x < SSW_ISTAT_COUNTERS) lds_st32(lds, 4u * (u32)threadIdx.x, 0u);
+	for (int64_t f0 = 0; f0 < m.nfrag; f0 += rows) {      /* (uniform over the grid) */
+		const int64_t f = f0 + row;
+		const bool live = f < m.nfrag;
+		unsigned long long ka1 = 0, ka2 = 0, kb1 = 0, kb2 = 0;
+		u32 ne1 = 0, ne2 = 0;
+		int64_t c0 = 0;
+		int n1 = 0;
+		if (live) {
+			c0 = m.cand_off[2 * f];
+			n1 = (int)(m.cand_off[2 * f + 1] - c0);      /* (each group at most SSW_MATES_GROUP_MAX: the host's check) */
+			const int n = (int)(m.cand_off[2 * f + 2] - c0);
+			for (int p = l; p < n; p += 16) {
+				const u32* r = (const u32*)(m.rec + m.slot[c0 + p]);
+				const u32 s = r[0] & 0xffffu, st = (r[10] >> 16) & ~(u32)SSW_OUT_WORD;      /* as k_groupbest reads them */
+				if (st == 0 && (int)s >= lo) {
+					if (p < n1) {
+						const unsigned long long k = ((unsigned long long)s << 32) | (u32)~(u32)p;
+						if (k > ka1) { ka2 = ka1; ka1 = k; } else if (k > ka2) ka2 = k;
+						++ne1;
+					} else {
+						const unsigned long long k = ((unsigned long long)s << 32) | (u32)~(u32)(p - n1);
+						if (k > kb1) { kb2 = kb1; kb1 = k; } else if (k > kb2) kb2 = k;
+						++ne2;
+					}
+				}
+			}
+		}
+		gb_merge<8>(ka1, ka2, ne1); gb_merge<4>(ka1, ka2, ne1); gb_merge<2>(ka1, ka2, ne1); gb_merge<1>(ka1, ka2, ne1);
+		gb_merge<8>(kb1, kb2, ne2); gb_merge<4>(kb1, kb2, ne2); gb_merge<2>(kb1, kb2, ne2); gb_merge<1>(kb1, kb2, ne2);
+		if (!live || l != 0 || !ka1 || !kb1) continue;
+		++cn[SSW_ISTAT_BOTH];
+		const int sa = (int)(u32)(ka1 >> 32), sb = (int)(u32)(kb1 >> 32);
+		if (sa - (int)((u32)(ka2 >> 32) & 0xffffu) < a.min_margin || sb - (int)((u32)(kb2 >> 32) & 0xffffu) < a.min_margin) continue;
+		++cn[SSW_ISTAT_UNIQUE];
+		const mb_dig da = mb_form(m, c0 + (int64_t)~(u32)ka1, lo), db = mb_form(m, c0 + n1 + (int64_t)~(u32)kb1, lo);
+		if ((da.ts ^ db.ts) & 0x7fffffffu) continue;
+		++cn[SSW_ISTAT_SAME];
+		const bool opposite = ((da.ts ^ db.ts) >> 31) != 0;
+#pragma unroll
+		for (int o = SSW_MATES_FR; o <= SSW_MATES_FF; ++o) {
+			if (opposite != (o != SSW_MATES_FF)) continue;
+			const long long D = mb_rawspan(o, da, db);
+			if (D >= 0 && D <= (long long)a.max_span) {
+				atomicAdd((int*)(a.hist + o * bins + D), 1);      /* (o * bins + D < 3 * (max_span + 1): inside the histogram) */
+				++cn[SSW_ISTAT_IN + o];
+			} else ++cn[SSW_ISTAT_OUT + o];
+		}
+	}
+	__syncthreads();      /* the LDS counters are zero */
+	if (l == 0) {
+#pragma unroll
+		for (int j = 0; j < SSW_ISTAT_USED; ++j) if (cn[j]) atomicAdd((int*)(lds + 4u * (u32)j), (int)cn[j]);
+	}
+	__syncthreads();
+	if (threadIdx.x < SSW_ISTAT_USED) {
+		const u32 v = lds_ld32(lds, 4u * (u32)threadIdx.x);
+		if (v) atomicAdd((int*)(a.counters + threadIdx.x), (int)v);
 	}
 }
 
@@ -4966,6 +5060,17 @@ extern "C" int ssw_shim_launch_materescue(const ssw_materescue_args* a, void* st
 	if (args.m.nfrag <= 0) return 0;
 	if (args.max_anchors < 1 || args.max_anchors > SSW_RESCUE_ANCHORS_MAX) return -2;
 	SSW_LAUNCH(k_materescue, ssw_materescue_args, args, (args.m.nfrag + 15) / 16, 256, MB_LDS_BYTES, stream);
+	return SSW_LAUNCH_OK();
+}
+
+/* at most `workgroups` workgroups (the host's bound: a few per compute unit), never more than the fragments need */
+extern "C" int ssw_shim_launch_insertstat(const ssw_insertstat_args* a, int workgroups, void* stream)
+{
+	ssw_insertstat_args args = *a;
+	if (args.m.nfrag <= 0) return 0;
+	if (workgroups < 1 || args.max_span < 0 || !args.hist || !args.counters) return -2;
+	const int64_t need = (args.m.nfrag + 15) / 16;
+	SSW_LAUNCH(k_insertstat, ssw_insertstat_args, args, need < workgroups ? need : (int64_t)workgroups, 256, IS_LDS_BYTES, stream);
 	return SSW_LAUNCH_OK();
 }
 

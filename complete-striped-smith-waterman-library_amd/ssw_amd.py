@@ -61,6 +61,18 @@ class Timing(C.Structure):
                 ("db_long_pairs", C.c_int64), ("rescue_windows", C.c_int64)]
 
 
+class INSERT_COUNTS(C.Structure):
+    """ssw_gpu_insert_counts (include/ssw_gpu.h)."""
+    _fields_ = [("n_both", C.c_int64), ("n_unique", C.c_int64), ("n_same", C.c_int64), ("n_in", C.c_int64 * 3), ("n_out", C.c_int64 * 3)]
+
+
+class INSERT_STATS(C.Structure):
+    """ssw_gpu_insert_stats (include/ssw_gpu.h)."""
+    _fields_ = [("n_total", C.c_int64), ("n_used", C.c_int64), ("p25", C.c_int32), ("p50", C.c_int32), ("p75", C.c_int32),
+                ("out_lo", C.c_int32), ("out_hi", C.c_int32), ("sum", C.c_uint64), ("sum2", C.c_uint64), ("mean", C.c_double),
+                ("sd", C.c_double), ("min_insert", C.c_int32), ("max_insert", C.c_int32)]
+
+
 HIT_DTYPE = np.dtype([("score1", "<u2"), ("score2", "<u2"), ("ref_end1", "<i4"), ("read_end1", "<i4"), ("ref_end2", "<i4")], align=True)
 HITS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)     # ssw_gpu_hits_fn (include/ssw_gpu.h)
 
@@ -131,6 +143,29 @@ def insert_penalty_normal(mean, sd, min_insert, max_insert, match, cap):
         e = math.erfc(abs(min_insert + i - mean) / (sd * math.sqrt(2.0)))
         out[i] = cap if e <= 0.0 else min(cap, int(math.floor(0.721 * match * (-math.log(e)) + 0.5)))
     return out
+
+
+def insert_fit(hist_row, lib=None):
+    """one row of Context.insert_hist's histogram -> the dict of ssw_gpu_insert_stats' fields (quartiles, outlier bounds, mean, sd and
+    the min_insert / max_insert a mates call takes), or None when the row holds too few observations (ssw_gpu_insert_fit returns 1).
+    Host arithmetic inside the library; no device."""
+    h = np.ascontiguousarray(hist_row, dtype=np.uint32)
+    if h.ndim != 1:
+        raise ValueError("hist_row must be a 1-D array")
+    st = INSERT_STATS()
+    rc = (lib or load()).ssw_gpu_insert_fit(h.ctypes.data_as(C.c_void_p), int(h.shape[0]), C.byref(st))
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise ValueError("ssw_gpu_insert_fit: an empty row, or 2^31 observations or more")
+    return {name: getattr(st, name) for name, _ in INSERT_STATS._fields_}
+
+
+def insert_model_normal(stats, match, cap):
+    """a fit (insert_fit's dict) -> dict(min_insert, max_insert, insert_penalty) to splat into Context.align_windows_mates: the fitted
+    range and insert_penalty_normal's table for normal(mean, sd) over it.  A fit with sd == 0 is refused by insert_penalty_normal."""
+    mn, mx = int(stats["min_insert"]), int(stats["max_insert"])
+    return dict(min_insert=mn, max_insert=mx, insert_penalty=insert_penalty_normal(stats["mean"], stats["sd"], mn, mx, match, cap))
 
 
 def _mates_rebase(sel, res, co, tb):
@@ -236,6 +271,13 @@ def load(path=None):
                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_int32,
                                                              C.POINTER(PairModel), C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
         L.ssw_gpu_pool_align_windows_mates_model.restype = C.c_int
+    if hasattr(L, "ssw_gpu_insert_hist"):
+        L.ssw_gpu_insert_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.POINTER(INSERT_COUNTS)]
+        L.ssw_gpu_insert_hist.restype = C.c_int
+        L.ssw_gpu_insert_fit.argtypes = [C.c_void_p, C.c_int32, C.POINTER(INSERT_STATS)]
+        L.ssw_gpu_insert_fit.restype = C.c_int
     if hasattr(L, "ssw_gpu_search_topk"):
         L.ssw_gpu_search_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(_u32p), _i64p]
@@ -659,6 +701,40 @@ class Context(object):
         if rebase and nf > 0:
             _mates_rebase(sel, res, co, tb)
         return sel, res, cig
+
+    def insert_hist(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mat, n, max_span, min_margin=0, min_score=0, gapO=3, gapE=1,
+                    maskLen=-1, score_size=2, flag=0, filters=0, filterd=0, mark_mismatch=False):
+        """insert-size histogram of a library (ssw_gpu_insert_hist): groups, candidates and nfwd as align_windows_mates; per fragment the
+        span between the best candidates of the two mates, where both exist, lead their runners-up by min_margin and lie on one target,
+        under every orientation their strands allow -> (hist uint32 [3, max_span + 1], rows "fr" / "rf" / "ff" (MATES_ORIENTATION),
+        counts: dict of ssw_gpu_insert_counts' fields, n_in / n_out as lists of three).  flag, filters, filterd and mark_mismatch are
+        passed on and ignored by the library: the fill is flag 0's.  insert_fit turns a row into the numbers a mates call takes."""
+        co = np.ascontiguousarray(cand_off, dtype=np.int64)
+        qi = np.ascontiguousarray(qidx, dtype=np.int32)
+        ti = np.ascontiguousarray(tidx, dtype=np.int32)
+        tb = np.ascontiguousarray(tbeg, dtype=np.int64)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        if co.ndim != 1 or co.shape[0] < 1 or co.shape[0] % 2 != 1:
+            raise ValueError("cand_off must be a 1-D array of 2 nfrag + 1 offsets")
+        if qi.ndim != 1 or qi.shape != ti.shape or qi.shape != tb.shape or qi.shape != tl.shape:
+            raise ValueError("qidx, tidx, tbeg and tlen must be 1-D arrays of the same length")
+        nf = (int(co.shape[0]) - 1) // 2
+        if nf > 0 and int(co[-1]) > qi.shape[0]:      # (the library reads cand_off[2 nfrag] candidates; everything else is its own check)
+            raise ValueError("cand_off names more candidates than the arrays hold")
+        max_span = int(max_span)
+        if max_span < 0 or max_span > 65535:          # (the histogram is allocated here: the library's own bound, before the allocation)
+            raise ValueError("max_span must be 0 .. 65535")
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        p = Params(mat.ctypes.data_as(_i8p), n, gapO, gapE, flag, filters, filterd, maskLen, score_size, 1 if mark_mismatch else 0)
+        hist = np.zeros((3, max_span + 1), dtype=np.uint32)
+        cnt = INSERT_COUNTS()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self.lib.ssw_gpu_insert_hist(self.h, queries.h, targets.h, vp(co), nf, vp(qi), vp(ti), vp(tb), vp(tl), int(nfwd), C.byref(p),
+                                          int(min_score), int(min_margin), max_span, vp(hist), C.byref(cnt))
+        if rc != 0:
+            raise RuntimeError("ssw_gpu_insert_hist: " + (self.lib.ssw_gpu_strerror(rc).decode() if rc == -2 else self.error()))
+        counts = dict(n_both=cnt.n_both, n_unique=cnt.n_unique, n_same=cnt.n_same, n_in=list(cnt.n_in), n_out=list(cnt.n_out))
+        return hist, counts
 
     def align_windows_mates_rescue(self, queries, targets, cand_off, qidx, tidx, tbeg, tlen, nfwd, mate_q, mat, n, min_insert, max_insert,
                                    unpaired_penalty, max_anchors=2, anchor_min_score=0, rescue_pad=16, min_score=0, rebase=False, gapO=3, gapE=1,

@@ -70,7 +70,7 @@ typedef struct {
 	int64_t fill_cells;    /* DP cells actually evaluated by the fill kernel (padding + halo included) */
 	int64_t cells;         /* sum of readLen*refLen over the batch (the GCUPS numerator) */
 	double reduce_ms;      /* score1/score2/end-position reduction (ssw_gpu_search_topk: the device time of the k_topk selection;
-	                          ssw_gpu_align_windows_best / _topk: of the k_groupbest / k_grouptopk selection) */
+	                          ssw_gpu_align_windows_best / _topk: of the k_groupbest / k_grouptopk selection; ssw_gpu_insert_hist: of k_insertstat) */
 	double locate_ms;      /* read_end1 + reverse (begin position) passes */
 	double trace_ms;       /* banded traceback + CIGAR re-score */
 	int64_t n_word;        /* alignments decided under 16-bit semantics */
@@ -344,7 +344,9 @@ int ssw_gpu_align_windows_topk(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, co
  * Mate rescue -- aligning a mate without a usable candidate where the other mate's anchors and the insert range put it:
  * ssw_gpu_align_windows_mates_rescue below.
  * An insert-size penalty per span in place of the flat "every proper combination costs the same": ssw_gpu_align_windows_mates_model below.
- * Not provided: more than the best two combinations; estimating the insert-size distribution from data; MAPQ; a CLI option.
+ * Estimating min_insert / max_insert, the orientation and the model's table from a first batch of reads: ssw_gpu_insert_hist and
+ * ssw_gpu_insert_fit below.
+ * Not provided: more than the best two combinations; MAPQ; a CLI option.
  */
 #define SSW_GPU_MATES_GROUP_MAX 4096
 #define SSW_GPU_MATES_FR 0
@@ -473,7 +475,8 @@ int ssw_gpu_align_windows_mates_rescue(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* que
  * SSW_GPU_INSERT_TABLE_MAX (with a NULL table the range stays unlimited); every refusal of the sibling, applied to the model's fields.
  * C++: BatchAligner::AlignWindowsMates' insert_penalty argument.  Python: the insert_penalty keyword of Context.align_windows_mates,
  * Context.align_windows_mates_rescue and Pool.align_windows_mates.
- * Not provided: estimating the distribution from data; MAPQ; a pool or BatchAligner variant of the rescue call; a CLI option.
+ * The distribution itself, estimated from data: ssw_gpu_insert_hist and ssw_gpu_insert_fit below.
+ * Not provided: MAPQ; a pool or BatchAligner variant of the rescue call; a CLI option.
  */
 #define SSW_GPU_INSERT_TABLE_MAX 65536
 typedef struct {
@@ -500,6 +503,85 @@ int ssw_gpu_align_windows_mates_rescue_model(ssw_gpu_ctx* ctx, const ssw_gpu_seq
                                              int32_t max_anchors, int32_t anchor_min_score, int32_t rescue_pad,
                                              ssw_gpu_mates* sel, ssw_gpu_result* results, ssw_gpu_rescued* origin,
                                              uint32_t** cigar_pool, int64_t* cigar_words);
+
+/*
+ * Insert sizes of a library, estimated from data: the numbers every mates call above takes from its caller -- min_insert, max_insert, the
+ * orientation, the pair model's table -- bootstrapped from a first batch of reads, as BWA-MEM's mem_pestat does.  The spans are measured
+ * with THIS library's definition, the D that k_matebest tests and indexes the penalty table with (E from the flag-0 fill, B = E - len + 1
+ * an estimate), not with a mapper's TLEN from real begin positions: where reads are clipped or gapped the two differ, and a table built
+ * from one would be shifted against the D it is later indexed with.
+ * ssw_gpu_insert_hist: groups, candidates, nfwd and strand, eligibility, E and B mean what they mean for ssw_gpu_align_windows_mates_lib.
+ * Per fragment f:
+ *   1. a and b are the candidates ssw_gpu_align_windows_best would return as `best` of groups 2 f and 2 f + 1 (score1 descending, then
+ *      position ascending, over eligible candidates only).  Either group has none: the fragment stops here.  Otherwise n_both++.
+ *   2. With that call's second_score1 of either group (0 with fewer than two eligible candidates; an ineligible runner-up never counts):
+ *      score1(best) - second_score1 < min_margin for either mate stops the fragment.  Otherwise n_unique++.  min_margin == 0 admits ties,
+ *      and the first by position is the best.
+ *   3. tidx[a] != tidx[b] stops the fragment.  Otherwise n_same++.
+ *   4. For each orientation o of SSW_GPU_MATES_FR, _RF, _FF independently: when the strands of a and b satisfy o's strand rule (they
+ *      differ for FR and RF, are equal for FF), D_o is computed by the orientation table above, in 64-bit and never clamped;
+ *      0 <= D_o <= max_span: hist[o][D_o]++ and n_in[o]++; otherwise n_out[o]++.
+ * A fragment with differing strands is tested under FR and under RF.  The two spans sum to len(a) + len(b), so as a rule one lies in
+ * range and the other is negative or tiny; with inserts shorter than the two reads together both may land in range.  The caller reads the
+ * library's orientation off where the mass lies: the row with the largest n_in, its mass away from the first few bins.
+ * params->flag, filters, filterd and mark_mismatch are not looked at: the fill is flag 0's, and there is no reverse pass, traceback or
+ * CIGAR in this call.  hist is [3][max_span + 1] 32-bit counts, row index SSW_GPU_MATES_FR / _RF / _FF; on success every entry is written.
+ * On the device: the forward fill of ssw_gpu_align_windows_best over all candidates (the fallback at flag 0 for those outside the
+ * envelopes, their records uploaded beside the fill's); then k_insertstat, one 16-lane row per fragment on a bounded grid whose rows stride
+ * over the fragments: two key pairs per row, the winners' digests and spans as k_matebest forms them, 32-bit integer atomic adds into
+ * the bins (sums of integers: the answer does not depend on the order of arrival), the nine counters kept in registers and added once
+ * per workgroup.  Nothing per fragment comes to the host.
+ * Memory beyond the fill's (an output of the call, not scratch under ssw_gpu_get_budget): per candidate 48 bytes of record, 4 of slot map
+ * and 16 of side table, per fragment 16 of offsets, and 3 * (max_span + 1) + 16 32-bit words of bins and counters (at most 768 KiB + 64).
+ * Errors (-1 with a message, before anything is launched or written): every check of ssw_gpu_align_windows_mates_lib that applies -- a
+ * NULL array, cand_off[0] != 0, a decreasing cand_off, a group over SSW_GPU_MATES_GROUP_MAX, the counts beyond 0x7fffff00, nfwd outside
+ * [0, queries->count], an index or window out of range, sequences of another context --; hist or counts NULL; min_margin outside
+ * 0 .. 65535; max_span outside 0 .. SSW_GPU_INSERT_SPAN_MAX.  nfrag == 0 returns 0 with hist and counts zeroed.  SSW_GPU_BUSY, the
+ * context lock and the budget as for ssw_gpu_align_windows.
+ * ssw_gpu_last_timing: reduce_ms is the device time of k_insertstat; the fill fields as for ssw_gpu_align_windows_mates_lib; best_flagged 0.
+ * Histograms of blocks of one library simply add, entry by entry and counter by counter.
+ *
+ * ssw_gpu_insert_fit: one row of such a histogram (n_entries = max_span + 1 counts) to the numbers a mates call takes.  Host arithmetic
+ * only: no context, no device.  mem_pestat's rule with the rounding pinned in integers; with h[d] the fragments of span d,
+ *   N = sum h;  N < 10: return 1.
+ *   kth(k) = the smallest d with h[0] + .. + h[d] > k;  p25, p50, p75 = kth((250 N + 499) / 1000), kth((500 N + 499) / 1000),
+ *   kth((750 N + 499) / 1000) in integer division;  iqr = p75 - p25;
+ *   out_lo = max(p25 - 2 iqr, 1), out_hi = min(p75 + 2 iqr, n_entries - 1);
+ *   n_used, sum, sum2 = sum of h[d], d h[d], d d h[d] over out_lo <= d <= out_hi;  n_used == 0: return 1;
+ *   mean = (double)sum / (double)n_used;  sd = sqrt((double)(n_used * sum2 - sum * sum) / ((double)n_used * (double)n_used)), the
+ *   numerator exact in 128 bits and converted once;
+ *   min_insert = max(min(p25 - 3 iqr, floor(mean - 4.0 sd + 0.499)), 1);
+ *   max_insert = min(max(p75 + 3 iqr, floor(mean + 4.0 sd + 0.499)), n_entries - 1).
+ * Every floating-point step is one correctly rounded IEEE double operation (no fused multiply-add), so mean and sd are the same bits on
+ * every host.  Returns 0: fitted; 1: too few observations, *out zeroed except n_total; -1: a NULL argument, n_entries < 1, or
+ * N >= 2^31.  A table for the model from the fit: ssw_amd.insert_model_normal (Python).
+ * Not provided: a pool variant (histograms of blocks simply add); a BatchAligner method; a CLI option; MAPQ; histograms from real begin
+ * positions (the flagged records' ref_begin1).
+ */
+#define SSW_GPU_INSERT_SPAN_MAX 65535          /* max_span + 1 <= SSW_GPU_INSERT_TABLE_MAX */
+typedef struct {
+	int64_t n_both;     /* fragments in which both mates have an eligible candidate */
+	int64_t n_unique;   /* ... and the best of either mate passes min_margin */
+	int64_t n_same;     /* ... and both bests lie on one target */
+	int64_t n_in[3];    /* per orientation o: strand rule holds and 0 <= D_o <= max_span (== sum of hist[o]) */
+	int64_t n_out[3];   /* per orientation o: strand rule holds, D_o outside 0 .. max_span */
+} ssw_gpu_insert_counts;
+int ssw_gpu_insert_hist(ssw_gpu_ctx* ctx, const ssw_gpu_seqs* queries, const ssw_gpu_seqs* targets,
+                        const int64_t* cand_off, int64_t nfrag,
+                        const int32_t* qidx, const int32_t* tidx, const int64_t* tbeg, const int32_t* tlen,
+                        int32_t nfwd, const ssw_gpu_params* params, int32_t min_score,
+                        int32_t min_margin, int32_t max_span,
+                        uint32_t* hist /* [3][max_span + 1], index SSW_GPU_MATES_FR / _RF / _FF */,
+                        ssw_gpu_insert_counts* counts);
+typedef struct {
+	int64_t n_total, n_used;        /* N; n inside the outlier bounds */
+	int32_t p25, p50, p75;          /* quartiles of the spans */
+	int32_t out_lo, out_hi;         /* outlier bounds */
+	uint64_t sum, sum2;             /* S1, S2 over the spans inside them */
+	double mean, sd;
+	int32_t min_insert, max_insert; /* the range a mates call is given */
+} ssw_gpu_insert_stats;
+int ssw_gpu_insert_fit(const uint32_t* hist_row, int32_t n_entries, ssw_gpu_insert_stats* out);
 
 int ssw_gpu_last_timing(const ssw_gpu_ctx* ctx, ssw_gpu_timing* out);
 /* the first min(out_size, sizeof(ssw_gpu_timing)) bytes of the record (the rest of `out`, if any, zeroed): a binary built against
