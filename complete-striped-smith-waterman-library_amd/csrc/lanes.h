@@ -269,6 +269,38 @@ SSW_DEV u32 fr_sub_one(u32 x, u32 c)
 #endif
 	return x - c;
 }
+/* two INDEPENDENT 32-bit adds in one 64-bit add (v_lshl_add_u64): y0 = x0 + k0, y1 = x1 + k1, with k the uniform 64-bit addend that does both (a
+   scalar register pair).  Two cases, and the caller says in a comment which one holds and builds k for it: x0 + k0 NEVER carries out of bit 31 (the
+   sum of two frame values: both halves stay below 0x7C00) -- then k = (k1 : k0), the two words side by side, and a wrap of the upper word falls off
+   the end; or it ALWAYS does (k0 = -c with x0 >= c in both halves: a subtract that does not borrow) -- then k is the 64-bit negative -(c1 : c),
+   whose upper word expects that carry.  The emulation checks that the pair add equals the two 32-bit adds.  On the device the operands become one
+   opaque register pair and the caller goes on with ITS halves (x0, x1 are rebound), as in fr_sub_pair: a second live copy costs two v_mov */
+SSW_DEV void fr_add2(u32& x0, u32& x1, u32 k0, u32 k1, unsigned long long k, u32& y0, u32& y1)
+{
+	unsigned long long x = (unsigned long long)x1 << 32 | x0;
+#ifdef SSW_SIMT_EMU
+	if (x + k != ((unsigned long long)(u32)(x1 + k1) << 32 | (u32)(x0 + k0))) emu::fail("fr_add2: the pair add differs from the two 32-bit adds");
+#else
+	(void)k0; (void)k1;
+	asm("" : "+v"(x));
+	x0 = (u32)x; x1 = (u32)(x >> 32);
+#endif
+	const unsigned long long y = x + k;
+	y0 = (u32)y; y1 = (u32)(y >> 32);
+}
+/* the frame add of ONE row and an independent subtract in one 64-bit add: x0 = h0 + s0 and f -= c, on fr_add_pair's terms -- (s0 : s1) is an aligned
+   pair of profile words, s1 = -c, one lower where s0 borrows (build_profile8 writes it so), and the lower add carries exactly then */
+SSW_DEV void fr_add_pair_sub(u32 h0, u32& f, u32 s0, u32 s1, u32 c, u32& x0)
+{
+	u32 y;
+	fr_add_pair<true>(h0, f, s0, s1, x0, y);
+#ifdef SSW_SIMT_EMU
+	if (y != f - c || x0 != h0 + s0) emu::fail("fr_add_pair_sub: the pair add differs from the add and the subtract");
+#else
+	(void)c;
+#endif
+	f = y;
+}
 SSW_DEV u32 umax32(u32 a, u32 b) { return a > b ? a : b; }
 /* 0xffff in every half where a > b (unsigned), else 0: saturating difference, min(., 1), x 0xffff -- three packed instructions.  One asm
    block on the device: written with the builtins, LLVM recognises the idiom at every step (umin(x, 1) -> x != 0, ...) and emits two 16-bit

@@ -73,6 +73,7 @@ typedef struct {
 	int pipe_low_prio;      /* SSW_GPU_PIPE_PRIO=low: the extra streams of a pipelined series at the LOWEST dispatch priority (the first form of round 6; measured slower) */
 	int pipe_parts;         /* SSW_GPU_PIPE_PARTS=2..8: the number of scratch parts / streams of a pipelined series (default 2; more were measured slower) */
 	int no_fill_half;       /* SSW_GPU_FILL_HALF=0: the 16-lane kernel also where the half-row chains (k_fill8) apply */
+	int no_fill_pairs;      /* SSW_GPU_FILL_PAIRS=0: k_fill8's diagonal-gap form with every plain add on its own (fill args dg = 2: the form before the adds went in pairs) */
 	int no_fill_dg;         /* SSW_GPU_FILL_DG=0: k_fill8 opens gaps from every H (the recurrence before the diagonal-gap form) also where the scoring allows the diagonal alone */
 	int no_pipe;            /* SSW_GPU_PIPE=0: the launches of a chunked short-query bucket one after the other on the main stream (the form before round 6) */
 	int no_lit_spec;        /* SSW_GPU_LIT_SPEC=0: the lane-model kernel runs its 16-bit rules after the 8-bit ones (never both side by side: the form before round 6) */
@@ -145,7 +146,8 @@ static int env_int(const char* name, int dflt) { const char* e = getenv(name); r
 static int env_is(const char* name, char ch) { const char* e = getenv(name); return e && e[0] == ch; }
 /* The PRODUCT library (libssw.so) reads two diagnostics here -- SSW_GPU_DEBUG, SSW_GPU_CALL_TRACE -- and nothing that changes which kernel
    form runs: the form-switching hooks below exist only in the build the test suite and the measurement scripts load
-   (-DSSW_GPU_TEST_HOOKS: libssw_hooks.so, tests/emu/libssw_emu.so; same kernels object, same host source). */
+   (-DSSW_GPU_TEST_HOOKS: libssw_hooks.so, tests/emu/libssw_emu.so; same host source, and the same kernels source with the few instantiations
+   that only a hook selects -- libssw_hooks.so links a kernels object of its own for them). */
 static void knobs_load(ssw_knobs* k)
 {
 	memset(k, 0, sizeof *k);
@@ -184,6 +186,7 @@ static void knobs_load(ssw_knobs* k)
 	k->no_pipe = env_is("SSW_GPU_PIPE", '0');
 	k->no_fill_half = env_is("SSW_GPU_FILL_HALF", '0');
 	k->no_fill_dg = env_is("SSW_GPU_FILL_DG", '0');
+	k->no_fill_pairs = env_is("SSW_GPU_FILL_PAIRS", '0');
 	k->pipe_low_prio = env_is("SSW_GPU_PIPE_PRIO", 'l');
 	k->pipe_any_count = env_is("SSW_GPU_PIPE_EVEN", '0');
 	{ const int v = env_int("SSW_GPU_TRACE_W1MAX", 0); if (v >= 2 && v <= 254) k->trace_w1max = v; }
@@ -809,7 +812,10 @@ static int keyed_cmp(const void* a, const void* b)
    value of classes 1 to 3, the three class offsets and the last fold.  R = 19: 103 / 19 = 5.42.  R = 9 is
    the one instance without the blocked row frame (RowFrame8<9>::P in ssw_kernels.hip): the column frame's 6.5.
    dg (gaps from the diagonal): three per row, and per two rows one more 64-bit add, the subtract of gapO - gapE (the last row of an odd R its own).
-   R = 19: 94 / 19 = 4.947; the exact counts are in include/ssw_gpu.h.  REPORTED is max(count, 5.0): the row-frame instances are held to
+   R = 19: 94 / 19 = 4.947.  dg == 1, the plain adds in pairs (RowFrame8 in ssw_kernels.hip): one less each for the class offsets of classes 1 and 2
+   in one 64-bit subtract (R >= 7), class 3's offset beside F's last subtract (R >= 11) and the last row's diagonal add beside another of F's
+   subtracts (R >= 13) -- R = 19: 91 / 19 = 4.789; the floor that shares F's first subtract is no part of the recurrence.  dg == 2 (test hooks): the
+   form without the pairs.  The exact counts are in include/ssw_gpu.h.  REPORTED is max(count, 5.0): the row-frame instances are held to
    5.0 <= fill_ops_per_row < 6.5 by their tests */
 static double fill8_ops_per_row(int R, int dg)
 {
@@ -821,7 +827,8 @@ static double fill8_ops_per_row(int R, int dg)
 		if (k == 0) last += (n & 1) == 0;
 		else { cm += 1 + ((n & 1) == 0); ++last; }
 	}
-	const double ops = (double)((dg ? 3 : 4) * R + (dg ? 2 : 1) * ((R + 1) / 2) + (R - 1) / 4 + cm + last / 2) / R;
+	const int paired = dg == 1 ? (R >= 7) + (R >= 11) + (R >= 13) : 0;
+	const double ops = (double)((dg ? 3 : 4) * R + (dg ? 2 : 1) * ((R + 1) / 2) + (R - 1) / 4 + cm + last / 2 - paired) / R;
 	return dg && ops < 5.0 ? 5.0 : ops;
 }
 
@@ -2430,6 +2437,7 @@ static int fill_args_for(const ssw_gpu_ctx* c, const batch_call* bc, const targe
 	if (!half || B->use_x || fa->form != 3 || !ssw_frame_params(&c->kn, top, prm->gapO, prm->gapE, bc->minmat, 8, &hb, &hk)) return 0;
 	fa->fr_base = hb; fa->fr_kmask = hk;
 	fa->dg = fill8_diag_gaps(&c->kn, bc->T, half, bc->n, bc->minmat, prm->gapO, prm->gapE);
+	if (fa->dg && c->kn.no_fill_pairs) fa->dg = 2;      /* (test hooks: an instantiation of their build only) */
 	return 1;
 }
 

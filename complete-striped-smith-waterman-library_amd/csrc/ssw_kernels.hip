@@ -412,6 +412,17 @@ template <int R> struct RowFrame8 {
 	   exceptions).  R8 = 17 needs 102 registers in it, four wavefronts per SIMD where the old form's 96 give five, and 28 bytes of scratch when
 	   it is held to 96: it keeps the old form */
 	static constexpr bool DG = PAIR && R != 17;
+	/* DG instances: the plain 32-bit adds of a step two by two in one 64-bit add (fr_add2: lanes.h; DESIGN.md "The plain adds in pairs").
+	   R3: the last row of class 3, after which that class's maximum is complete and F pays its 4 x gapE.
+	   CMPAIR: (a1 : a2) - (g : 2g) in cm_finish8.  A3PAIR: (a3 : F) - (3g : 4g) after row R3.  FLPAIR: (floor : F) + (5g : -4g) after row 3, from
+	   the class-0 floor of the step before to the class-3 floor of the step after (a fifth floor register, fln in fill_body8) */
+	static constexpr int R3 = R >= 4 ? (R - 4) / 4 * 4 + 3 : -1;
+	static constexpr bool CMPAIR = DG && R >= 7;      /* (R8 = 5: a1 and a2 ARE H of rows 1 and 2, and a pair of them is two copies) */
+	static constexpr bool A3PAIR = DG && R >= 4 && R3 != 3;
+	static constexpr bool FLPAIR = DG && R >= 4 && R3 != 3 && R != 15;
+	/* XLPAIR: x of the odd last row, H of row R - 2 plus its profile word, beside F's subtract after row 7 -- the addend pair comes out of the
+	   profile as it is: the word behind the last row's, which belongs to no row, holds -4g (build_profile8) */
+	static constexpr bool XLPAIR = DG && (R & 1) && R3 >= 11;
 };
 template <int R, int... I> SSW_DEV void rows_set_cls(Rows8<R>& a, u32 v, u32 g, RowSeq<I...>) { ((row_at<I>(a) = v + (u32)RowFrame8<R>::cls(I) * g), ...); }
 SSW_DEV u32 pk_max_all(u32 a) { return a; }
@@ -427,9 +438,9 @@ template <typename... T> SSW_DEV u32 pk_max_all(u32 a, u32 b, u32 c, T... rest) 
    in E and F.  It is formed where x is -- rows 2j and 2j + 1 in one 64-bit add on the pair that fr_add_pair delivers (fr_sub_pair, nc1 = -(c1:c1)) --
    and leaves the chain h -> t -> F -> h of the next row one maximum per row.  xc goes FIRST into the maxima of three: in a dead row it is the
    one operand with bit 15 set */
-template <int R, int r, bool DG>
+template <int R, int r, bool DG, bool PR>
 SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& x2, u32& xc, u32& xc2, u32& f, u32& a0, u32& a1, u32& a2, u32& a3,
-                        u32 c1, unsigned long long nc1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3)
+                        u32 c1, unsigned long long nc1, u32 gapE2, u32 fl0, u32 fl1, u32 fl2, u32 fl3, u32& fln, u32& xl)
 {
 	typedef RowFrame8<R> F;
 	constexpr int P = F::P, k = F::cls(r), j = r / P + (k == 0), n = F::count(k);
@@ -441,7 +452,8 @@ SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& 
 		fr_add_pair<F::HPAIR>(Hr, row_at<(r + 2 < R ? r + 1 : 0)>(H), sc[(r + 1) >> 2][(r + 1) & 3], sc[(r + 1) >> 2][(r + 2) & 3], xn, x2);
 		if constexpr (DG) fr_sub_pair(xn, x2, c1, nc1, xcn, xc2);
 	} else if constexpr (r + 1 < R) {
-		xn = Hr + sc[(r + 1) >> 2][(r + 1) & 3];
+		if constexpr (PR && F::XLPAIR) xn = xl;      /* (formed after row 7, below) */
+		else xn = Hr + sc[(r + 1) >> 2][(r + 1) & 3];
 		if constexpr (DG) xcn = fr_sub_one(xn, c1);
 	}
 	const u32 h = pk_max3_fr(x, Er, f);
@@ -456,15 +468,31 @@ SSW_DEV void chain_row8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32& x, u32& 
 		Er = pk_max3_fr(Er, t, k == 0 ? fl0 : k == 1 ? fl1 : k == 2 ? fl2 : fl3);
 		f = pk_max(f, t);
 	}
-	if (r != R - 1 && F::cls(r + 1) == 0) f -= (u32)(k + 1) * gapE2;      /* back to class 0; the last row leaves f OPEN, in its own class */
+	constexpr bool fa3 = PR && F::A3PAIR && r == F::R3, ffl = PR && F::FLPAIR && r == 3, fxl = PR && F::XLPAIR && r == 7;      /* F's subtract shares a 64-bit add (below) */
+	if (!fa3 && !ffl && !fxl && r != R - 1 && F::cls(r + 1) == 0) f -= (u32)(k + 1) * gapE2;      /* back to class 0; the last row leaves f OPEN, in its own class */
 	if (j == 0) a = h;
 	else if ((j & 1) == 0) a = pk_max3_fr(a, row_at<(r >= P ? r - P : 0)>(H), h);
 	else if (j == n - 1 && k != 0) a = pk_max(a, h);      /* (class 0's single value waits for cm_finish8) */
+	if constexpr (ffl) {
+		/* (fln : f) + (5g : -4g): fln comes in as the class-0 floor of the step BEFORE, which nobody reads any more, and leaves as the class-3
+		   floor of the step AFTER, five gapE on -- both operands of the pair die in it.  Lower word: the sum is a frame value, both halves
+		   below 0x7C00 -- it NEVER carries, the addend is the two words side by side; f - 4g wraps inside the upper word */
+		const u32 n4 = 0u - 4u * gapE2;
+		fr_add2(fln, f, 5u * gapE2, n4, (unsigned long long)n4 << 32 | 5u * gapE2, fln, f);
+	} else if constexpr (fxl) {
+		/* (H[R-2] : f) + (s[R-1] : -4g): the old H of row R - 2 is read by nobody else and changes at row R - 2 only.  Lower word: it carries
+		   exactly where the profile word borrowed (fr_add_pair), and the upper word is built one lower there */
+		fr_add_pair_sub(row_at<(R >= 2 ? R - 2 : 0)>(H), f, sc[(R - 1) >> 2][(R - 1) & 3], sc[(R - 1) >> 2][((R - 1) & 3) + 1], 4u * gapE2, xl);
+	} else if constexpr (fa3) {
+		/* (a3 : f) - (3g : 4g), class 3's maximum being complete.  Lower word: a3 is an H of class 3, at least that class's floor, which holds
+		   more than 3g in both halves -- it NEVER borrows, so the 64-bit negative is the two subtracts.  cm_finish8 takes a3 as it is */
+		fr_add2(a3, f, 0u - 3u * gapE2, 0u - 4u * gapE2, 0ull - ((unsigned long long)(4u * gapE2) << 32 | 3u * gapE2), a3, f);
+	}
 	Hr = h;
 	x = xn; xc = xcn;
 }
 /* the step's column maximum in class 0 from the four classes' */
-template <int R>
+template <int R, bool PR>
 SSW_DEV u32 cm_finish8(Rows8<R>& H, u32 a0, u32 a1, u32 a2, u32 a3, u32 gapE2)
 {
 	typedef RowFrame8<R> F;
@@ -472,17 +500,23 @@ SSW_DEV u32 cm_finish8(Rows8<R>& H, u32 a0, u32 a1, u32 a2, u32 a3, u32 gapE2)
 		if constexpr (F::LEFT0) return pk_max_all(a0, row_at<F::ROW0>(H));
 		else return a0;
 	} else if constexpr (R >= 4) {
-		const u32 b1 = a1 - gapE2, b2 = a2 - 2u * gapE2, b3 = a3 - 3u * gapE2;
+		u32 b1, b2;
+		/* (a1 : a2) - (g : 2g).  Lower word: a1 is an H of class 1, at least that class's floor, which holds more than g in both halves -- it
+		   NEVER borrows, so the 64-bit negative is the two subtracts */
+		if constexpr (PR && F::CMPAIR) fr_add2(a1, a2, 0u - gapE2, 0u - 2u * gapE2, 0ull - ((unsigned long long)(2u * gapE2) << 32 | gapE2), b1, b2);
+		else { b1 = a1 - gapE2; b2 = a2 - 2u * gapE2; }
+		const u32 b3 = PR && F::A3PAIR ? a3 : a3 - 3u * gapE2;      /* (A3PAIR: chain_row8 has brought it down with F) */
 		if constexpr (F::LEFT0) return pk_max_all(a0, row_at<F::ROW0>(H), b1, b2, b3);
 		else return pk_max_all(a0, b1, b2, b3);
 	} else if constexpr (R == 3) return pk_max_all(a0, row_at<0>(H), a1 - gapE2, a2 - 2u * gapE2);
 	else if constexpr (R == 2) return pk_max_all(a0, row_at<0>(H), a1 - gapE2);
 	else return pk_max_all(a0, row_at<0>(H));
 }
-template <bool DG, int R, int... I>
+template <bool DG, bool PR, int R, int... I>
 SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32& f, u32 cm, u32 c1, unsigned long long nc1, u32 gapE2,
-                           u32 fl0, u32 fl1, u32 fl2, u32 fl3, RowSeq<I...>)
+                           u32 fl0, u32 fl1, u32 fl2, u32 fl3, u32& fln, RowSeq<I...>)
 {
+	u32 xl = 0;
 	u32 x, x2 = 0, xc = 0, xc2 = 0, a0 = cm, a1 = 0, a2 = 0, a3 = 0;
 	if constexpr (RowFrame8<R>::PAIR && R >= 2) {      /* rows 0 and 1: the incoming diagonal and the old H[0] */
 		fr_add_pair<RowFrame8<R>::HPAIR>(d, row_at<0>(H), sc[0][0], sc[0][1], x, x2);
@@ -491,8 +525,8 @@ SSW_DEV u32 chain_rows_fr8(const u32x4* sc, Rows8<R>& H, Rows8<R>& E, u32 d, u32
 		x = d + sc[0][0];
 		if constexpr (DG) xc = fr_sub_one(x, c1);
 	}
-	(chain_row8<R, I, DG>(sc, H, E, x, x2, xc, xc2, f, a0, a1, a2, a3, c1, nc1, gapE2, fl0, fl1, fl2, fl3), ...);
-	return cm_finish8<R>(H, a0, a1, a2, a3, gapE2);
+	(chain_row8<R, I, DG, PR>(sc, H, E, x, x2, xc, xc2, f, a0, a1, a2, a3, c1, nc1, gapE2, fl0, fl1, fl2, fl3, fln, xl), ...);
+	return cm_finish8<R, PR>(H, a0, a1, a2, a3, gapE2);
 }
 
 /* profile of two pairs: word ((b*C + c)*16 + chain*8 + p)*4 + k = scores of residue b against rows p*R + 4c + k of pair `chain`.  All 8R rows
@@ -511,16 +545,22 @@ SSW_DEV void build_profile8(unsigned char* lds, int first, int nthreads, const i
 		const int c = rem >> 6, l = (rem & 63) >> 2, k = rem & 3;
 		const int ch = l >> 3, r = c * 4 + k, row = (l & 7) * R + r;
 		u32 v;
-		if (b == n || (ch && !live1)) v = fr_pack(FR_DEAD, FR_DEAD);
+		const bool dead = b == n || (ch && !live1);
+		const auto entry = [&](int r, int row) {      /* (live entries only) */
+			int lo = 0, hi = 0;
+			if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
+			if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
+			const int fr = (1 + RowFrame8<R>::cls(r) - (r == 0 ? RowFrame8<R>::KL : RowFrame8<R>::cls(r - 1))) * gapE;
+			return fr_pack(lo + fr, hi + fr);
+		};
+		if (RowFrame8<R>::XLPAIR && r == R) {
+			/* the word behind the last row's is the upper word of ITS pair: F's -4 gapE (chain_row8, XLPAIR), one lower where the last row's
+			   word borrows, as below; a dead word neither borrows nor carries */
+			v = 0u - 4u * pk_dup(gapE);
+			if (!dead && fr_borrows(entry(R - 1, row - 1))) v -= 1u;
+		} else if (dead) v = fr_pack(FR_DEAD, FR_DEAD);
 		else if (r >= R) v = 0;
 		else {
-			const auto entry = [&](int r, int row) {
-				int lo = 0, hi = 0;
-				if (row < len[2 * ch]) lo = mat[b * n + q[2 * ch][row]];
-				if (q[2 * ch + 1] && row < len[2 * ch + 1]) hi = mat[b * n + q[2 * ch + 1][row]];
-				const int fr = (1 + RowFrame8<R>::cls(r) - (r == 0 ? RowFrame8<R>::KL : RowFrame8<R>::cls(r - 1))) * gapE;
-				return fr_pack(lo + fr, hi + fr);
-			};
 			v = entry(r, row);
 			/* the upper word of a pair (fr_add_pair) lends 1 to a negative lower word; the last row of an odd R is added alone */
 			if (RowFrame8<R>::PAIR && (r & 1) && fr_borrows(entry(r - 1, row - 1))) v -= 1u;
@@ -610,10 +650,11 @@ SSW_DEV void fill_flush8(unsigned char* lds, u32 rb, int base, int l16, int stor
 	}
 }
 
-template <int R, bool DG>
+template <int R, bool DG, bool PR>
 SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* lds)
 {
 	static_assert(!DG || RowFrame8<R>::DG, "gaps from the diagonal: no such instance");
+	static_assert(!PR || DG, "the plain adds in pairs: a part of the form with gaps from the diagonal");
 	typedef ChainGeom<R> G;
 	constexpr int C = G::C;
 	const int tid = (int)threadIdx.x, l16 = tid & 15, grp = tid >> 4, ch = l16 & 1, pos = l16 >> 1;
@@ -683,6 +724,8 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 	constexpr int KL = RowFrame8<R>::KL;
 	const u32 klg = (u32)KL * a.gapE2;
 	u32 fl0 = zero0 + a.gapE2, fl1 = fl0 + a.gapE2, fl2 = fl1 + a.gapE2, fl3 = fl2 + a.gapE2;
+	constexpr bool FLPAIR = PR && RowFrame8<R>::FLPAIR;
+	u32 fln = fl3 + a.gapE2;      /* FLPAIR: the class-3 floor of the step after; during rows 0 to 3 the floor that has just left class 0, from which chain_row8 forms it beside F's subtract */
 	typedef typename RowSeqTo<R>::type Rows;
 	Rows8<R> H, E;
 	rows_set_cls(H, zero0, a.gapE2, Rows()); rows_set_cls(E, fl0, a.gapE2, Rows());
@@ -701,6 +744,7 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 			const u32 k = (u32)(a.fr_kmask + 1) * a.gapE2;
 			rows_sub(H, k, Rows()); rows_sub(E, k, Rows());
 			Hlast -= k; Fout -= k; cmout -= k; hsave -= k; fl0 -= k; fl1 -= k; fl2 -= k; fl3 -= k;
+			if constexpr (FLPAIR) fln -= k;
 		}
 		{   /* stage target columns [s0+16, s0+32), prefetch [s0+32, s0+48) */
 			const int p = (s0 + 16 + l16) & 63;
@@ -727,10 +771,11 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 			/* head of the chain: the zero that row_shr fills in becomes phi(column) in class KL, which is that class's floor of the step before */
 			const u32 hin = xl_row_shr2_umax(Hlast, KL == 0 ? fl0 : KL == 1 ? fl1 : KL == 2 ? fl2 : fl3);
 			if constexpr (RowFrame8<R>::P == 1) fl0 += gE;
+			else if constexpr (FLPAIR) { const u32 old = fl0; fl0 = fl1; fl1 = fl2; fl2 = fl3; fl3 = fln; fln = old; }
 			else { const u32 up = fl3 + gE; fl0 = fl1; fl1 = fl2; fl2 = fl3; fl3 = up; }
 			xl_row_shr2_sub_keep(fin, Fout, gEv);
 			u32 f = fin, d = hsave;
-			const u32 cm = chain_rows_fr8<DG>(sc, H, E, d, f, xl_row_shr2_zero(cmout), gO, ngO, gE, fl0, fl1, fl2, fl3, Rows());
+			const u32 cm = chain_rows_fr8<DG, PR>(sc, H, E, d, f, xl_row_shr2_zero(cmout), gO, ngO, gE, fl0, fl1, fl2, fl3, fln, Rows());
 			hsave = hin; Hlast = row_at<R - 1>(H); Fout = f; cmout = cm;
 			if (pos == 7) {      /* raw: the frame of this step (hprev: one gapE below it) */
 				lds_st32(lds, park + 4u * j, cm); lds_st32(lds, park + 64u + 4u * j, f); lds_st32(lds, park + 128u + 4u * j, hprev);
@@ -746,11 +791,12 @@ SSW_DEV void fill_body8(const ssw_fill_args& a, const int bid, unsigned char* ld
 
 /* register budget per class as for k_fill: up to 9 rows per position 72 registers, up to 15 96, beyond that 128.  (R8 = 19 held to 96
    registers -- five wavefronts per SIMD, with spills -- measured 2.9 % slower than at 118 registers and four: docs/NOTEBOOK.md) */
-template <int R, bool DG>
+/* PR: the plain adds in pairs (RowFrame8).  Every dg instance has them; the dg form without them is instantiated for the test hooks only */
+template <int R, bool DG, bool PR = DG>
 __global__ void __launch_bounds__(256) SSW_WAVES_PER_EU(R <= 9 ? 7 : R <= 15 ? 5 : 4, 8) k_fill8(ssw_fill_args a)
 {
 	SSW_DYN_LDS(lds);
-	fill_body8<R, DG>(a, (int)blockIdx.x, lds);
+	fill_body8<R, DG, PR>(a, (int)blockIdx.x, lds);
 }
 
 /* k_fillm: SEVERAL geometry buckets in one launch (round 4).  A batch of mixed read lengths -- the reference's own benchmark: 1000 reads of
@@ -4942,7 +4988,13 @@ extern "C" int ssw_shim_launch_fill(int R, const ssw_fill_args* a, void* stream)
 }
 
 /* half-row chains: R8 = ceil(len / 8) rows per position, odd values up to 23; frame form only.  a->dg: gaps from the diagonal only (the
-   instances with RowFrame8::DG: every R8 but 9 and 17) */
+   instances with RowFrame8::DG: every R8 but 9 and 17); a->dg == 2: that form with every plain add on its own, as it was before the adds
+   went in pairs -- an instantiation of the test hooks' build (and the emulator's) only, SSW_GPU_FILL_PAIRS=0 */
+#if defined(SSW_GPU_TEST_HOOKS) || defined(SSW_SIMT_EMU)
+#define FILL8_UNPAIRED(r) if (args.dg == 2) SSW_LAUNCH((k_fill8<r, RowFrame8<r>::DG, false>), ssw_fill_args, args, grid, 256, ldsb, stream); else
+#else
+#define FILL8_UNPAIRED(r) if (args.dg == 2) return -2; else
+#endif
 extern "C" int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* stream)
 {
 	ssw_fill_args args = *a;
@@ -4952,7 +5004,7 @@ extern "C" int ssw_shim_launch_fill8(int R8, const ssw_fill_args* a, void* strea
 	switch (R8) {
 #define X(r) case r: { const size_t ldsb = (size_t)(args.n + 1) * ChainGeom<r>::PSTRIDE + 16 * CHAIN8_BYTES; \
 		if (args.dg && !RowFrame8<r>::DG) return -2; \
-		if (args.dg) SSW_LAUNCH((k_fill8<r, RowFrame8<r>::DG>), ssw_fill_args, args, grid, 256, ldsb, stream); \
+		FILL8_UNPAIRED(r) if (args.dg) SSW_LAUNCH((k_fill8<r, RowFrame8<r>::DG>), ssw_fill_args, args, grid, 256, ldsb, stream); \
 		else SSW_LAUNCH((k_fill8<r, false>), ssw_fill_args, args, grid, 256, ldsb, stream); } break;
 		X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23)
 #undef X

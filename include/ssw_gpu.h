@@ -80,8 +80,11 @@ typedef struct {
 	double fill_ops_per_row; /* VALU instructions of the recurrence per (row, column) of a query pair in that kernel: 6.5 (column frame) / 7.5 / 8.5 / 9;
 	                            k_fill8<R> (column frame + blocked row frame, one diagonal add per two rows): its own count per instance, 5.42 at R = 19.
 	                            "k_fill8<R,frame> dg" (gaps open from the diagonal candidate only, where the scoring and the target allow it):
-	                            max(count, 5.0), the counts being 6/1, 17/3, 28/5, 38/7, 56/11, 66/13, 76/15, 94/19 = 4.947, 104/21 = 4.952 and
-	                            114/23 = 4.957 -- the three largest instances report 5.0; R = 9 and R = 17 have no such form.
+	                            max(count, 5.0), the counts being 6/1, 17/3, 28/5, 37/7, 54/11, 63/13 = 4.846, 73/15 = 4.867, 91/19 = 4.789,
+	                            101/21 = 4.810 and 111/23 = 4.826 -- the instances from R = 11 on report 5.0; R = 9 and R = 17 have no such form.
+	                            The REPORTED value of two instances moved when the adds went in pairs: R = 7 reports 37/7 = 5.286 (was 38/7 = 5.429)
+	                            and R = 11 reports 5.0 (was 56/11 = 5.091); every other instance reports what it did.
+	                            (With every plain add on its own, as before the adds went in pairs: 38/7, 56/11, 66/13, 76/15, 94/19, 104/21, 114/23.)
 	                            k_chainq<R,pairs,..> reports the batch fill's 6.5 / 9 although it merges the two halves' profile entries per row
 	                            (one more instruction): a roofline computed from it is understated for that kernel */
 	int32_t fill_rows_per_lane;
